@@ -22,7 +22,16 @@ Synthetic data: darknet-format random weights (utility/synth.py, seeds
 so that ~32 boxes/frame survive (the "32 tracks" of configs[2]); frames are
 low-frequency backgrounds with moving rectangles.
 
-Prints ONE JSON line on rank 0 (contract in the task statement) including
+A plain run sets up, warms up, times --steps steps and prints ONE JSON line on rank 0: metric, value (frames/s), unit,
+higher_is_better, dtype, ms_per_step (one timed step), the configuration and, for N > 1, the per-rank figures.
+  --dump-outputs DIR  after the timed steps, writes what the LAST timed step computed -- the arrays a caller of the
+                      step receives (track: boxes, counts, ids, nids, netout) -- as DIR/<name>.npy, float32 (float
+                      results) or float64 (integer results); an array over its share of 64 MB is replaced by a fixed
+                      seeded sample of its flattened elements (the same elements for the same arguments).
+  --full              everything else, behind the headline steps (off by default): the instrumented per-kernel pass
+                      (kernels, roofline, --layer-report) and, at --gpus 1 for the track workload, the extra
+                      configurations (--no-extra) and the CPU baseline (--no-cpu-baseline).
+With --full the line also holds
   roofline     -- achieved / peak / frac / traffic of the DOMINANT kernel family (the one with the most HIP-event
                   time inside the timed region; with the default policy wino_gemm_s3_kernel: executed fp16 MFMA
                   FLOPs -- three per fp32 multiply-add of two-term split operands -- against the 2.5 PFLOP/s dense
@@ -286,6 +295,32 @@ def detect_batch8_extra(device, H, W, seed0):
     return out
 
 
+DUMP_BYTES = 60 * 10 ** 6       # under 64 MB with the .npy headers
+
+
+def dump_outputs(dirname, res):
+    """--dump-outputs: every tensor of a step's result as <dirname>/<name>.npy -- float32 for float results, float64 for
+    integer ones (exact) -- within DUMP_BYTES in all: an array over its equal share is replaced by a fixed seeded sample
+    of its flattened elements, in index order."""
+    if torch.is_tensor(res):
+        items = [("output", res)]
+    elif isinstance(res, dict):
+        items = [(k, v) for k, v in sorted(res.items()) if torch.is_tensor(v)]
+    else:
+        items = [("output%d" % i, v) for i, v in enumerate(res) if torch.is_tensor(v)]
+    os.makedirs(dirname, exist_ok=True)
+    for name, t in items:
+        dtype, size = (torch.float32, 4) if t.is_floating_point() else (torch.float64, 8)
+        cap = DUMP_BYTES // len(items) // size
+        flat = t.detach().reshape(-1)
+        if flat.numel() > cap:
+            idx = np.sort(np.random.default_rng(0).choice(flat.numel(), cap, replace=False))
+            arr = flat[torch.from_numpy(idx).to(flat.device)].to(dtype).cpu().numpy()
+        else:
+            arr = t.detach().to(dtype).cpu().numpy()
+        np.save(os.path.join(dirname, name + ".npy"), arr)
+
+
 def _time_steps(step, warmup, steps):
     for _ in range(warmup):
         step()
@@ -371,162 +406,9 @@ def load_traffic(clips, T, size):
     return best
 
 
-def main():
-    # the classes print a model summary like Keras does; stdout must carry ONLY the JSON line
-    import contextlib
-    with contextlib.redirect_stdout(sys.stderr):
-        out = _run()
-    if out is not None:
-        print(json.dumps(out), flush=True)
-
-
-def _run():
-    ap = argparse.ArgumentParser()
-    ap.add_argument("--gpus", type=int, default=1)
-    ap.add_argument("--steps", type=int, default=5)
-    ap.add_argument("--prof-steps", type=int, default=5, help="steps of the separate instrumented pass (per-kernel HIP events) behind the timed steps")
-    ap.add_argument("--warmup", type=int, default=2)
-    ap.add_argument("--workload", choices=["track", "detect", "tiny"], default="track")
-    ap.add_argument("--seqs", type=int, default=32, help="sequences per step (tiny)")
-    ap.add_argument("--clips", type=int, default=48, help="clips per GPU per step (track)")
-    ap.add_argument("--T", type=int, default=30)
-    ap.add_argument("--size", type=int, default=416)
-    ap.add_argument("--graphs", dest="graphs", action="store_true", default=True,
-                    help="dt_graph_enable for the timed steps: hipGraph replay of the detector trunk / recurrences (default; the instrumented pass behind them runs plain launches)")
-    ap.add_argument("--no-graphs", dest="graphs", action="store_false", help="plain launches in the timed steps too")
-    ap.add_argument("--boxes", type=int, default=32, help="boxes/frame the synthetic tracker head is calibrated to (track)")
-    ap.add_argument("--batch", type=int, default=8, help="frames per step (detect)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--h2d", action="store_true", help="also copy the frames from pinned host memory every step (PCIe-inclusive rate; never the headline value)")
-    ap.add_argument("--cpu-frames", type=int, default=30)
-    ap.add_argument("--shard", choices=["clip", "frame"], default="clip",
-                    help="N>1 (track): clip = each rank owns --clips whole clips (weak scaling, no data-path collective); "
-                         "frame = --clips clips in TOTAL, every rank runs the detector on its time steps of all of them, "
-                         "per-frame rows all-gathered, recurrence on each clip's owner (strong scaling; configs[4])")
-    ap.add_argument("--no-extra", action="store_true", help="skip the configs[1] extra block")
-    ap.add_argument("--layer-report", default=None, help="write a per-layer table (HIP-event times) to this file")
-    args = ap.parse_args()
-
-    if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
-        # typed as a plain command: become the launcher -- one rank per GPU of this node under torch.distributed.run
-        # (backend nccl = RCCL unless DT_DIST_BACKEND says otherwise); rank 0 of the child job prints the JSON line to
-        # the stdout this process inherited
-        import socket
-        import subprocess
-        with socket.socket() as sk:
-            sk.bind(("127.0.0.1", 0))
-            port = sk.getsockname()[1]
-        env = dict(os.environ, HSA_ENABLE_IPC_MODE_LEGACY=os.environ.get("HSA_ENABLE_IPC_MODE_LEGACY", "0"))
-        cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", str(args.gpus),
-               "--master-addr", "127.0.0.1", "--master-port", str(port), os.path.abspath(__file__)] + sys.argv[1:]
-        rc = subprocess.call(cmd, env=env, stdout=sys.__stdout__, stderr=sys.__stderr__)
-        if rc != 0:
-            sys.exit(rc)
-        return None
-    rank, world, local = init_from_env()
-    assert world == args.gpus, "--gpus %d but WORLD_SIZE=%d: launch with torchrun --nproc-per-node %d, or run " \
-                               "`python bench.py --gpus %d` without a launcher" % (args.gpus, world, args.gpus, args.gpus)
-    assert torch.cuda.is_available(), "bench.py needs an MI355X; there is no CPU fallback"
-    device = torch.device("cuda", torch.cuda.current_device())
-    H = W = args.size
-
-    if args.workload == "track":
-        frame_shard = args.shard == "frame" and world > 1
-        # frame-shard: ONE set of --clips clips for the whole job; a rank keeps only its own time steps of them resident
-        # (sharded ingest: t mod N = rank) once the head is calibrated
-        frames = make_frames(args.clips, args.T, H, W, device, seed0=42 + (0 if frame_shard else 100 * rank))
-        trk, blob, tw = build_tracker(H, W, args.T, args.boxes, frames)
-        if frame_shard:
-            from parallel import frame_shard_times
-            frames = frames[:, frame_shard_times(args.T, rank, world)].contiguous()
-        xstats = {}
-        ctx = trk.model.ctx
-        frames_per_step = args.clips * args.T / (world if frame_shard else 1)
-        gflop_per_frame = GFLOP_TRACK_416 * (H * W) / (416.0 * 416.0)
-
-        host_frames = frames.cpu().pin_memory() if args.h2d else None
-
-        def step():
-            src = frames
-            if host_frames is not None:
-                frames.copy_(host_frames, non_blocking=True)     # same stream: serialised in front of the step
-            xstats.clear()
-            if frame_shard:
-                return track_clips_frame_sharded(trk, src, cap=max(128, 2 * args.boxes), T=args.T, stats=xstats)
-            res = trk.track_clips(src, cap=max(128, 2 * args.boxes))
-            if world > 1:
-                res = gather_detections(res, n_clips_max=args.clips, ctx=ctx, stats=xstats)
-            return res
-    elif args.workload == "tiny":
-        # BASELINE.json configs[3]: TinyTracker (ROLO-style) over 64-frame sequences, FRAME-sharded:
-        # every rank runs detector + pooling on its slice of the time axis of all sequences, the
-        # small per-frame rows are all-gathered, the LSTM over T runs replicated.  Strong scaling.
-        from models_tracking.TinyTracker import TinyTracker
-        from parallel import gather_frame_rows
-        C, T = 80, 64
-        assert T % world == 0
-        blob = synth.synth_darknet_blob(C, seed=1234)
-        det = KerasYOLO({'LABELS': KerasYOLO.LABELS_COCO, 'BATCH_SIZE': 4, 'IMAGE_H': H, 'IMAGE_W': W,
-                         'GRID_H': H // 32, 'GRID_W': W // 32}, weights=blob)
-        ctx = det.model.ctx
-        cfg = {"model_tracker": {"name": "TinyTracker", "lstm_units": 512, "sequence_length": T},
-               "train": {"pool": "Global", "batch_size": 4}}
-        tt = TinyTracker(cfg, feature_dims=(H // 16, W // 16, 512), weights=synth.synth_tiny_weights(512), ctx=ctx)
-        t_loc = T // world
-        frames = make_frames(args.seqs, t_loc, H, W, device, seed0=42 + 100 * rank)
-        frames_per_step = args.seqs * t_loc
-        gflop_per_frame = GFLOP_DETECT_416_C80 * (H * W) / (416.0 * 416.0)
-        tw = None
-        xstats = {}
-
-        def step():
-            rows, _ = tt.frame_rows(frames.reshape(args.seqs * t_loc, H, W, 3), det)
-            rows = gather_frame_rows(rows.reshape(args.seqs, t_loc, -1).contiguous())
-            return ctx.tiny_sequence(rows)
-    else:
-        C = 80
-        blob = synth.synth_darknet_blob(C, seed=1234)
-        det = KerasYOLO({'LABELS': KerasYOLO.LABELS_COCO, 'BATCH_SIZE': args.batch, 'IMAGE_H': H, 'IMAGE_W': W,
-                         'GRID_H': H // 32, 'GRID_W': W // 32}, weights=blob)
-        ctx = det.model.ctx
-        frames = make_frames(1, args.batch, H, W, device, seed0=42 + 100 * rank)[0].contiguous()
-        frames_per_step = args.batch
-        gflop_per_frame = GFLOP_DETECT_416_C80 * (H * W) / (416.0 * 416.0)
-        tw = None
-        xstats = {}
-
-        def step():
-            return det.detect(frames)
-
-    def sync_all():
-        torch.cuda.synchronize()
-        if world > 1:
-            dist.barrier()
-        torch.cuda.synchronize()
-
-    if args.graphs:
-        ctx.graph_enable(True)        # captured during the warm-up steps (second call per shape), replayed afterwards
-    res = None
-    for _ in range(max(args.warmup, 3) if args.graphs else args.warmup):
-        res = step()
-    sync_all()
-    # ---- the contract number: K steps with NO per-launch instrumentation (HIP events around every launch cost ~1 %) ----
-    ctx.profile_reset()
-    ctx.profile_enable(False)
-    sync_all()
-    t0 = time.perf_counter()
-    for _ in range(args.steps):
-        res = step()
-    sync_all()
-    elapsed = time.perf_counter() - t0
-    per_rank_ms = None
-    if world > 1:
-        rec = [None] * world
-        dist.all_gather_object(rec, {"rank": rank, "ms_per_step": 1e3 * elapsed / args.steps})      # every rank's own clock, both shard modes
-        per_rank_ms = rec
-        tmax = torch.tensor([elapsed], dtype=torch.float64, device=device if dist.get_backend() == "nccl" else "cpu")
-        dist.all_reduce(tmax, op=dist.ReduceOp.MAX)
-        elapsed = float(tmax.item())
+def instrumented_report(args, ctx, step, sync_all, rank):
+    """--full: the per-kernel table and the roofline, from a pass of their own behind the timed steps.  Returns the fields of
+    the JSON line that come from it."""
     # ---- a SEPARATE instrumented pass for the per-kernel table and the roofline: HIP events around every launch, on the launch
     # stream (with --graphs: none -- profiling bypasses the replayed graphs, so the table then describes plain launches) ----
     prof_steps = max(1, min(args.prof_steps, args.steps))
@@ -537,20 +419,10 @@ def _run():
     sync_all()
     t1 = time.perf_counter()
     for _ in range(prof_steps):
-        res = step()
+        step()
     sync_all()
     elapsed_prof = time.perf_counter() - t1
     ctx.profile_enable(False)
-
-    # frame-shard: where each rank spent the last step -- the part spread over all ranks (detector + input projection) vs the
-    # owner stage (row wait + recurrence + decode on the clips it owns; a rank that owns none idles there)
-    stage_ms = None
-    if args.workload == "track" and args.shard == "frame" and world > 1:
-        mine = frame_shard_stage_ms(xstats)
-        rec = [None] * world
-        dist.all_gather_object(rec, {"rank": rank, "clips_owned": xstats.get("clips_owned"),
-                                     "sharded_stage_ms": mine[0] if mine else None, "owner_stage_ms": mine[1] if mine else None})
-        stage_ms = rec
 
     kern = {}
     for name in ("conv_gemm_s3", "conv_igemm", "conv_direct_h2", "conv_fused", "wino_input", "wino_output", "conv1_direct", "convlstm_gates", "decode_nms", "associate", "splitk_reduce", "pool",
@@ -687,10 +559,6 @@ def _run():
                                                     "executed_tflops": p["flops"] / (p["ms"] * 1e-3) / 1e12,
                                                     "implementation_GBps": p["bytes"] / (p["ms"] * 1e-3) / 1e9}
         families[fam]["layers"] = layers
-    boxes_per_frame = None
-    if args.workload == "track" and res is not None and isinstance(res, dict):
-        boxes_per_frame = float(res["counts"].float().mean().item())
-
     if rank == 0 and args.layer_report:
         with open(args.layer_report, "w") as f:
             f.write("# per-layer HIP-event times of the instrumented pass (%d steps, behind the %d un-instrumented headline steps); EXECUTED MFMA FLOP / algorithmic bytes\n" % (prof_steps, args.steps))
@@ -702,6 +570,240 @@ def _run():
                 f.write("%-32s %8d %12.4f %10.2f %10.1f\n" % (name, p["launches"], p["ms"] / prof_steps,
                                                             p["flops"] / (p["ms"] * 1e-3) / 1e12,
                                                             p["bytes"] / (p["ms"] * 1e-3) / 1e9))
+    return {
+        "timing": {"ms_per_step_instrumented": 1e3 * elapsed_prof / prof_steps, "instrumented_steps": prof_steps,
+                   "note": "kernels / roofline come from the separate instrumented pass (a HIP event pair around each of ~280 launches per step)"},
+        "dtype_detail": (("fp32 storage, fp32 accumulation everywhere; the Winograd-form and 1x1 layers' GEMMs form each fp32 product from THREE fp16 MFMA "
+                          "partial products (lo*hi + hi*lo + hi*hi) of 2-term split operands: x * 2^s = hi + lo with hi = fp16(x 2^s), lo = fp16(x 2^s - hi), "
+                          "|x 2^s - hi - lo| <= 2^-23 |x 2^s| and zero for three elements in four; s per tensor from its MEASURED max |x| (taken by the "
+                          "producing kernel's epilogue), per Winograd position for the weights; accumulators scaled back by the exact inverse power of two.  "
+                          "Error against float64 at every benched GEMM shape: rms 5.5e-8 / max 1.0e-6 of sum |u||v| -- below the six-product bf16 form "
+                          "(6.8e-8 / 1.1e-6) and the fp32 library GEMM (8.7e-8 / 1.6e-6) on the same data, asserted in pytest -m gpu "
+                          "(test_split_bf16_gemm_benched_shapes_against_float64; profiles/parity_r06_gemm_split_f64.txt).  extra.track_bf16x3 / "
+                          "extra.track_fp32_mfma_only: the same step in the round-5 form and on the fp32 MFMA instruction only") if s3_h2 else
+                         ("fp32 storage, fp32 accumulation everywhere; the F(6x6,3x3) layers' GEMMs form each fp32 product from six bf16 MFMA "
+                          "partial products of 3-term split operands (x = x1 + x2 + x3, exact to 2^-25 |x|): error against float64 no "
+                          "larger than the fp32 MFMA path's (DT_S3=0), which the parity tests assert")) if s3["ms"] > 0 else
+                        "fp32 storage, fp32 MFMA arithmetic, fp32 accumulation",
+        "roofline": None if dominant is None else {
+            "bound": "mfma",
+            # the four contract fields describe ONE family -- the one with the most time in the step -- and nothing else;
+            # every other figure of a family lives in families[<name>], computed from that family's own launches only
+            "kernel": families[dominant]["kernel"] + " -- " + families[dominant]["instruction"],
+            "dominant_family": dominant,
+            "achieved": families[dominant]["achieved"], "peak": families[dominant]["peak_tflops"], "unit": "TFLOP/s",
+            "frac": families[dominant]["frac"],
+            "traffic": families[dominant]["traffic_bytes_per_launch"],
+            "traffic_unit": "bytes per launch of the dominant family (FETCH_SIZE x in-run calibration + WRITE_SIZE; beyond-L2, incl. Infinity Cache hits)",
+            "traffic_source": os.path.relpath(tr[0], ROOT) if tr is not None else None,
+            "traffic_per_step": tr[1].get("traffic_bytes_per_step") if tr is not None else None,
+            "families": families, "transforms": transforms,
+            "frac_whole_conv_path": conv_path_pipe_frac,
+            "whole_conv_path": {"executed_fp32_mfma_tflop_per_step": conv_path_flops / steps / 1e12,
+                                "executed_bf16_mfma_tflop_per_step": conv_path_bf16 / steps / 1e12,
+                                "fp32_equivalent_tflops": ((conv_path_flops + s3["flops"] / s3_products + c3h2["flops"] / 3.0 + (conv1["flops"] / 3.0 if conv1_bf16 else 0.0)) / (conv_path_ms * 1e-3) / 1e12)
+                                if conv_path_ms > 0 else None,
+                                "ms_per_step": conv_path_ms / steps,
+                                "direct_form_tflop_per_step": direct_form_all / steps / 1e12,
+                                "direct_form_tflops": (direct_form_all / (conv_path_ms * 1e-3) / 1e12) if conv_path_ms > 0 else None,
+                                "direct_form_bytes_per_step": direct_form_bytes_all / steps,
+                                "implementation_bytes_per_step": (s3["bytes"] + ig["bytes"] + wino_in["bytes"] + wino_out["bytes"] + fused["bytes"] + c3h2["bytes"] + conv1["bytes"]) / steps},
+            "note": "achieved / peak / frac / traffic = the DOMINANT kernel family (most time in the step): MFMA FLOPs its launches execute / "
+                    "their HIP-event time, against the dense peak of the instruction it issues (pipe utilisation, <= 1). Per family "
+                    "(families.*): executed = FLOPs on the matrix pipe; algorithmic = SURVEY.md 8d direct-form FLOPs (2MKN of the "
+                    "reference's layer) of the layers THAT family's launches computed -- the 3x3 layers run in Winograd form "
+                    "(F(6x6,3x3): 1.78 multiplies per output instead of 9; fused F(4x4,3x3): 2.25), so achieved_algorithmic exceeds "
+                    "achieved; wino_gemm_s3 carries every fp32 operand as two fp16 terms of the scaled operand (three bf16 terms under DT_S3_H2=0) and forms each product from three (six) 16-bit "
+                    "MFMA partial products with fp32 accumulation (fp32 accuracy, tests/test_gpu_parity.py::"
+                    "test_split_bf16_gemm_benched_shapes_against_float64): fp32_equivalent_tflops = executed / mfma_products_per_multiply. "
+                    "implementation_* = bytes the kernels move by their own count (V + U + M' for the GEMMs); traffic_* = PMC "
+                    "measurement (profiles/). transforms = the HBM-bound Winograd transform kernels around the GEMMs. "
+                    "frac_whole_conv_path = time the matrix pipe needs at its peaks for everything the conv path executes "
+                    "(16-bit FLOPs / 2500 + fp32 FLOPs / 157.3) / the conv path's time incl. transforms."},
+        "kernels": kern
+    }
+
+
+def main():
+    # the classes print a model summary like Keras does; stdout must carry ONLY the JSON line
+    import contextlib
+    with contextlib.redirect_stdout(sys.stderr):
+        out = _run()
+    if out is not None:
+        print(json.dumps(out), flush=True)
+
+
+def _run():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--gpus", type=int, default=1)
+    ap.add_argument("--steps", type=int, default=5)
+    ap.add_argument("--prof-steps", type=int, default=5, help="steps of the separate instrumented pass (per-kernel HIP events) behind the timed steps")
+    ap.add_argument("--warmup", type=int, default=2)
+    ap.add_argument("--workload", choices=["track", "detect", "tiny"], default="track")
+    ap.add_argument("--seqs", type=int, default=32, help="sequences per step (tiny)")
+    ap.add_argument("--clips", type=int, default=48, help="clips per GPU per step (track)")
+    ap.add_argument("--T", type=int, default=30)
+    ap.add_argument("--size", type=int, default=416)
+    ap.add_argument("--graphs", dest="graphs", action="store_true", default=True,
+                    help="dt_graph_enable for the timed steps: hipGraph replay of the detector trunk / recurrences (default; the instrumented pass behind them runs plain launches)")
+    ap.add_argument("--no-graphs", dest="graphs", action="store_false", help="plain launches in the timed steps too")
+    ap.add_argument("--boxes", type=int, default=32, help="boxes/frame the synthetic tracker head is calibrated to (track)")
+    ap.add_argument("--batch", type=int, default=8, help="frames per step (detect)")
+    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--h2d", action="store_true", help="also copy the frames from pinned host memory every step (PCIe-inclusive rate; never the headline value)")
+    ap.add_argument("--cpu-frames", type=int, default=30)
+    ap.add_argument("--shard", choices=["clip", "frame"], default="clip",
+                    help="N>1 (track): clip = each rank owns --clips whole clips (weak scaling, no data-path collective); "
+                         "frame = --clips clips in TOTAL, every rank runs the detector on its time steps of all of them, "
+                         "per-frame rows all-gathered, recurrence on each clip's owner (strong scaling; configs[4])")
+    ap.add_argument("--no-extra", action="store_true", help="skip the configs[1] extra block")
+    ap.add_argument("--layer-report", default=None, help="write a per-layer table (HIP-event times) to this file (needs --full)")
+    ap.add_argument("--full", action="store_true",
+                    help="behind the headline steps: the instrumented per-kernel pass (kernels, roofline), the extra configurations and the CPU baseline")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the last timed step's outputs to DIR/<name>.npy (float32 / float64, at most 64 MB in all)")
+    args = ap.parse_args()
+    if args.layer_report and not args.full:
+        ap.error("--layer-report comes from the instrumented pass: add --full")
+
+    if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
+        # typed as a plain command: become the launcher -- one rank per GPU of this node under torch.distributed.run
+        # (backend nccl = RCCL unless DT_DIST_BACKEND says otherwise); rank 0 of the child job prints the JSON line to
+        # the stdout this process inherited
+        import socket
+        import subprocess
+        with socket.socket() as sk:
+            sk.bind(("127.0.0.1", 0))
+            port = sk.getsockname()[1]
+        env = dict(os.environ, HSA_ENABLE_IPC_MODE_LEGACY=os.environ.get("HSA_ENABLE_IPC_MODE_LEGACY", "0"))
+        cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", str(args.gpus),
+               "--master-addr", "127.0.0.1", "--master-port", str(port), os.path.abspath(__file__)] + sys.argv[1:]
+        rc = subprocess.call(cmd, env=env, stdout=sys.__stdout__, stderr=sys.__stderr__)
+        if rc != 0:
+            sys.exit(rc)
+        return None
+    rank, world, local = init_from_env()
+    assert world == args.gpus, "--gpus %d but WORLD_SIZE=%d: launch with torchrun --nproc-per-node %d, or run " \
+                               "`python bench.py --gpus %d` without a launcher" % (args.gpus, world, args.gpus, args.gpus)
+    assert torch.cuda.is_available(), "bench.py needs an MI355X; there is no CPU fallback"
+    device = torch.device("cuda", torch.cuda.current_device())
+    H = W = args.size
+
+    if args.workload == "track":
+        frame_shard = args.shard == "frame" and world > 1
+        # frame-shard: ONE set of --clips clips for the whole job; a rank keeps only its own time steps of them resident
+        # (sharded ingest: t mod N = rank) once the head is calibrated
+        frames = make_frames(args.clips, args.T, H, W, device, seed0=42 + (0 if frame_shard else 100 * rank))
+        trk, blob, tw = build_tracker(H, W, args.T, args.boxes, frames)
+        if frame_shard:
+            from parallel import frame_shard_times
+            frames = frames[:, frame_shard_times(args.T, rank, world)].contiguous()
+        xstats = {}
+        ctx = trk.model.ctx
+        frames_per_step = args.clips * args.T / (world if frame_shard else 1)
+        gflop_per_frame = GFLOP_TRACK_416 * (H * W) / (416.0 * 416.0)
+
+        host_frames = frames.cpu().pin_memory() if args.h2d else None
+
+        def step():
+            src = frames
+            if host_frames is not None:
+                frames.copy_(host_frames, non_blocking=True)     # same stream: serialised in front of the step
+            xstats.clear()
+            if frame_shard:
+                return track_clips_frame_sharded(trk, src, cap=max(128, 2 * args.boxes), T=args.T, stats=xstats)
+            res = trk.track_clips(src, cap=max(128, 2 * args.boxes))
+            if world > 1:
+                res = gather_detections(res, n_clips_max=args.clips, ctx=ctx, stats=xstats)
+            return res
+    elif args.workload == "tiny":
+        # BASELINE.json configs[3]: TinyTracker (ROLO-style) over 64-frame sequences, FRAME-sharded:
+        # every rank runs detector + pooling on its slice of the time axis of all sequences, the
+        # small per-frame rows are all-gathered, the LSTM over T runs replicated.  Strong scaling.
+        from models_tracking.TinyTracker import TinyTracker
+        from parallel import gather_frame_rows
+        C, T = 80, 64
+        assert T % world == 0
+        blob = synth.synth_darknet_blob(C, seed=1234)
+        det = KerasYOLO({'LABELS': KerasYOLO.LABELS_COCO, 'BATCH_SIZE': 4, 'IMAGE_H': H, 'IMAGE_W': W,
+                         'GRID_H': H // 32, 'GRID_W': W // 32}, weights=blob)
+        ctx = det.model.ctx
+        cfg = {"model_tracker": {"name": "TinyTracker", "lstm_units": 512, "sequence_length": T},
+               "train": {"pool": "Global", "batch_size": 4}}
+        tt = TinyTracker(cfg, feature_dims=(H // 16, W // 16, 512), weights=synth.synth_tiny_weights(512), ctx=ctx)
+        t_loc = T // world
+        frames = make_frames(args.seqs, t_loc, H, W, device, seed0=42 + 100 * rank)
+        frames_per_step = args.seqs * t_loc
+        gflop_per_frame = GFLOP_DETECT_416_C80 * (H * W) / (416.0 * 416.0)
+        tw = None
+        xstats = {}
+
+        def step():
+            rows, _ = tt.frame_rows(frames.reshape(args.seqs * t_loc, H, W, 3), det)
+            rows = gather_frame_rows(rows.reshape(args.seqs, t_loc, -1).contiguous())
+            return ctx.tiny_sequence(rows)
+    else:
+        C = 80
+        blob = synth.synth_darknet_blob(C, seed=1234)
+        det = KerasYOLO({'LABELS': KerasYOLO.LABELS_COCO, 'BATCH_SIZE': args.batch, 'IMAGE_H': H, 'IMAGE_W': W,
+                         'GRID_H': H // 32, 'GRID_W': W // 32}, weights=blob)
+        ctx = det.model.ctx
+        frames = make_frames(1, args.batch, H, W, device, seed0=42 + 100 * rank)[0].contiguous()
+        frames_per_step = args.batch
+        gflop_per_frame = GFLOP_DETECT_416_C80 * (H * W) / (416.0 * 416.0)
+        tw = None
+        xstats = {}
+
+        def step():
+            return det.detect(frames)
+
+    def sync_all():
+        torch.cuda.synchronize()
+        if world > 1:
+            dist.barrier()
+        torch.cuda.synchronize()
+
+    if args.graphs:
+        ctx.graph_enable(True)        # captured during the warm-up steps (second call per shape), replayed afterwards
+    res = None
+    for _ in range(max(args.warmup, 3) if args.graphs else args.warmup):
+        res = step()
+    sync_all()
+    # ---- the contract number: K steps with NO per-launch instrumentation (HIP events around every launch cost ~1 %) ----
+    ctx.profile_reset()
+    ctx.profile_enable(False)
+    sync_all()
+    t0 = time.perf_counter()
+    for _ in range(args.steps):
+        res = step()
+    sync_all()
+    elapsed = time.perf_counter() - t0
+    per_rank_ms = None
+    if world > 1:
+        rec = [None] * world
+        dist.all_gather_object(rec, {"rank": rank, "ms_per_step": 1e3 * elapsed / args.steps})      # every rank's own clock, both shard modes
+        per_rank_ms = rec
+        tmax = torch.tensor([elapsed], dtype=torch.float64, device=device if dist.get_backend() == "nccl" else "cpu")
+        dist.all_reduce(tmax, op=dist.ReduceOp.MAX)
+        elapsed = float(tmax.item())
+    if rank == 0 and args.dump_outputs:
+        dump_outputs(args.dump_outputs, res)
+    full = instrumented_report(args, ctx, step, sync_all, rank) if args.full else None
+
+    # frame-shard: where each rank spent the last step (with --full: the last instrumented one) -- the part spread over all ranks (detector + input projection) vs the
+    # owner stage (row wait + recurrence + decode on the clips it owns; a rank that owns none idles there)
+    stage_ms = None
+    if args.workload == "track" and args.shard == "frame" and world > 1:
+        mine = frame_shard_stage_ms(xstats)
+        rec = [None] * world
+        dist.all_gather_object(rec, {"rank": rank, "clips_owned": xstats.get("clips_owned"),
+                                     "sharded_stage_ms": mine[0] if mine else None, "owner_stage_ms": mine[1] if mine else None})
+        stage_ms = rec
+
+    boxes_per_frame = None
+    if args.workload == "track" and res is not None and isinstance(res, dict):
+        boxes_per_frame = float(res["counts"].float().mean().item())
+
     if rank == 0:
         total_frames = frames_per_step * world * args.steps
         fps = total_frames / elapsed
@@ -711,23 +813,9 @@ def _run():
             "value": fps, "unit": "frames/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
             "ms_per_step": 1e3 * elapsed / args.steps, "higher_is_better": True,
             "timing": {"headline": "%d steps without per-launch events (profile off)%s" % (args.steps, ", detector trunk and recurrences replayed as hipGraphs (dt_graph_enable)" if args.graphs else ", plain launches"),
-                       "hipgraph": bool(args.graphs),
-                       "ms_per_step_instrumented": 1e3 * elapsed_prof / prof_steps, "instrumented_steps": prof_steps,
-                       "note": "kernels / roofline come from the separate instrumented pass (a HIP event pair around each of ~280 launches per step)"},
+                       "hipgraph": bool(args.graphs)},
             "scaling": "strong" if (args.workload == "tiny" or (args.workload == "track" and args.shard == "frame" and world > 1)) else "weak",
             "vs_baseline": None, "dtype": "f32", "data": "synthetic",
-            "dtype_detail": (("fp32 storage, fp32 accumulation everywhere; the Winograd-form and 1x1 layers' GEMMs form each fp32 product from THREE fp16 MFMA "
-                              "partial products (lo*hi + hi*lo + hi*hi) of 2-term split operands: x * 2^s = hi + lo with hi = fp16(x 2^s), lo = fp16(x 2^s - hi), "
-                              "|x 2^s - hi - lo| <= 2^-23 |x 2^s| and zero for three elements in four; s per tensor from its MEASURED max |x| (taken by the "
-                              "producing kernel's epilogue), per Winograd position for the weights; accumulators scaled back by the exact inverse power of two.  "
-                              "Error against float64 at every benched GEMM shape: rms 5.5e-8 / max 1.0e-6 of sum |u||v| -- below the six-product bf16 form "
-                              "(6.8e-8 / 1.1e-6) and the fp32 library GEMM (8.7e-8 / 1.6e-6) on the same data, asserted in pytest -m gpu "
-                              "(test_split_bf16_gemm_benched_shapes_against_float64; profiles/parity_r06_gemm_split_f64.txt).  extra.track_bf16x3 / "
-                              "extra.track_fp32_mfma_only: the same step in the round-5 form and on the fp32 MFMA instruction only") if s3_h2 else
-                             ("fp32 storage, fp32 accumulation everywhere; the F(6x6,3x3) layers' GEMMs form each fp32 product from six bf16 MFMA "
-                              "partial products of 3-term split operands (x = x1 + x2 + x3, exact to 2^-25 |x|): error against float64 no "
-                              "larger than the fp32 MFMA path's (DT_S3=0), which the parity tests assert")) if s3["ms"] > 0 else
-                            "fp32 storage, fp32 MFMA arithmetic, fp32 accumulation",
             "config": {"workload": ("BASELINE.json configs[2]: MultiObjDetTracker (YOLOv2 C=12 + ConvLSTM2D(512) + 1x1 "
                                     "+ decode/NMS + track ids), %d clips x %d frames per GPU per step, %dx%d uint8; the synthetic head is calibrated "
                                     "to %d CANDIDATE boxes per frame, of which about 20 survive NMS (config.boxes_per_frame: measured).  The step computes the model's "
@@ -747,44 +835,11 @@ def _run():
             "ranks_seen": dist.get_world_size() if (world > 1 and dist.is_initialized()) else 1,
             "exchange_bytes_received_per_step_rank0": int(xstats.get("bytes_received", 0)),
             "frame_shard_stage_ms_per_rank": stage_ms, "ms_per_step_per_rank": per_rank_ms,
-            "roofline": None if dominant is None else {
-                "bound": "mfma",
-                # the four contract fields describe ONE family -- the one with the most time in the step -- and nothing else;
-                # every other figure of a family lives in families[<name>], computed from that family's own launches only
-                "kernel": families[dominant]["kernel"] + " -- " + families[dominant]["instruction"],
-                "dominant_family": dominant,
-                "achieved": families[dominant]["achieved"], "peak": families[dominant]["peak_tflops"], "unit": "TFLOP/s",
-                "frac": families[dominant]["frac"],
-                "traffic": families[dominant]["traffic_bytes_per_launch"],
-                "traffic_unit": "bytes per launch of the dominant family (FETCH_SIZE x in-run calibration + WRITE_SIZE; beyond-L2, incl. Infinity Cache hits)",
-                "traffic_source": os.path.relpath(tr[0], ROOT) if tr is not None else None,
-                "traffic_per_step": tr[1].get("traffic_bytes_per_step") if tr is not None else None,
-                "families": families, "transforms": transforms,
-                "frac_whole_conv_path": conv_path_pipe_frac,
-                "whole_conv_path": {"executed_fp32_mfma_tflop_per_step": conv_path_flops / steps / 1e12,
-                                    "executed_bf16_mfma_tflop_per_step": conv_path_bf16 / steps / 1e12,
-                                    "fp32_equivalent_tflops": ((conv_path_flops + s3["flops"] / s3_products + c3h2["flops"] / 3.0 + (conv1["flops"] / 3.0 if conv1_bf16 else 0.0)) / (conv_path_ms * 1e-3) / 1e12)
-                                    if conv_path_ms > 0 else None,
-                                    "ms_per_step": conv_path_ms / steps,
-                                    "direct_form_tflop_per_step": direct_form_all / steps / 1e12,
-                                    "direct_form_tflops": (direct_form_all / (conv_path_ms * 1e-3) / 1e12) if conv_path_ms > 0 else None,
-                                    "direct_form_bytes_per_step": direct_form_bytes_all / steps,
-                                    "implementation_bytes_per_step": (s3["bytes"] + ig["bytes"] + wino_in["bytes"] + wino_out["bytes"] + fused["bytes"] + c3h2["bytes"] + conv1["bytes"]) / steps},
-                "note": "achieved / peak / frac / traffic = the DOMINANT kernel family (most time in the step): MFMA FLOPs its launches execute / "
-                        "their HIP-event time, against the dense peak of the instruction it issues (pipe utilisation, <= 1). Per family "
-                        "(families.*): executed = FLOPs on the matrix pipe; algorithmic = SURVEY.md 8d direct-form FLOPs (2MKN of the "
-                        "reference's layer) of the layers THAT family's launches computed -- the 3x3 layers run in Winograd form "
-                        "(F(6x6,3x3): 1.78 multiplies per output instead of 9; fused F(4x4,3x3): 2.25), so achieved_algorithmic exceeds "
-                        "achieved; wino_gemm_s3 carries every fp32 operand as two fp16 terms of the scaled operand (three bf16 terms under DT_S3_H2=0) and forms each product from three (six) 16-bit "
-                        "MFMA partial products with fp32 accumulation (fp32 accuracy, tests/test_gpu_parity.py::"
-                        "test_split_bf16_gemm_benched_shapes_against_float64): fp32_equivalent_tflops = executed / mfma_products_per_multiply. "
-                        "implementation_* = bytes the kernels move by their own count (V + U + M' for the GEMMs); traffic_* = PMC "
-                        "measurement (profiles/). transforms = the HBM-bound Winograd transform kernels around the GEMMs. "
-                        "frac_whole_conv_path = time the matrix pipe needs at its peaks for everything the conv path executes "
-                        "(16-bit FLOPs / 2500 + fp32 FLOPs / 157.3) / the conv path's time incl. transforms."},
-            "kernels": kern,
         }
-        if world == 1 and not args.no_extra and args.workload == "track":
+        if full is not None:
+            out["timing"].update(full.pop("timing"))
+            out.update(full)
+        if args.full and world == 1 and not args.no_extra and args.workload == "track":
             import gc
             out["extra"] = {}
             for key, fn in (("detect_batch8", lambda: detect_batch8_extra(device, H, W, seed0=4242)),
@@ -823,7 +878,7 @@ def _run():
                 out["extra"][key] = fn()
                 gc.collect()                      # each extra owns a context with its own workspaces: release them
                 torch.cuda.empty_cache()
-        if world == 1 and not args.no_cpu_baseline and args.workload == "track":
+        if args.full and world == 1 and not args.no_cpu_baseline and args.workload == "track":
             from oracle import oracle as orc
             orc.lib()
             variants = cpu_baseline_track(blob, tw, H, W, args.cpu_frames)

@@ -389,3 +389,26 @@ def test_gather_detections_finds_padding_itself(tmp_path):
     for r, (p, o) in enumerate(zip(procs, outs)):
         assert p.returncode == 0, o
         assert "RANK %d OK" % r in o, o
+
+
+def test_bench_dump_outputs_dtypes_budget_and_fixed_sample(tmp_path):
+    """bench.py --dump-outputs on a result shaped like the headline step's: float results as float32, integer results as
+    float64 (exact), at most 64 MB in all, and the array over its share replaced by the same seeded sample every time."""
+    import torch
+    sys.path.insert(0, ROOT)
+    import bench
+    g = torch.Generator().manual_seed(3)
+    res = dict(boxes=torch.rand(48, 30, 128, 8, generator=g), counts=torch.randint(0, 30, (48, 30), generator=g, dtype=torch.int32),
+               ids=torch.randint(-1, 50, (48, 30, 128), generator=g, dtype=torch.int32), nids=torch.randint(0, 50, (48,), generator=g, dtype=torch.int32),
+               netout=torch.randn(48, 30, 13, 13, 5, 17, generator=g), note=None)
+    for d in ("a", "b"):
+        bench.dump_outputs(str(tmp_path / d), res)
+    names = sorted(os.listdir(tmp_path / "a"))
+    assert names == ["boxes.npy", "counts.npy", "ids.npy", "netout.npy", "nids.npy"]
+    assert sum(os.path.getsize(tmp_path / "a" / n) for n in names) <= 64e6
+    for n in names:
+        a, b = np.load(tmp_path / "a" / n), np.load(tmp_path / "b" / n)
+        assert a.dtype == (np.float32 if res[n[:-4]].is_floating_point() else np.float64) and np.array_equal(a, b)
+    assert np.array_equal(np.load(tmp_path / "a" / "ids.npy"), res["ids"].numpy()) and np.array_equal(np.load(tmp_path / "a" / "boxes.npy"), res["boxes"].numpy())
+    sample = np.load(tmp_path / "a" / "netout.npy")
+    assert sample.ndim == 1 and 0 < sample.size < res["netout"].numel() and np.isin(sample, res["netout"].numpy()).all()
