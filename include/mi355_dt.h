@@ -292,11 +292,13 @@ DT_API int dt_gemm_split(dt_ctx *ctx, const float *d_v, const float *d_u, int P,
                          float *d_m);
 
 /* ---- tuning / test knobs ------------------------------------------------- *
- * The DT_* environment variables of DESIGN.md's appendix are read ONCE, in dt_create (no launch path calls
- * getenv); this re-reads them into a live context.  dt_conv2d / dt_convlstm_step do the same on entry. */
+ * The DT_* environment variables of DESIGN.md's appendix are read in dt_create (no launch path calls getenv);
+ * this re-reads them into a live context.  dt_conv2d / dt_convlstm_step do the same on entry. */
 DT_API int dt_policy_reload(dt_ctx *ctx);
-/* One knob of ONE context without touching the process environment: name "pin", value 1 / 0 = DT_PIN for this context only
- * (kernel selection independent of the batch a call carries; object_tracking_amd/parallel.py: deterministic=True). */
+/* One knob of ONE context without touching the process environment: name "pin", value 1 / 0 = DT_PIN on / off for this
+ * context only (kernel selection independent of the batch a call carries; object_tracking_amd/parallel.py: deterministic=True),
+ * -1 = follow DT_PIN again.  The override persists through dt_policy_reload and the test entry points' re-reads.  Any other
+ * name or value fails with DT_ERR_ARG. */
 DT_API int dt_policy_set(dt_ctx *ctx, const char *name, int value);
 
 /* ---- profiling --------------------------------------------------------- */

@@ -170,12 +170,9 @@ __global__ __launch_bounds__(64 * WGM * WGN, (WGM * WGN > 4 ? (WGM * WGN) / 4 : 
         int z, m0, n0;
     };
     auto tile_of = [&](int L) {
-        int t = L;
-        if (p.xcd_remap) {
-            const int q = total >> 3, r = total & 7;
-            const int xcd = L & 7, j = L >> 3;
-            t = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + j;   // bijective for any total
-        }
+        const int q = total >> 3, r = total & 7;
+        const int xcd = L & 7, j = L >> 3;
+        const int t = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + j;   // bijective for any total
         Tile T;
         T.z = t / ntiles;
         const int bid = t - T.z * ntiles;
@@ -748,7 +745,7 @@ static int launch_one(hipStream_t st, const ConvArgs &a, int ksplit = 1)
         return n;
     }();
     const int slots = ((cus * (WGM * WGN > 4 ? 1 : 2)) / 8) * 8;   // multiple of 8: L % 8 stays the XCD
-    if (PERSIST && !a.no_persist && ksplit == 1 && slots > 0 && grid > slots) grid = slots;
+    if (PERSIST && ksplit == 1 && slots > 0 && grid > slots) grid = slots;
 #endif
     hipLaunchKernelGGL(kern, dim3((unsigned)grid, (unsigned)ksplit), dim3(64 * WGM * WGN), lds, st, a);
     return hipGetLastError() == hipSuccess ? 0 : 1;
@@ -771,11 +768,9 @@ static int launch_cfg(hipStream_t st, const ConvArgs &a, int cfg)
 int launch_conv_igemm(hipStream_t st, const ConvArgs &a_in, int ks, int order, int epi, int cfg)
 {
     ConvArgs a = a_in;
-    // a.xcd_remap / a.no_persist / a.gn_default come from the caller's Policy (network.hip:launch_igemm)
     // column tiles per group of the tile order: measured FETCH_SIZE optimum is 1 for the 3x3
     // layers (all ~64 workgroups resident on an XCD share ONE weight panel) and 2 for 1x1 / gates
-    if (a_in.tile_gn < 0) a.tile_gn = -a_in.tile_gn - 1;   // caller-chosen width, encoded as -(gn+1)
-    else a.tile_gn = a_in.gn_default > 0 ? a_in.gn_default - 1 : ((ks == 3 && epi != EPI_GATES) ? 1 : 2);
+    a.tile_gn = (ks == 3 && epi != EPI_GATES) ? 1 : 2;
     // a caller-forced tile configuration (Policy::conv_cfg: A/B runs and the tests that exercise every
     // configuration at small shapes) applies to the 128-wide-or-wider layers
     if (a.force_cfg > 0 && cfg != CFG_128x64 && cfg != CFG_64x128 && epi != EPI_PARTIAL) cfg = a.force_cfg - 1;

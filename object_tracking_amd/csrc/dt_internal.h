@@ -74,15 +74,12 @@ struct ConvArgs {
     int act;      // 0: LeakyReLU(slope), 1: sigmoid (Dense heads)
     const float *zeros; // >= 16 B of device zeros: source of out-of-image taps (set by launch_conv_igemm)
     int ksplit;    // EPI_PARTIAL: number of K splits (grid.y); out = slab [ksplit][M][out_ld]
-    int tile_gn;   // column tiles per group in the tile order (0 = all)
-    int xcd_remap; // 1: give each XCD a contiguous range of tiles (set by launch_conv_igemm)
+    int tile_gn;   // column tiles per group in the tile order (0 = all; set by launch_conv_igemm)
     // batched GEMMs (Winograd positions): grid.z problems, blockIdx.z advances in / wt / out by these (floats)
     int zbatch;
     long long z_in, z_wt, z_out;
     int force_cfg; // > 0: tile configuration + 1 forced by the caller's policy (Policy::conv_cfg); 0: none
-    int no_persist; // 1: one tile per workgroup even where the persistent tile loop applies (Policy::persist = 0, A/B runs)
     unsigned *amax_out; // EPI_PLAIN (no split-K) / EPI_POOL / EPI_S2D: non-null = max |x| of the stored outputs into this slot (dt_amax_publish)
-    int gn_default; // > 0: column-group width + 1 used when tile_gn is 0 (Policy::tile_gn, A/B runs); 0: the per-layer default
 };
 
 // Tile configurations of the MFMA kernel
@@ -107,9 +104,6 @@ struct WinoArgs {
     // P = (ts+2)^2 Winograd positions
     int B, H, W, th, tw, Mt, ts;
     int g;   // frames per side of the virtual mosaic the tiles live on (1: one frame; winograd.hip:vpixel)
-    int coop;  // F(6x6) lane-cooperative transform kernels: -1 small launches only (default), 0 never, 1 always (Policy::wino_coop)
-    int grid_in, grid_out, thr_out;   // A/B knobs (Policy::wino_grid_in / wino_grid_out / wino_thr_out): workgroup cap of the big input / output transform launches
-                                      // and the output kernel's workgroup size; 0 = the built-in choice
     // input transform: in (NHWC, pixel stride in_ld, image stride in_bs), C channels -> v [P][Mt][C]
     const float *in;
     long long in_bs;
@@ -388,13 +382,13 @@ struct ConvLayer {
     bool scale_has_zero = false;
 };
 
-// Tuning / test knobs.  Read from the environment ONCE, in dt_create; the two layer-level
-// test entry points (dt_conv2d, dt_convlstm_step) re-read it so that the parity tests can force a policy on a
-// live context.  No launch path calls getenv.
+// Tuning / test knobs.  ctx->pol is assigned by network.hip:policy_refresh only: in dt_create,
+// dt_policy_reload, dt_policy_set and the two layer-level test entry points (dt_conv2d, dt_convlstm_step, so that the
+// parity tests can force a policy on a live context through the environment).  No launch path calls getenv.
 struct Policy {
     int wino = 1;            // DT_WINO: 0 never / 1 default policy / 2 everywhere the transforms are defined
     int wino_tile = 0;       // DT_WINO_TILE: 2/4/6 for every layer; 0 = default (6, recurrent convolution 4)
-    int wino_minc = 64, wino_minn = 128, wino_mint = 0;   // DT_WINO_MINC / MINN / MINT (A/B runs)
+    int wino_mint = 0;       // DT_WINO_MINT: Winograd tiles from which a launch takes the transforms; 0 = the per-tile-size default (wino_runs)
     double wino_ws_gb = 96.0;   // DT_WINO_WS_GB: V + M' workspace above this -> direct form
     int mosaic = -1;         // DT_WINO_MOSAIC: 1 never, 2/3/4 force, -1 = fewest tiles
     int fused4 = 1;          // DT_WINO_FUSED4: the fused F(4x4) kernel (wino4s_fused.hip): 0 never / 1 conv_2 / 3 / 5 (Cin <= 64) from 1024
@@ -409,16 +403,11 @@ struct Policy {
     int c3h2 = 1;            // DT_C3H2: conv_2 / conv_3 / conv_5 as DIRECT 3x3 convolutions in the two-term fp16 form (conv3_h2.hip) from 1024 16x16-pixel blocks
                              //          (where the fused F(4x4) fp32 kernel ran until round 5); 0 = the fused kernel; 2 = at any size (parity tests).  Needs the fp16
                              //          form (DT_S3_H2, not DT_PIN).  Read at weight load (0: no fp16 copy of the weights) and per launch
-    int c3h2_blocks2 = 1024; // DT_C3H2_BLOCKS2: 16 x 16-pixel blocks from which conv_2 (Cin = 32) takes the direct kernel under DT_C3H2=1 (conv_3 / conv_5: 1024)
-    int wino_cfg = -1, wino_gn = -1;   // DT_WINO_CFG / DT_WINO_GN (A/B runs)
-    int wino_grid_in = 0, wino_grid_out = 0, wino_thr_out = 0;   // DT_WINO_GRID_IN / DT_WINO_GRID_OUT / DT_WINO_THR_OUT (A/B runs: WinoArgs::grid_in / grid_out / thr_out)
-    int ksplit = 0;          // DT_KSPLIT
     int conv_cfg = -1;       // DT_CONV_CFG
     int s3_conv1 = 1;        // DT_S3_CONV1: conv_1 on the bf16 pipe with split operands (conv1_s3_kernel); 0 = conv1_mfma_kernel (fp32 MFMA)
     int s3 = 1;              // DT_S3: the F(6x6) layers' batched GEMMs on the bf16 matrix pipe with 3-term split operands (wino_gemm_s3.hip):
-                             //        0 never (fp32 MFMA) / 1 where it wins (K >= s3_mink, GEMM rows >= s3_minrows) / 2 wherever the shape allows
-    int s3_mink = 128, s3_minrows = 2048;   // DT_S3_MINK / DT_S3_MINROWS (K >= 128 since round 4: with the line-sized epilogue stores the K = 128 GEMMs of
-                                            // conv_6 / conv_8 take 3.4 instead of 4.3 ms on the fp32 kernel, their split input transform costs 0.7 back)
+                             //        0 never (fp32 MFMA) / 1 where it wins (K >= 128, GEMM rows >= s3_minrows) / 2 wherever the shape allows
+    int s3_minrows = 2048;   // DT_S3_MINROWS
     int s3_minrows_h2 = 64;  // ... the row threshold where the launch would take the fp16 form (three products per multiply: the split GEMM beats the fp32 MFMA
                              //     kernel from far fewer rows than the bf16 form does -- detector forward at 32 / 64 / 128 / 192 frames: 3.50 -> 2.85, 6.60 -> 4.45,
                              //     9.91 -> 7.17, 14.5 -> 10.2 ms; 64 rather than 128 for the 75 / 98 rows of the 13 x 13 layers at 12 / 16 frames; profiles/r06_experiments.txt section 10).
@@ -448,16 +437,12 @@ struct Policy {
                                   // batch 8 (conv_10 / 12: 5408 rows = 22 workgroups) the fp32 kernel with split-K is faster (0.035 vs 0.061 ms)
     int s3_1x1 = 1;          // DT_S3_1X1: the 1x1 layers with N % 128 == 0 run on wino_gemm_s3.hip straight from the fp32 activation (the kernel splits
                              //            its A fragments itself); 0 = fp32 MFMA
-    int wino_coop = -1;      // DT_WINO_COOP: lane-cooperative F(6x6) transform kernels: -1 for small launches (default) / 0 never / 1 always
-    int persist = 1;         // DT_PERSIST: 0 = one tile per workgroup for the GEMM-shaped launches (A/B runs)
-    int xcd_remap = 1;       // DT_XCD_REMAP: 0 = plain tile numbering (L2 traffic experiments)
-    int tile_gn = -1;        // DT_TILE_GN: column tiles per group of the tile order; -1 = per-layer default
 };
-void policy_from_env(Policy &p, int pin_override = -1 /* >= 0: this value instead of DT_PIN */);
 
 struct dt_ctx {
     std::string err;
     Policy pol;
+    int pin_override = -1;   // dt_policy_set("pin"): 0 / 1 instead of DT_PIN, -1 = follow DT_PIN
     hipStream_t stream = nullptr;
     int device_ok = 0;
     // detector
@@ -478,8 +463,8 @@ struct dt_ctx {
     // 64..127: scratch of the weight packs
     unsigned *amax = nullptr;
     struct AmaxTag { const float *lo, *hi; int cols, slot; };   // the tensor that occupies [lo, hi), `cols` channels per pixel -> the slot that holds its max |x|
-    bool h2_small = false;                   // the running call carries fewer than Policy::h2_minframes frames: no fp16 form, no max-|x| publication
-    std::vector<AmaxTag> amax_tag;           // valid inside one API call only (amax_reset), and until a layer writes into [lo, hi) (amax_forget)
+    bool h2_small = false;                   // the running call carries fewer than Policy::h2_minframes frames: no fp16 form, no max-|x| publication (call_begin)
+    std::vector<AmaxTag> amax_tag;           // valid inside one API call only (call_begin), and until a layer writes into [lo, hi) (amax_forget)
     float *conv1_w = nullptr, *conv1_b = nullptr, *lut255 = nullptr;
     unsigned *conv1_w3 = nullptr, *conv1_w3u8 = nullptr;   // device: split-bf16 weight tables of conv1_s3_kernel: w and w / 255 (conv1.hip:conv1_split_tables)
     std::vector<float> conv1_hwio32, conv1_scale, conv1_shift;   // host copy of conv_1 as a Cin = 32 layer (dt_detector_extract)

@@ -175,8 +175,13 @@ static void s3_drop(dt_ctx *ctx, const void *wino)
 #define DT_AMAX_SLOTS 128
 enum { AMAX_ONE = 0, AMAX_IN = 32, AMAX_TRK = 56, AMAX_TEST = 57, AMAX_PACK = 64 };
 static unsigned *amax_slot(dt_ctx *ctx, int slot) { return ctx->amax ? ctx->amax + (size_t)slot * DT_AMAX_WORDS : nullptr; }
-// every API entry that runs layers starts here: what a previous call knew about a tensor's maximum says nothing about the bytes behind the pointer now
-static void amax_reset(dt_ctx *ctx) { ctx->amax_tag.clear(); ctx->h2_small = false; }
+// every API entry that runs layers starts here: what a previous call knew about a tensor's maximum says nothing about the bytes behind the pointer now,
+// and a call of fewer than Policy::h2_minframes frames takes no fp16 form (frames = 0: a layer-level test entry, never small)
+static void call_begin(dt_ctx *ctx, int frames)
+{
+    ctx->amax_tag.clear();
+    ctx->h2_small = frames > 0 && frames < ctx->pol.h2_minframes;
+}
 // the slot that holds max |x| of the rows x cols tensor at x: the one its producer filled (tagged), else measured here into `slot`
 // a layer is about to write `floats` floats from `lo` on: what was known about tensors in that range is void
 static void amax_forget(dt_ctx *ctx, const float *lo, long long floats)
@@ -200,9 +205,6 @@ static int amax_begin(dt_ctx *ctx)
     return DT_OK;
 }
 // slot a layer's epilogue fills with the max |x| of what it writes: conv_1 .. conv_23 only (the test entry points run "layer 0")
-// blocks of 16 x 16 pixels from which a narrow 3x3 layer takes the direct fp16-form kernel (conv3_h2.hip) instead of the fused fp32 one (Policy::c3h2_blocks2 for
-// conv_2, Cin = 32; 1024 for conv_3 / conv_5)
-static long long c3h2_min_blocks(const dt_ctx *ctx, int cin) { return cin <= 32 ? ctx->pol.c3h2_blocks2 : 1024; }
 static int amax_out_slot(const ConvLayer &L) { return L.idx >= 1 && L.idx <= 23 ? L.idx : 0; }
 static const unsigned *ensure_amax(dt_ctx *ctx, const float *x, long long rows, int cols, long long ld, int slot)
 {
@@ -228,6 +230,54 @@ static int upload(dt_ctx *ctx, float **dst, const std::vector<float> &h)
     return DT_OK;
 }
 
+// ---- kernel-selection policy (dt_internal.h: Policy) ------------------------------------------------------------------------------
+// the integer knobs and their environment variables; DT_WINO_WS_GB (a double) and the two derived fp16-form row thresholds are read after the loop
+static const struct { const char *name; int Policy::*field; } k_knobs[] = {
+    {"DT_WINO", &Policy::wino}, {"DT_WINO_TILE", &Policy::wino_tile}, {"DT_WINO_MINT", &Policy::wino_mint},
+    {"DT_WINO_MOSAIC", &Policy::mosaic}, {"DT_WINO_FUSED4", &Policy::fused4}, {"DT_TRK_MERGE", &Policy::trk_merge},
+    {"DT_PIN", &Policy::pin}, {"DT_C3H2", &Policy::c3h2}, {"DT_C3FUSE", &Policy::c3fuse}, {"DT_CONV_CFG", &Policy::conv_cfg},
+    {"DT_S3", &Policy::s3}, {"DT_S3_CONV1", &Policy::s3_conv1}, {"DT_S3_MINROWS", &Policy::s3_minrows}, {"DT_S3_H2", &Policy::s3_h2},
+    {"DT_H2_MINFRAMES", &Policy::h2_minframes}, {"DT_S3_HALF", &Policy::s3_half}, {"DT_S3_REC_MINROWS", &Policy::s3_rec_minrows},
+    {"DT_S3_1X1", &Policy::s3_1x1}, {"DT_S3_1X1_MINK", &Policy::s3_1x1_mink}, {"DT_S3_1X1_MINROWS", &Policy::s3_1x1_minrows},
+};
+
+static void policy_from_env(Policy &p)
+{
+    const Policy d;
+    for (const auto &k : k_knobs) {
+        const char *e = getenv(k.name);
+        p.*k.field = e ? atoi(e) : d.*k.field;
+    }
+    { const char *e = getenv("DT_WINO_WS_GB"); p.wino_ws_gb = e ? atof(e) : d.wino_ws_gb; }
+    p.s3_minrows_h2 = getenv("DT_S3_MINROWS") ? p.s3_minrows : d.s3_minrows_h2;
+    p.s3_rec_minrows_h2 = getenv("DT_S3_REC_MINROWS") ? p.s3_rec_minrows : d.s3_rec_minrows_h2;
+}
+
+static bool policy_equal(const Policy &a, const Policy &b)
+{
+    for (const auto &k : k_knobs)
+        if (a.*k.field != b.*k.field) return false;
+    return a.wino_ws_gb == b.wino_ws_gb && a.s3_minrows_h2 == b.s3_minrows_h2 && a.s3_rec_minrows_h2 == b.s3_rec_minrows_h2;
+}
+
+// The one writer of ctx->pol: the environment, then the context's pin override (dt_policy_set), then what DT_PIN implies.  Captured
+// graphs hold the launches of the policy they were captured under: any change drops them.
+static void policy_refresh(dt_ctx *ctx)
+{
+    Policy p;
+    policy_from_env(p);
+    if (ctx->pin_override >= 0) p.pin = ctx->pin_override;
+    if (p.pin) {      // every choice below otherwise looks at the number of frames / rows / tiles of the launch (no split-K either: run_conv)
+        p.wino = 2; p.mosaic = 1; p.fused4 = 2; p.s3_half = -1;
+        if (p.s3) p.s3 = 2;
+        p.trk_merge = 0;      // ONE form of the input projection, whichever entry point carries the frame (the merged weights are a different rounding of the
+                              // same network, and dt_track_recurrent on a caller's z rows cannot take them)
+        // (the fp16 form of the split GEMM is off under DT_PIN as well: h2_wanted)
+    }
+    if (!policy_equal(p, ctx->pol)) graphs_clear(ctx);
+    ctx->pol = p;
+}
+
 // ---------------------------------------------------------------------------
 extern "C" int dt_abi_version(void) { return 107; }   // 1.07: + dt_gemm_split (test entry point of wino_gemm_s3.hip: bf16 x 3 or fp16 x 2 terms), dt_policy_set
 
@@ -249,7 +299,7 @@ extern "C" int dt_create(dt_ctx **out)
                        prop.gcnArchName);
     dt_ctx *c = new dt_ctx();
     c->device_ok = 1;
-    policy_from_env(c->pol);
+    policy_refresh(c);
     std::vector<float> lut(256);
     for (int i = 0; i < 256; ++i) lut[i] = (float)((double)i / 255.0);   // utils.py:150-153
     if (upload(c, &c->lut255, lut) != DT_OK) {
@@ -622,66 +672,23 @@ static void prof_direct_form(dt_ctx *ctx, double flops, double bytes, int family
 // ---------------------------------------------------------------------------
 // Winograd path for the 3x3 layers from conv_3 up and the ConvLSTM convolutions (winograd.hip)
 // ---------------------------------------------------------------------------
+// Thresholds the A/B rounds settled (profiles/r04_experiments.txt, r06_experiments.txt).  The split GEMM (wino_gemm_s3.hip) from K = 128
+// (round 4: with the line-sized epilogue stores the K = 128 GEMMs of conv_6 / conv_8 take 3.4 instead of 4.3 ms on the fp32 kernel, their
+// split input transform costs 0.7 back):
+static const int S3_MINK = 128;
+// blocks of 16 x 16 pixels from which a narrow 3x3 layer (conv_2 / 3 / 5) takes the direct fp16-form kernel (conv3_h2.hip) instead of the fused fp32 one:
+static const long long C3H2_MIN_BLOCKS = 1024;
+
 // Policy::wino: 1 (default) = layers with Cin >= 64 and Cout >= 128 (conv_3 and up: below that the batched
 //          GEMMs have K <= 32 and the transforms' traffic costs more than the MFMA work saved) when a
 //          launch has enough tiles (wino_runs);
 //          0 = never (direct MFMA form everywhere); 2 = every 3x3 layer the transforms support,
 //          at any size (parity tests of the path at small shapes).  Applied when weights are loaded.
-void policy_from_env(Policy &p, int pin_override)
-{
-    auto geti = [](const char *name, int dflt) { const char *e = getenv(name); return e ? atoi(e) : dflt; };
-    Policy d;
-    p.wino = geti("DT_WINO", d.wino);
-    p.wino_tile = geti("DT_WINO_TILE", d.wino_tile);
-    p.wino_minc = geti("DT_WINO_MINC", d.wino_minc);
-    p.wino_minn = geti("DT_WINO_MINN", d.wino_minn);
-    p.wino_mint = geti("DT_WINO_MINT", d.wino_mint);
-    { const char *e = getenv("DT_WINO_WS_GB"); p.wino_ws_gb = e ? atof(e) : d.wino_ws_gb; }
-    p.mosaic = geti("DT_WINO_MOSAIC", d.mosaic);
-    p.fused4 = geti("DT_WINO_FUSED4", d.fused4);
-    p.c3h2 = geti("DT_C3H2", d.c3h2);
-    p.c3fuse = geti("DT_C3FUSE", d.c3fuse);
-    p.c3h2_blocks2 = geti("DT_C3H2_BLOCKS2", d.c3h2_blocks2);
-    p.wino_cfg = geti("DT_WINO_CFG", d.wino_cfg);
-    p.wino_gn = geti("DT_WINO_GN", d.wino_gn);
-    p.wino_grid_in = geti("DT_WINO_GRID_IN", d.wino_grid_in);
-    p.wino_grid_out = geti("DT_WINO_GRID_OUT", d.wino_grid_out);
-    p.wino_thr_out = geti("DT_WINO_THR_OUT", d.wino_thr_out);
-    p.ksplit = geti("DT_KSPLIT", d.ksplit);
-    p.conv_cfg = geti("DT_CONV_CFG", d.conv_cfg);
-    p.wino_coop = geti("DT_WINO_COOP", d.wino_coop);
-    p.s3 = geti("DT_S3", d.s3);
-    p.s3_conv1 = geti("DT_S3_CONV1", d.s3_conv1);
-    p.s3_mink = geti("DT_S3_MINK", d.s3_mink);
-    p.s3_minrows = geti("DT_S3_MINROWS", d.s3_minrows);
-    p.s3_minrows_h2 = getenv("DT_S3_MINROWS") ? p.s3_minrows : d.s3_minrows_h2;
-    p.s3_1x1 = geti("DT_S3_1X1", d.s3_1x1);
-    p.s3_1x1_mink = geti("DT_S3_1X1_MINK", d.s3_1x1_mink);
-    p.s3_1x1_minrows = geti("DT_S3_1X1_MINROWS", d.s3_1x1_minrows);
-    p.s3_rec_minrows = geti("DT_S3_REC_MINROWS", d.s3_rec_minrows);
-    p.s3_rec_minrows_h2 = getenv("DT_S3_REC_MINROWS") ? p.s3_rec_minrows : d.s3_rec_minrows_h2;
-    p.s3_half = geti("DT_S3_HALF", d.s3_half);
-    p.s3_h2 = geti("DT_S3_H2", d.s3_h2);
-    p.h2_minframes = geti("DT_H2_MINFRAMES", d.h2_minframes);
-    p.persist = geti("DT_PERSIST", d.persist);
-    p.xcd_remap = geti("DT_XCD_REMAP", d.xcd_remap);
-    p.tile_gn = geti("DT_TILE_GN", d.tile_gn);
-    p.trk_merge = geti("DT_TRK_MERGE", d.trk_merge);
-    p.pin = pin_override >= 0 ? pin_override : geti("DT_PIN", d.pin);
-    if (p.pin) {      // every choice below otherwise looks at the number of frames / rows / tiles of the launch
-        p.wino = 2; p.mosaic = 1; p.fused4 = 2; p.s3_half = -1; p.ksplit = 1;
-        if (p.s3) p.s3 = 2;
-        p.trk_merge = 0;      // ONE form of the input projection, whichever entry point carries the frame (the merged weights are a different rounding of the
-                              // same network, and dt_track_recurrent on a caller's z rows cannot take them)
-        // (the fp16 form of the split GEMM is off under DT_PIN as well: h2_wanted)
-    }
-}
-
 static bool wino_wanted(const dt_ctx *ctx, int ks, int cin, int cout)
 {
     const Policy &p = ctx->pol;
     if (ks != 3 || p.wino == 0 || cin % 32 || cout % 4) return false;
-    return p.wino == 2 || (cin >= p.wino_minc && cout >= p.wino_minn);
+    return p.wino == 2 || (cin >= 64 && cout >= 128);
 }
 
 // Output tile of the Winograd form: 6 = F(6x6,3x3) (default), 4 = F(4x4,3x3), 2 = F(2x2,3x3); Policy::wino_tile
@@ -794,9 +801,6 @@ static int pick_cfg_gemm(int Mt, int N, int P)
 static int launch_igemm(dt_ctx *ctx, ConvArgs &a, int ks, int order, int epi, int cfg)
 {
     a.force_cfg = ctx->pol.conv_cfg >= 0 ? ctx->pol.conv_cfg + 1 : 0;
-    a.no_persist = ctx->pol.persist ? 0 : 1;
-    a.xcd_remap = ctx->pol.xcd_remap;
-    a.gn_default = ctx->pol.tile_gn >= 0 ? ctx->pol.tile_gn + 1 : 0;
     return launch_conv_igemm(ctx->stream, a, ks, order, epi, cfg);
 }
 
@@ -842,8 +846,6 @@ static int run_wino(dt_ctx *ctx, const float *wino_wt, int ts, const float *bias
     WinoArgs w;
     memset(&w, 0, sizeof(w));
     w.B = B; w.H = H; w.W = W; w.ts = ts;
-    w.coop = ctx->pol.wino_coop;
-    w.grid_in = ctx->pol.wino_grid_in; w.grid_out = ctx->pol.wino_grid_out; w.thr_out = ctx->pol.wino_thr_out;
     {
         const WinoGeom q = wino_geometry(ctx, ts, B, H, W, io.out2 != nullptr);
         w.g = q.g; w.th = q.th; w.tw = q.tw; w.Mt = q.Mt;
@@ -862,7 +864,7 @@ static int run_wino(dt_ctx *ctx, const float *wino_wt, int ts, const float *bias
     const bool h2_avail = h2_wanted(ctx) && ctx->wino_h2.find(wino_wt) != ctx->wino_h2.end();
     const int minrows = h2_avail ? ctx->pol.s3_minrows_h2 : ctx->pol.s3_minrows, rec_minrows = h2_avail ? ctx->pol.s3_rec_minrows_h2 : ctx->pol.s3_rec_minrows;
     if (((ts == 6 && !io.cstate) || rec) && ctx->pol.s3 != 0 && cin % 32 == 0 && N % 128 == 0 && npad % 128 == 0 && wino_gemm_s3_usable(w.Mt, cin, N) &&
-        (ctx->pol.s3 == 2 || (cin >= ctx->pol.s3_mink && (rec ? (rec_minrows > 0 && w.Mt >= rec_minrows) : w.Mt >= minrows)))) {
+        (ctx->pol.s3 == 2 || (cin >= S3_MINK && (rec ? (rec_minrows > 0 && w.Mt >= rec_minrows) : w.Mt >= minrows)))) {
         auto it = ctx->wino_s3.find(wino_wt);
         if (it != ctx->wino_s3.end()) u_s3 = it->second;
     }
@@ -925,10 +927,7 @@ static int run_wino(dt_ctx *ctx, const float *wino_wt, int ts, const float *bias
         prof_direct_form(ctx, 2.0 * B * H * W * 9.0 * cin_df * N,
                          4.0 * ((double)B * H * W * cin_df + 9.0 * cin_df * N + (io.out ? (double)B * H * W * N : 0.0) +
                                 (io.out2 ? (double)B * H * W * N / 4.0 : 0.0) + (io.cstate ? 4.0 * B * H * W * N / 4.0 : 0.0)));
-        int cfg = pick_cfg_gemm(w.Mt, N, P);
-        if (ctx->pol.wino_cfg >= 0) cfg = ctx->pol.wino_cfg;               // A/B runs
-        if (ctx->pol.wino_gn >= 0) a.tile_gn = -ctx->pol.wino_gn - 1;      // A/B runs: column-group width (see launch_conv_igemm)
-        const int rc = launch_igemm(ctx, a, 1, ORD_LINEAR, EPI_PLAIN, cfg);
+        const int rc = launch_igemm(ctx, a, 1, ORD_LINEAR, EPI_PLAIN, pick_cfg_gemm(w.Mt, N, P));
         if (rc) return dt_fail(ctx, rc == 2 ? DT_ERR_ARG : DT_ERR_DEVICE, "%s: Winograd GEMM launch failed (rc=%d)", tag, rc);
     }
     {
@@ -976,7 +975,7 @@ static int pick_cfg(int M, int cout, int ks)
 static bool s3_1x1_eligible(const dt_ctx *ctx, const ConvLayer &L, long long M)
 {
     return L.ks == 1 && L.wt_s3 && ctx->pol.s3 != 0 && ctx->pol.s3_1x1 != 0 && L.cin % 32 == 0 && L.cout >= 64 && M < (1ll << 31) - 256 &&
-           (ctx->pol.s3 == 2 || (L.cin >= ctx->pol.s3_mink && L.cin >= ctx->pol.s3_1x1_mink && M >= ctx->pol.s3_minrows && M >= ctx->pol.s3_1x1_minrows));
+           (ctx->pol.s3 == 2 || (L.cin >= S3_MINK && L.cin >= ctx->pol.s3_1x1_mink && M >= ctx->pol.s3_minrows && M >= ctx->pol.s3_1x1_minrows));
 }
 
 static int run_conv(dt_ctx *ctx, const ConvLayer &L, const float *in, int in_ld, int B, int H, int W, float *out,
@@ -1033,7 +1032,7 @@ static int run_conv(dt_ctx *ctx, const ConvLayer &L, const float *in, int in_ld,
     if (L.w3_h2 && L.pscale_w3 && ctx->pol.c3h2 != 0 && h2_wanted(ctx) && in_ld % 4 == 0 && (reinterpret_cast<uintptr_t>(in) & 15) == 0 &&
         ((epi == EPI_PLAIN && order == ORD_LINEAR) || (epi == EPI_POOL && !((H | W) & 1)))) {
         const long long blocks = (long long)B * ((H + 15) / 16) * ((W + 15) / 16) * ((L.cout + 127) / 128);
-        if (ctx->pol.c3h2 == 2 || blocks >= c3h2_min_blocks(ctx, L.cin)) {
+        if (ctx->pol.c3h2 == 2 || blocks >= C3H2_MIN_BLOCKS) {
             Conv3H2Args c;
             memset(&c, 0, sizeof(c));
             c.in = in; c.in_bs = a.in_bs; c.in_ld = in_ld; c.B = B; c.H = H; c.W = W; c.Cin = L.cin; c.N = L.cout; c.Np = L.npad;
@@ -1098,7 +1097,7 @@ static int run_conv(dt_ctx *ctx, const ConvLayer &L, const float *in, int in_ld,
             // (the cost model prices the fp32 MFMA kernel's tiles: where the F(6x6) launch takes the split GEMM in the fp16 form -- run_wino's own test -- F(4x4) on the
             //  fp32 kernel is no alternative: at 20 frames it cost the 13x13 layers 0.10-0.24 ms each against 0.05-0.11 on the split kernel)
             const bool s3_h2_takes_it = ctx->pol.s3 != 0 && h2_wanted(ctx) && ctx->wino_h2.find(L.wino) != ctx->wino_h2.end() && L.cin % 32 == 0 && L.cout % 128 == 0 &&
-                                        L.npad % 128 == 0 && (ctx->pol.s3 == 2 || (L.cin >= ctx->pol.s3_mink && q6.Mt >= ctx->pol.s3_minrows_h2));
+                                        L.npad % 128 == 0 && (ctx->pol.s3 == 2 || (L.cin >= S3_MINK && q6.Mt >= ctx->pol.s3_minrows_h2));
             if (!s3_h2_takes_it && t6 <= 4096 && small_gemm_cost(q4.Mt, L.cout, 36, nullptr) < small_gemm_cost(q6.Mt, L.cout, 64, nullptr)) { wt = L.wino_alt; ts = 4; }
         }
         return run_wino(ctx, wt, ts, L.bias, L.cin, L.cout, L.npad, B, H, W, io, slope, tag, 0, L.idx >= 1 && L.idx <= 23 ? AMAX_IN + L.idx : AMAX_TEST);
@@ -1114,7 +1113,7 @@ static int run_conv(dt_ctx *ctx, const ConvLayer &L, const float *in, int in_ld,
     if (epi == EPI_PLAIN && order == ORD_LINEAR && cfg != CFG_128x64) {
         const int tiles = ((a.M + 127) / 128) * ((L.cout + 127) / 128);
         const int nk = a.K / 32;
-        if (tiles < 2 * 512) {
+        if (tiles < 2 * 512 && !ctx->pol.pin) {      // (DT_PIN: no split-K -- the split count would depend on the batch)
             int smax = nk / 6;                           // keep >= 6 chunks (192 of K) per split
             if (smax > 32) smax = 32;
             double best = 1e30;
@@ -1125,7 +1124,6 @@ static int run_conv(dt_ctx *ctx, const ConvLayer &L, const float *in, int in_ld,
                 if (t < best - 1e-9) { best = t; ksplit = sp; }
             }
         }
-        if (ctx->pol.ksplit > 0) ksplit = ctx->pol.ksplit < nk ? ctx->pol.ksplit : nk;
         if (ksplit > 1) cfg = CFG_128x128;   // the split-K path is built for the 128x128 tile
     }
     if (ksplit > 1) {
@@ -1188,7 +1186,7 @@ static bool conv34_fusable(const dt_ctx *ctx, const ConvLayer &L3, const ConvLay
 {
     const long long blocks = (long long)B * ((H + 15) / 16) * ((W + 15) / 16);
     return ctx->pol.c3fuse != 0 && L3.ks == 3 && L3.w3_h2 && L3.pscale_w3 && L3.cout == 128 && L4.ks == 1 && L4.cin == 128 && L4.cout <= 64 && L4.wt_h2 && L4.pscale_h2 &&
-           ctx->pol.c3h2 != 0 && h2_wanted(ctx) && in_ld % 4 == 0 && (reinterpret_cast<uintptr_t>(in) & 15) == 0 && (ctx->pol.c3h2 == 2 || blocks >= 1024);
+           ctx->pol.c3h2 != 0 && h2_wanted(ctx) && in_ld % 4 == 0 && (reinterpret_cast<uintptr_t>(in) & 15) == 0 && (ctx->pol.c3h2 == 2 || blocks >= C3H2_MIN_BLOCKS);
 }
 static int run_conv34_fused(dt_ctx *ctx, const ConvLayer &L3, const ConvLayer &L4, const float *in, int in_ld, int B, int H, int W, float *out, int out_ld, float slope)
 {
@@ -1296,7 +1294,6 @@ static int detect_internal(dt_ctx *ctx, const void *frames, int dtype, int B, De
     float *cat = ws_get(ctx, "cat", (size_t)B * (H / 32) * (W / 32) * 1280 * sizeof(float));
     if (!bufA || !bufB || !skip || !cat) return DT_ERR_DEVICE;
     ctx->last_batch = B;
-    ctx->h2_small = B < ctx->pol.h2_minframes;
     {   // dt_detector_tap may only hand out 'feat' / 'netout' if THIS forward wrote the library-owned workspaces
         auto owned = [&](const char *name, const float *p) {
             auto it = ctx->ws.find(name);
@@ -1317,7 +1314,7 @@ static int detect_internal(dt_ctx *ctx, const void *frames, int dtype, int B, De
         if (int rcz = amax_begin(ctx)) return rcz;
         // (its epilogue takes max |x| of what it writes: conv_2's direct fp16-form kernel scales its input by it)
         // (conv_1 publishes only where conv_2 will read it: the direct fp16-form kernel)
-        const bool c2_direct = ctx->pol.c3h2 == 2 || (ctx->pol.c3h2 != 0 && (long long)B * ((H / 2 + 15) / 16) * ((W / 2 + 15) / 16) >= c3h2_min_blocks(ctx, 32));
+        const bool c2_direct = ctx->pol.c3h2 == 2 || (ctx->pol.c3h2 != 0 && (long long)B * ((H / 2 + 15) / 16) * ((W / 2 + 15) / 16) >= C3H2_MIN_BLOCKS);
         unsigned *am1 = c1s3 && h2_wanted(ctx) && c2_direct && conv1_direct_fills_amax(frames, dtype, W, ctx->conv1_w3, ctx->conv1_w3u8) ? amax_slot(ctx, 1) : nullptr;
         if (launch_conv1_direct(ctx->stream, frames, dtype, B, H, W, ctx->conv1_w, ctx->conv1_b, ctx->lut255, LEAKY,
                                 bufA, c1s3 ? ctx->conv1_w3 : nullptr, c1s3 ? ctx->conv1_w3u8 : nullptr, am1))
@@ -1342,7 +1339,7 @@ extern "C" int dt_detect_forward(dt_ctx *ctx, const void *d_frames, int frames_d
                                  float *d_feat)
 {
     if (!ctx || !d_frames) return dt_fail(ctx, DT_ERR_ARG, "null argument");
-    amax_reset(ctx);
+    call_begin(ctx, batch);
     const int G2 = (ctx->image_h / 32) * (ctx->image_w / 32);
     Dest feat{d_feat, 1024}, net{d_netout, ctx->cb};
     if (!d_feat) {
@@ -1414,7 +1411,7 @@ static bool parse_layer_name(const dt_ctx *ctx, const char *name, int *idx, int 
 extern "C" int dt_detector_extract(dt_ctx *ctx, const void *d_frames, int frames_dtype, int batch, const char *layer,
                                    float *d_out, size_t out_floats, int *shape4)
 {
-    if (ctx) amax_reset(ctx);
+    if (ctx) call_begin(ctx, batch);      // the same kernel forms as dt_detect_forward at this batch
     if (!ctx || !layer) return dt_fail(ctx, DT_ERR_ARG, "null argument");
     if (!ctx->cb) return dt_fail(ctx, DT_ERR_STATE, "dt_detector_config must be called first");
     int idx = 0, kind = 0, oh = 0, ow = 0, oc = 0;
@@ -1651,7 +1648,6 @@ static int convlstm_sequence(dt_ctx *ctx, const float *z, int Cx, int n_clips, i
                              const float *wx_wino = nullptr, const float *wh_wino = nullptr, float *xproj_ext = nullptr)
 {
     const int GG = gh * gw, F = n_clips * T, N4 = 4 * U;
-    ctx->h2_small = F < ctx->pol.h2_minframes;
     float *xproj = xproj_ext ? xproj_ext : ws_get(ctx, "trk_xproj", (size_t)F * GG * N4 * sizeof(float));
     float *cst = hseq ? ws_get(ctx, "trk_c", (size_t)n_clips * GG * U * sizeof(float)) : nullptr;
     if (!xproj || (hseq && !cst)) return DT_ERR_DEVICE;
@@ -1776,7 +1772,7 @@ static int track_recurrent_internal(dt_ctx *ctx, const float *z, int n_clips, in
 extern "C" int dt_track_forward(dt_ctx *ctx, const void *d_frames, int frames_dtype, int n_clips, int T,
                                 float *d_trk, float *d_det)
 {
-    if (ctx) amax_reset(ctx);
+    if (ctx) call_begin(ctx, n_clips * T);
     if (!ctx || !d_frames) return dt_fail(ctx, DT_ERR_ARG, "null argument");
     if (!ctx->trk_loaded) return dt_fail(ctx, DT_ERR_STATE, "tracker weights not loaded");
     if (n_clips <= 0 || T <= 0) return dt_fail(ctx, DT_ERR_ARG, "n_clips and T must be positive");
@@ -1806,7 +1802,7 @@ extern "C" int dt_track_row_width(dt_ctx *ctx)
 
 extern "C" int dt_track_detect(dt_ctx *ctx, const void *d_frames, int frames_dtype, int n_frames, float *d_z)
 {
-    if (ctx) amax_reset(ctx);
+    if (ctx) call_begin(ctx, n_frames);
     if (!ctx || !d_frames || !d_z) return dt_fail(ctx, DT_ERR_ARG, "null argument");
     if (!ctx->trk_loaded) return dt_fail(ctx, DT_ERR_STATE, "tracker weights not loaded");
     if (n_frames <= 0) return dt_fail(ctx, DT_ERR_ARG, "n_frames must be positive");
@@ -1819,7 +1815,7 @@ extern "C" int dt_track_detect(dt_ctx *ctx, const void *d_frames, int frames_dty
 
 extern "C" int dt_track_recurrent(dt_ctx *ctx, const float *d_z, int n_clips, int T, float *d_trk, float *d_det)
 {
-    if (ctx) amax_reset(ctx);
+    if (ctx) call_begin(ctx, n_clips * T);
     if (!ctx || !d_z) return dt_fail(ctx, DT_ERR_ARG, "null argument");
     if (!ctx->trk_loaded) return dt_fail(ctx, DT_ERR_STATE, "tracker weights not loaded");
     if (n_clips <= 0 || T <= 0) return dt_fail(ctx, DT_ERR_ARG, "n_clips and T must be positive");
@@ -1843,7 +1839,7 @@ extern "C" int dt_track_xproj_width(dt_ctx *ctx)
 
 extern "C" int dt_track_detect_xproj(dt_ctx *ctx, const void *d_frames, int frames_dtype, int n_frames, float *d_xp, float *d_det)
 {
-    if (ctx) amax_reset(ctx);
+    if (ctx) call_begin(ctx, n_frames);
     if (!ctx || !d_frames || !d_xp) return dt_fail(ctx, DT_ERR_ARG, "null argument");
     if (!ctx->trk_loaded) return dt_fail(ctx, DT_ERR_STATE, "tracker weights not loaded");
     if (n_frames <= 0) return dt_fail(ctx, DT_ERR_ARG, "n_frames must be positive");
@@ -1863,7 +1859,7 @@ extern "C" int dt_track_detect_xproj(dt_ctx *ctx, const void *d_frames, int fram
 
 extern "C" int dt_track_recurrent_xproj(dt_ctx *ctx, const float *d_xp, int n_clips, int T, float *d_trk)
 {
-    if (ctx) amax_reset(ctx);
+    if (ctx) call_begin(ctx, n_clips * T);
     if (!ctx || !d_xp) return dt_fail(ctx, DT_ERR_ARG, "null argument");
     if (!ctx->trk_loaded) return dt_fail(ctx, DT_ERR_STATE, "tracker weights not loaded");
     if (n_clips <= 0 || T <= 0) return dt_fail(ctx, DT_ERR_ARG, "n_clips and T must be positive");
@@ -2083,12 +2079,12 @@ extern "C" int dt_top_box(dt_ctx *ctx, const float *d_boxes, const int *d_counts
 extern "C" int dt_conv2d(dt_ctx *ctx, const float *d_in, int B, int H, int W, int Cin, const float *h_kernel, int k,
                          int Cout, const float *h_bias, float leaky_slope, int pool, float *d_out, float *d_out2)
 {
-    if (ctx) amax_reset(ctx);
+    if (ctx) call_begin(ctx, 0);
     if (!ctx || !d_in || !h_kernel || !d_out) return dt_fail(ctx, DT_ERR_ARG, "null argument");
     if (Cin % 32) return dt_fail(ctx, DT_ERR_ARG, "Cin must be a multiple of 32");
     if (k != 1 && k != 3) return dt_fail(ctx, DT_ERR_ARG, "kernel size must be 1 or 3");
     if (pool && ((H | W) & 1)) return dt_fail(ctx, DT_ERR_ARG, "pooling needs even H and W");
-    policy_from_env(ctx->pol);   // test entry point: the parity tests force policies on a live context through the environment
+    policy_refresh(ctx);   // test entry point: the parity tests force policies on a live context through the environment
     std::vector<float> zero(Cout, 0.0f);
     int rc = load_conv_layer(ctx, 0, k, Cin, Cout, h_kernel, nullptr, h_bias ? h_bias : zero.data());
     if (rc) return rc;
@@ -2125,11 +2121,11 @@ extern "C" int dt_convlstm_step(dt_ctx *ctx, const float *d_x, int B, int H, int
                                 const float *d_c, int U, const float *h_kernel, const float *h_recurrent,
                                 const float *h_bias, float *d_h_out, float *d_c_out)
 {
-    if (ctx) amax_reset(ctx);
+    if (ctx) call_begin(ctx, 0);
     if (!ctx || !d_x || !d_h || !d_c || !h_kernel || !h_recurrent || !h_bias || !d_h_out || !d_c_out)
         return dt_fail(ctx, DT_ERR_ARG, "null argument");
     if (Cx % 32 || U % 32) return dt_fail(ctx, DT_ERR_ARG, "Cx and U must be multiples of 32");
-    policy_from_env(ctx->pol);   // test entry point (see dt_conv2d)
+    policy_refresh(ctx);   // test entry point (see dt_conv2d)
     const int N4 = 4 * U, GG = H * W;
     std::vector<int> n_map;
     gate_interleave_map(U, n_map);
@@ -2194,7 +2190,7 @@ extern "C" int dt_convlstm_step(dt_ctx *ctx, const float *d_x, int B, int H, int
 extern "C" int dt_gemm_split(dt_ctx *ctx, const float *d_v, const float *d_u, int P, int Mt, int K, int N, int half, int nt, float *d_m)
 {
     if (!ctx || !d_v || !d_u || !d_m) return dt_fail(ctx, DT_ERR_ARG, "null argument");
-    amax_reset(ctx);
+    call_begin(ctx, 0);
     if (P <= 0 || Mt <= 0 || K <= 0 || N <= 0 || K % 32 || N % 128 || !wino_gemm_s3_usable(Mt, K, N) || (nt != 2 && nt != 3) || (nt == 2 && P > 64))
         return dt_fail(ctx, DT_ERR_ARG, "dt_gemm_split: unsupported shape P=%d Mt=%d K=%d N=%d nt=%d", P, Mt, K, N, nt);
     const bool rows_form = half == 2;      // the 1x1 layers' form: the kernel reads d_v as fp32 rows and splits its fragments itself
@@ -2240,26 +2236,26 @@ extern "C" int dt_gemm_split_bf16(dt_ctx *ctx, const float *d_v, const float *d_
     return dt_gemm_split(ctx, d_v, d_u, P, Mt, K, N, half, 3, d_m);
 }
 
-// Re-reads the tuning / test knobs from the environment into the context (they are otherwise read once, in
-// dt_create).  Knobs that shape the uploaded weights (DT_WINO, DT_WINO_TILE) take effect at the next weight load.
+// Re-reads the tuning / test knobs from the environment into the context (they are otherwise read in dt_create and by the
+// layer-level test entry points); the context's pin override stays.  Knobs that shape the uploaded weights (DT_WINO, DT_WINO_TILE)
+// take effect at the next weight load.
 extern "C" int dt_policy_reload(dt_ctx *ctx)
 {
     if (!ctx) return DT_ERR_ARG;
-    graphs_clear(ctx);        // a captured graph holds the launches of the OLD kernel selection
-    policy_from_env(ctx->pol);
+    policy_refresh(ctx);
     return DT_OK;
 }
 
 // One knob of ONE context, without going through the process environment (which other contexts and threads share):
-//   "pin" 1 / 0 : kernel selection independent of the batch (DT_PIN; parallel.py: deterministic=True) -- the other knobs are re-read
-//                 from the environment as dt_policy_reload does, then pinned or not.  Captured graphs are dropped only when the value changes.
+//   "pin" 1 / 0 / -1 : kernel selection independent of the batch (DT_PIN; parallel.py: deterministic=True) on / off / as DT_PIN says.
+//                      The override holds for the context's life, through every later re-read of the environment.
 extern "C" int dt_policy_set(dt_ctx *ctx, const char *name, int value)
 {
     if (!ctx || !name) return DT_ERR_ARG;
     if (strcmp(name, "pin") != 0) return dt_fail(ctx, DT_ERR_ARG, "dt_policy_set: unknown knob '%s'", name);
-    const int v = value ? 1 : 0;
-    if (v != (ctx->pol.pin ? 1 : 0)) graphs_clear(ctx);
-    policy_from_env(ctx->pol, v);
+    if (value < -1 || value > 1) return dt_fail(ctx, DT_ERR_ARG, "dt_policy_set: pin must be -1, 0 or 1 (got %d)", value);
+    ctx->pin_override = value;
+    policy_refresh(ctx);
     return DT_OK;
 }
 

@@ -194,16 +194,6 @@ template <int BIT, typename T> __device__ __forceinline__ void s3_store(unsigned
     if (WINO_S3_NT & BIT) __builtin_nontemporal_store(v, reinterpret_cast<T *>(p));
     else *reinterpret_cast<T *>(p) = v;
 }
-typedef __bf16 wino_bf2 __attribute__((ext_vector_type(2)));
-__device__ __forceinline__ void s3_split2(const VecOf<2>::T x, unsigned t[3])
-{
-    const wino_bf2 h = __builtin_convertvector(x, wino_bf2);
-    const VecOf<2>::T r1 = x - __builtin_convertvector(h, VecOf<2>::T);
-    const wino_bf2 m = __builtin_convertvector(r1, wino_bf2);
-    const VecOf<2>::T r2 = r1 - __builtin_convertvector(m, VecOf<2>::T);
-    const wino_bf2 l = __builtin_convertvector(r2, wino_bf2);
-    t[0] = __builtin_bit_cast(unsigned, h); t[1] = __builtin_bit_cast(unsigned, m); t[2] = __builtin_bit_cast(unsigned, l);
-}
 
 // ---- the fp16 form (wino_gemm_s3.hip, NT = 2): x scaled by a power of two, then  hi = f16(x), lo = f16(x - hi)  (nearest even) ----
 typedef _Float16 wino_h4 __attribute__((ext_vector_type(4)));
@@ -217,14 +207,12 @@ __device__ __forceinline__ void h2_split4(const VecOf<4>::T x, wino_u2 t[2])
 
 // One work item = (tile, V channels).  Tile (grp, ty, tx) covers virtual rows TS*ty-1 .. TS*ty+TS, cols
 // TS*tx-1 .. TS*tx+TS ('same' padding, separators and the rows/columns past the image read as zero).
-// S3: V leaves as split-bf16 terms [P][3][C/16][Mp][16] (wino_gemm_s3.hip).  Items then run (16-channel block, tile, channel group)
-// with the channel group fastest and the tile next: the 16 / V lanes of a block's channel groups and the consecutive tiles behind
-// them are CONTIGUOUS in every (position, term) plane -- a store instruction of a wavefront writes one 256-byte (V = 2) run of ONE
-// plane, where the lane-cooperative producers write eight 128-byte lines of eight planes.  Built and measured in round 4 as a
-// candidate for the big F(6x6) launches (V = 2): 12.2 ms per step against 11.5 for the cooperative producer -- kept as the
-// DT_WINO_COOP=0 form (A/B, parity tests); V = 4: the F(4x4) recurrent step with DT_WINO_COOP=0.
+// S3 (V = 4 only): V leaves as split-bf16 terms [P][3][C/16][Mp][16] (wino_gemm_s3.hip).  Items then run (16-channel block, tile,
+// channel group) with the channel group fastest and the tile next: the 4 lanes of a block's channel groups and the consecutive tiles
+// behind them are CONTIGUOUS in every (position, term) plane.  The F(4x4) recurrent step's producer where C % 32 != 0 (launch_wino_input).
 template <int TS, int V, bool S3 = false> __global__ __launch_bounds__(WINO_THREADS) void wino_input_kernel(WinoArgs p)
 {
+    static_assert(!S3 || V == 4, "the split-bf16 store is written for float4 items");
     typedef typename VecOf<V>::T T;
     constexpr int NI = TS + 2;
     const int cq_n = p.C / V;
@@ -264,7 +252,7 @@ template <int TS, int V, bool S3 = false> __global__ __launch_bounds__(WINO_THRE
             for (int i = 0; i < NI; ++i) d[i][j] = col[i];
         }
         // (Bt d) B : along the rows, stored plane by plane
-        if constexpr (S3 && V == 4) {
+        if constexpr (S3) {
             const long long term = (long long)(p.C >> 4) * p.Mp * 16;
             unsigned short *dst = p.v_s3 + ((long long)(c >> 4) * p.Mp + tile) * 16 + (c & 15);
 #pragma unroll
@@ -277,21 +265,6 @@ template <int TS, int V, bool S3 = false> __global__ __launch_bounds__(WINO_THRE
                 for (int j = 0; j < NI; ++j)
 #pragma unroll
                     for (int k = 0; k < 3; ++k) s3_store<1>(dst + ((long long)(NI * i + j) * 3 + k) * term, tr[j][k]);
-            }
-        } else if constexpr (S3 && V == 2) {
-            const long long term = (long long)(p.C >> 4) * p.Mp * 16;
-            unsigned short *dst = p.v_s3 + ((long long)(c >> 4) * p.Mp + tile) * 16 + (c & 15);
-#pragma unroll
-            for (int i = 0; i < NI; ++i) {
-                bt_1d<TS>(d[i]);
-                unsigned tr[NI][3];      // a row's splits before its stores (a VALU write to a register an in-flight store reads waits for it)
-#pragma unroll
-                for (int j = 0; j < NI; ++j) s3_split2(d[i][j], tr[j]);
-#pragma unroll
-                for (int j = 0; j < NI; ++j)
-#pragma unroll
-                    for (int k = 0; k < 3; ++k)
-                        s3_store<1>(dst + ((long long)(NI * i + j) * 3 + k) * term, tr[j][k]);
             }
         } else {
             float *dst = p.v + (long long)tile * p.C + c;
@@ -549,35 +522,20 @@ __device__ __forceinline__ void wino_item_sync()
 #endif
 }
 #define WINO_COOP_MAX_ITEMS (768 * WINO_THREADS)     // (tile, channel-pair) items below which a launch takes the cooperative kernels
-// S3: V leaves as the split-bf16 operand of wino_gemm_s3.hip, [P][3][C/16][Mp][16]; the item order then puts 4 channel
-// quads x 2 tiles in a wavefront and 2 k-blocks x 2 tile pairs in a workgroup (64-byte store runs per wave-instruction,
-// neighbours of the same 128-byte lines in the same workgroup, for the loads as well)
-template <bool S3>
 __global__ __launch_bounds__(WINO_THREADS) void wino_input_coop6_kernel(WinoArgs p)
 {
     typedef VecOf<4>::T T;
     __shared__ __attribute__((aligned(16))) float s_t[(WINO_THREADS / 8) * WINO_COOP_ITEM];
     const int cq_n = p.C / 4;
-    const int mt4 = (p.Mt + 3) & ~3;
-    const long long items = S3 ? (long long)mt4 * cq_n : (long long)p.Mt * cq_n;
+    const long long items = (long long)p.Mt * cq_n;
     const long long plane = (long long)p.Mt * p.C;
     const int sub = threadIdx.x & 7, slot = threadIdx.x >> 3;
     float *st = s_t + slot * WINO_COOP_ITEM;
     for (long long base = (long long)blockIdx.x * (WINO_THREADS / 8); base < items; base += (long long)gridDim.x * (WINO_THREADS / 8)) {
         const long long it = base + slot;
-        bool live = it < items;
-        int tile, c;
-        if (S3) {
-            const long long hi = it >> 5;                    // (k-block pair, tile group of 4), tile group fastest
-            const int tg = (int)(hi % (mt4 >> 2)), kp = (int)(hi / (mt4 >> 2));
-            tile = tg * 4 + (int)((it >> 4) & 1) * 2 + (int)((it >> 2) & 1);
-            c = (kp * 2 + (int)((it >> 3) & 1)) * 16 + (int)(it & 3) * 4;
-            live = live && tile < p.Mt;
-            if (!live) { tile = 0; c = 0; }
-        } else {
-            tile = live ? (int)(it / cq_n) : 0;
-            c = live ? (int)(it - (long long)tile * cq_n) * 4 : 0;
-        }
+        const bool live = it < items;
+        const int tile = live ? (int)(it / cq_n) : 0;
+        const int c = live ? (int)(it - (long long)tile * cq_n) * 4 : 0;
         const TileId t = tile_id(p, tile);
         T col[8];
 #pragma unroll
@@ -594,19 +552,7 @@ __global__ __launch_bounds__(WINO_THREADS) void wino_input_coop6_kernel(WinoArgs
 #pragma unroll
         for (int j = 0; j < 8; ++j) row[j] = vload<4>(st + (j * 9 + sub) * 4);     // row xi = sub: all eight columns
         bt_1d<6>(row);                           // (Bt d) B : along the row
-        if (live && S3) {
-            const long long term = (long long)(p.C >> 4) * p.Mp * 16;        // elements of one (plane, term)
-            unsigned short *dst = p.v_s3 + ((long long)(c >> 4) * p.Mp + tile) * 16 + (c & 15);
-            wino_u2 tr[8][3];       // all splits before the first store (see wino_input_s3_kernel)
-#pragma unroll
-            for (int j = 0; j < 8; ++j) s3_split4(row[j], tr[j]);
-            __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-            for (int j = 0; j < 8; ++j)
-#pragma unroll
-                for (int k = 0; k < 3; ++k)
-                    s3_store<1>(dst + ((long long)(8 * sub + j) * 3 + k) * term, tr[j][k]);
-        } else if (live) {
+        if (live) {
             float *dst = p.v + (long long)tile * p.C + c;
 #pragma unroll
             for (int j = 0; j < 8; ++j) vstore_v<4>(dst + (long long)(8 * sub + j) * plane, row[j]);
@@ -618,7 +564,7 @@ __global__ __launch_bounds__(WINO_THREADS) void wino_input_coop6_kernel(WinoArgs
 // The split-operand producer proper: EIGHT channels per lane (two float4 halves through the same column / row passes), so
 // that every (plane, term) store is 16 bytes and a wavefront -- 2 channel octets x 4 consecutive tiles -- writes whole
 // 128-byte lines of the [P][3][C/16][Mp][16] layout; the two wavefronts of a workgroup take neighbouring K blocks (the
-// other half of the same input lines).  wino_input_coop6_kernel<true> is the 4-channel form of the same thing (DT_S3_IN=0).
+// other half of the same input lines).
 #define WINO_S3IN_THREADS 128
 typedef unsigned int wino_u4 __attribute__((ext_vector_type(4)));
 // NT = 3: three bf16 terms; NT = 2: two fp16 terms of V[p] * dt_h2_base(amax of the input) * rowfac[xi] * rowfac[nu] (dt_internal.h)
@@ -900,10 +846,7 @@ int launch_wino_h2_pack(hipStream_t st, const float *u, int P, int npad, int K, 
 }
 
 // a launch this small is latency-bound on the one-thread-per-item kernels: take the cooperative form
-static inline bool wino_coop_wanted(const WinoArgs &a, long long items_pairs)
-{
-    return a.coop > 0 || (a.coop < 0 && items_pairs < (long long)WINO_COOP_MAX_ITEMS);
-}
+static inline bool wino_coop_wanted(long long items_pairs) { return items_pairs < (long long)WINO_COOP_MAX_ITEMS; }
 
 int launch_wino_input(hipStream_t st, const WinoArgs &a)
 {
@@ -913,34 +856,24 @@ int launch_wino_input(hipStream_t st, const WinoArgs &a)
         const long long wgs = ((long long)((a.Mt + 3) & ~3) * (a.C / 8) + WINO_S3IN_THREADS / 8 - 1) / (WINO_S3IN_THREADS / 8);
         // workgroup cap: 24576 (grid-stride beyond) instead of one workgroup per 16 items -- measured in the step on two boxes
         // (profiles/r06_experiments.txt section 9): 9.84-10.09 -> 9.34-9.45 ms per step for caps of 8192 .. 32768, back to 9.8 at 65536
-        const long long cap = a.grid_in > 0 ? a.grid_in : 24576;
+        const long long cap = 24576;
         const unsigned grid = (unsigned)(wgs < cap ? wgs : cap);
         if (a.ts == 6) hipLaunchKernelGGL((wino_input_s3_kernel<6, 2>), dim3(grid), dim3(WINO_S3IN_THREADS), 0, st, a);
         else hipLaunchKernelGGL((wino_input_s3_kernel<4, 2>), dim3(grid), dim3(WINO_S3IN_THREADS), 0, st, a);
     } else if (a.v_s3 && a.ts == 4) {
         if (a.C % 16 || a.Mp < a.Mt) return 2;
-        if (a.C % 32 == 0 && a.coop != 0) {      // the cooperative 8-channel form (20 instead of 44 us per recurrent step at 48 clips)
+        if (a.C % 32 == 0) {      // the cooperative 8-channel form (20 instead of 44 us per recurrent step at 48 clips)
             const long long wgs = ((long long)((a.Mt + 3) & ~3) * (a.C / 8) + WINO_S3IN_THREADS / 8 - 1) / (WINO_S3IN_THREADS / 8);
             hipLaunchKernelGGL(wino_input_s3_kernel<4>, dim3((unsigned)(wgs < 262144 ? wgs : 262144)), dim3(WINO_S3IN_THREADS), 0, st, a);
         } else
             hipLaunchKernelGGL((wino_input_kernel<4, 4, true>), dim3(wino_blocks((long long)a.Mt * (a.C / 4))), dim3(wino_threads((long long)a.Mt * (a.C / 4))), 0, st, a);
     } else if (a.v_s3) {
         if (a.ts != 6 || a.C % 32 || a.Mp < a.Mt) return 2;
-        if (a.coop == 0) {
-            // A/B (DT_WINO_COOP=0): one thread per (tile, channel pair), 256-byte runs of ONE plane per store instruction -- measured
-            // SLOWER than the cooperative producer's eight 128-byte lines of eight planes (12.2 vs 11.5 ms per step)
-            const long long items = (long long)a.Mt * (a.C / 2);
-            hipLaunchKernelGGL((wino_input_kernel<6, 2, true>), dim3(wino_blocks(items)), dim3(wino_threads(items)), 0, st, a);
-        } else if (a.coop == 2) {      // A/B: the 4-channel cooperative form
-            const long long wgs = ((long long)((a.Mt + 3) & ~3) * (a.C / 4) + WINO_THREADS / 8 - 1) / (WINO_THREADS / 8);
-            hipLaunchKernelGGL(wino_input_coop6_kernel<true>, dim3((unsigned)(wgs < 65536 ? wgs : 65536)), dim3(WINO_THREADS), 0, st, a);
-        } else {
-            const long long wgs = ((long long)((a.Mt + 3) & ~3) * (a.C / 8) + WINO_S3IN_THREADS / 8 - 1) / (WINO_S3IN_THREADS / 8);
-            hipLaunchKernelGGL(wino_input_s3_kernel<6>, dim3((unsigned)(wgs < 262144 ? wgs : 262144)), dim3(WINO_S3IN_THREADS), 0, st, a);
-        }
-    } else if (a.ts == 6 && wino_coop_wanted(a, (long long)a.Mt * (a.C / 2))) {
+        const long long wgs = ((long long)((a.Mt + 3) & ~3) * (a.C / 8) + WINO_S3IN_THREADS / 8 - 1) / (WINO_S3IN_THREADS / 8);
+        hipLaunchKernelGGL(wino_input_s3_kernel<6>, dim3((unsigned)(wgs < 262144 ? wgs : 262144)), dim3(WINO_S3IN_THREADS), 0, st, a);
+    } else if (a.ts == 6 && wino_coop_wanted((long long)a.Mt * (a.C / 2))) {
         const long long wgs = ((long long)a.Mt * (a.C / 4) + WINO_THREADS / 8 - 1) / (WINO_THREADS / 8);
-        hipLaunchKernelGGL(wino_input_coop6_kernel<false>, dim3((unsigned)(wgs < 65536 ? wgs : 65536)), dim3(WINO_THREADS), 0, st, a);
+        hipLaunchKernelGGL(wino_input_coop6_kernel, dim3((unsigned)(wgs < 65536 ? wgs : 65536)), dim3(WINO_THREADS), 0, st, a);
     } else if (a.ts == 6)
         hipLaunchKernelGGL((wino_input_kernel<6, 2>), dim3(wino_blocks((long long)a.Mt * (a.C / 2))), dim3(wino_threads((long long)a.Mt * (a.C / 2))), 0,
                            st, a);
@@ -974,16 +907,12 @@ int launch_wino_output(hipStream_t st, const WinoArgs &a, int gates)
         // vector stores need aligned rows; ragged N (conv_23-like heads) never takes this path
         if (a.N % 4 || (a.out && a.out_ld % 4) || (a.out2 && a.out2_ld % 4)) return 2;
         if (a.bias16 && (a.slope != 1.0f || a.out2 || !a.out)) return 2;      // the border corrections: linear, full-resolution epilogue only
-        if (a.ts == 6 && wino_coop_wanted(a, (long long)a.Mt * (a.N / 2))) {
+        if (a.ts == 6 && wino_coop_wanted((long long)a.Mt * (a.N / 2))) {
             const long long wgs = ((long long)a.Mt * (a.N / 4) + WINO_THREADS / 8 - 1) / (WINO_THREADS / 8);
             hipLaunchKernelGGL(wino_output_coop6_kernel, dim3((unsigned)(wgs < 65536 ? wgs : 65536)), dim3(WINO_THREADS), 0, st, a);
-        } else if (a.ts == 6) {
-            const long long items = (long long)a.Mt * (a.N / 2);
-            unsigned th = wino_threads(items), nb = wino_blocks(items);
-            if (th == WINO_THREADS && (a.thr_out == 64 || a.thr_out == 128)) { th = (unsigned)a.thr_out; nb = (unsigned)((items + th - 1) / th < 256 * 32 * (WINO_THREADS / th) ? (items + th - 1) / th : 256 * 32 * (WINO_THREADS / th)); }
-            if (a.grid_out > 0 && nb > (unsigned)a.grid_out) nb = (unsigned)a.grid_out;
-            hipLaunchKernelGGL((wino_output_kernel<6, 2>), dim3(nb), dim3(th), 0, st, a);
-        }
+        } else if (a.ts == 6)
+            hipLaunchKernelGGL((wino_output_kernel<6, 2>), dim3(wino_blocks((long long)a.Mt * (a.N / 2))), dim3(wino_threads((long long)a.Mt * (a.N / 2))),
+                               0, st, a);
         else if (a.ts == 2)
             hipLaunchKernelGGL((wino_output_kernel<2, 4>), dim3(wino_blocks((long long)a.Mt * (a.N / 4))), dim3(wino_threads((long long)a.Mt * (a.N / 4))),
                                0, st, a);

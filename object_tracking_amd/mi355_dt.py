@@ -135,6 +135,7 @@ class Context(object):
         if rc != 0:
             raise NativeError("dt_create failed (%d): %s" % (rc, self.lib.dt_last_error(None).decode()))
         self.h = h
+        self.pin = -1                   # the pin override last handed to dt_policy_set (-1: DT_PIN decides)
         self.cb = None
         self.grid = None
         self.nb_box = None
@@ -553,12 +554,14 @@ class Context(object):
         return [n for n in buf.value.decode().split("\n") if n]
 
     def reload_policy(self):
-        """re-read the DT_* tuning / test knobs from the environment (they are read once, in dt_create)"""
+        """re-read the DT_* tuning / test knobs from the environment (read in dt_create; a pin override stays)"""
         self._check(self.lib.dt_policy_reload(self.h), "dt_policy_reload")
 
     def policy_set(self, name, value):
-        """one knob of THIS context ("pin"), without the process environment (dt_policy_set)"""
+        """one knob of THIS context without the process environment (dt_policy_set): "pin" 1 / 0, or -1 to follow DT_PIN"""
         self._check(self.lib.dt_policy_set(self.h, name.encode(), int(value)), "dt_policy_set")
+        if name == "pin":
+            self.pin = int(value)
 
     def graph_enable(self, on=True):
         """hipGraph replay of the detector trunk and the ConvLSTM recurrence (low-latency serving)."""

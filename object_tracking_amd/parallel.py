@@ -172,20 +172,23 @@ def _all_to_all_rows(send, group, async_op):
 class pinned_policy(object):
     """DT_PIN=1 on ONE live context (dt_policy_set: no process-wide environment variable is touched, other contexts and threads keep
     their policy): the library's kernel selection no longer looks at the batch a call carries, so a frame is the same rounding of the
-    network whatever batch it travels in -- for any world size / `chunks`.  The context is un-pinned on exit (captured hipGraphs are
-    dropped when the value changes: a deployment that replays graphs pins its context once, not per call)."""
+    network whatever batch it travels in -- for any world size / `chunks`.  On exit the context's previous pin override comes back, so
+    nested blocks and a context pinned before (or by DT_PIN) stay pinned (captured hipGraphs are dropped when the policy changes: a
+    deployment that replays graphs pins its context once, not per call)."""
 
     def __init__(self, ctx, on=True):
         self.ctx, self.on = ctx, on
+        self.saved = None
 
     def __enter__(self):
         if self.on:
+            self.saved = self.ctx.pin
             self.ctx.policy_set("pin", 1)
         return self
 
     def __exit__(self, *exc):
         if self.on:
-            self.ctx.policy_set("pin", 0)
+            self.ctx.policy_set("pin", self.saved)
 
 
 def track_clips_frame_sharded(trk, frames, cap=None, group=None, T=None, chunks=2, stats=None, rows=None, deterministic=False):

@@ -1160,6 +1160,75 @@ def test_pinned_policy_is_batch_independent(ctx):
     assert chan_err(flat_c(plain_whole.cpu().numpy()), flat_c(whole.cpu().numpy())) < 1e-4
 
 
+def _forms(c, run):
+    """the kernel-form entries of the profile (split GEMM operand form, direct fp16-form 3x3 kernel) that `run` records"""
+    c.profile_reset(); c.profile_enable(True)
+    run()
+    c.profile_enable(False)
+    names = c.profile_names()
+    return {n: c.profile_read(n)["launches"] for n in names if n.startswith("s3_form:") or n.startswith("conv_direct_h2")}
+
+
+def test_pin_survives_pinned_policy_under_dt_pin(ctx, monkeypatch):
+    """A context created under DT_PIN=1 is still pinned after a pinned_policy block: a 16-frame forward (from 12 frames the default
+    policy takes the fp16 form) runs the split GEMM in the bf16 form only.  policy_set("pin", 0) then un-pins it."""
+    from parallel import pinned_policy
+    monkeypatch.setenv("DT_PIN", "1")
+    det, _, _ = _detector(ctx, 416, 416, 12)
+    c = det.model.ctx
+    d = dev(np.concatenate([synth.synth_clip(8, 416, 416, 2, seed=s) for s in (21, 22)]), c)
+    with pinned_policy(c):
+        pass
+    f = _forms(c, lambda: c.detect_forward(d))
+    assert f.get("s3_form:bf16x3", 0) > 0 and "s3_form:f16x2" not in f and "conv_direct_h2" not in f, f
+    c.policy_set("pin", 0)
+    f = _forms(c, lambda: c.detect_forward(d))
+    assert f.get("s3_form:f16x2", 0) > 0 and f.get("conv_direct_h2", 0) > 0, f
+
+
+def test_nested_pinned_policy_keeps_outer_pin(ctx):
+    from parallel import pinned_policy
+    det, _, _ = _detector(ctx, 416, 416, 12)
+    c = det.model.ctx
+    d = dev(np.concatenate([synth.synth_clip(8, 416, 416, 2, seed=s) for s in (23, 24)]), c)
+    with pinned_policy(c):
+        with pinned_policy(c):
+            pass
+        f = _forms(c, lambda: c.detect_forward(d))
+        assert f.get("s3_form:bf16x3", 0) > 0 and "s3_form:f16x2" not in f and "conv_direct_h2" not in f, f
+    f = _forms(c, lambda: c.detect_forward(d))
+    assert f.get("s3_form:f16x2", 0) > 0, f
+
+
+def test_policy_set_pin_holds_in_conv2d(ctx):
+    """dt_conv2d re-reads the environment on entry (the parity tests' way to force a policy): a pin set on the context survives it.
+    (Cin 256: no fused F(4x4) shape, which DT_PIN would take at any size.)"""
+    rng = np.random.default_rng(31)
+    x = torch.from_numpy(rng.standard_normal((4, 26, 26, 256)).astype(np.float32)).to(ctx.device)
+    k = (rng.standard_normal((3, 3, 256, 256)) * 0.03).astype(np.float32)
+    try:
+        ctx.policy_set("pin", 1)
+        f = _forms(ctx, lambda: ctx.conv2d(x, k))
+        assert f.get("s3_form:bf16x3", 0) > 0 and "s3_form:f16x2" not in f, f
+    finally:
+        ctx.policy_set("pin", -1)
+    f = _forms(ctx, lambda: ctx.conv2d(x, k))
+    assert f.get("s3_form:f16x2", 0) > 0, f      # (the same call un-pinned takes the fp16 form: the witness can fire)
+
+
+def test_extract_selects_kernels_as_detect_forward(ctx):
+    """dt_detector_extract picks kernel forms by its batch exactly as dt_detect_forward does: at 8 frames (below DT_H2_MINFRAMES) neither
+    runs the fp16 form, so the per-layer taps see the kernels of the forward."""
+    det, _, _ = _detector(ctx, 416, 416, 12)
+    c = det.model.ctx
+    d = dev(np.concatenate([synth.synth_clip(4, 416, 416, 2, seed=s) for s in (25, 26)]), c)
+    fwd = _forms(c, lambda: c.detect_forward(d))
+    ext = _forms(c, lambda: c.detector_extract(d, "leaky_re_lu_20"))
+    assert set(ext) == set(fwd) and "s3_form:f16x2" not in ext and "conv_direct_h2" not in ext, (fwd, ext)
+    d16 = torch.cat([d, d])
+    assert "s3_form:f16x2" in _forms(c, lambda: c.detector_extract(d16, "leaky_re_lu_20"))      # 16 frames: the fp16 form
+
+
 # ---- hipGraph replay of the launch-bound inner sequences (dt_graph_enable) ------------------
 def test_graph_replay_is_bit_identical(ctx):
     """Detector trunk, ConvLSTM recurrence and LSTM sequence captured on the second call with a shape and

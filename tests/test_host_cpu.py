@@ -37,6 +37,33 @@ def test_no_cpu_fallback_without_gpu():
         decode_netout(np.zeros((3, 3, 5, 9), dtype=np.float32), 0.5, 0.45, [1.0] * 10, 4)
 
 
+def test_pinned_policy_restores_the_previous_pin():
+    """parallel.pinned_policy hands dt_policy_set the override the context had before (Context.pin), not a fixed 0: nested blocks
+    and a context pinned by the caller or by DT_PIN (-1: follow the environment) stay pinned."""
+    import mi355_dt
+    from parallel import pinned_policy
+    sent = []
+
+    class Lib(object):
+        def dt_policy_set(self, h, name, value):
+            sent.append((name, value))
+            return 0
+
+    c = mi355_dt.Context.__new__(mi355_dt.Context)      # the Python side only: no device, no dt_create
+    c.lib, c.h, c.pin = Lib(), None, -1
+    with pinned_policy(c):
+        with pinned_policy(c):
+            assert c.pin == 1
+        assert c.pin == 1
+    assert c.pin == -1 and [v for _, v in sent] == [1, 1, 1, -1] and all(n == b"pin" for n, _ in sent)
+    c.policy_set("pin", 0)
+    with pinned_policy(c):
+        pass
+    assert c.pin == 0 and sent[-1] == (b"pin", 0)
+    with pinned_policy(c, on=False):
+        assert c.pin == 0
+
+
 def test_product_never_imports_oracle():
     pkg = os.path.join(ROOT, "object_tracking_amd")
     for dp, _, fs in os.walk(pkg):
