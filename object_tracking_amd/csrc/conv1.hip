@@ -173,28 +173,8 @@ __device__ __forceinline__ float c1_bf16_f32(unsigned short h) { return __uint_a
 // moves one float32 rounding from the activation to the weight (each product still carries exactly one rounding of 2^-24):
 // fp32 accuracy, not the same bits as the float32-frame path (tests: both within 5e-6 of the oracle, 2e-6 of each other).
 // U8 = false (float32 frames, already normalised): arbitrary values, the general three-term form with six products.
-#ifndef C1_PF
-#define C1_PF 2              // tiles of frame loads in flight ahead of the tile being computed (1 or 2)
-#endif
-#ifndef C1_LDS_BARRIER
-#define C1_LDS_BARRIER 1     // 0: __syncthreads() (round 3's form) for A/B
-#endif
-#if C1_LDS_BARRIER
+constexpr int C1_PF = 2;     // tiles of frame loads in flight ahead of the tile being computed (register sets rawA, rawB)
 #define C1_SYNC() asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory")
-#else
-#define C1_SYNC() __syncthreads()
-#endif
-#ifndef C1_NTS
-#define C1_NTS 1             // 1: the output rows as nontemporal stores (A/B builds)
-#endif
-#if C1_NTS
-#define C1_STORE(ptr, val) __builtin_nontemporal_store((val), (ptr))
-#else
-#define C1_STORE(ptr, val) (*(ptr) = (val))
-#endif
-#ifndef C1_ABLATE
-#define C1_ABLATE 0          // timing-only builds (results WRONG): 1 no output stores, 2 no frame loads, 4 no fragment reads + MFMAs, 8 no staging
-#endif
 template <bool U8, bool FULL = false>      // FULL: H and W are multiples of 16 -- every tile is whole, no bounds checks around the stores
 __global__ __launch_bounds__(256) void conv1_s3_kernel(Conv1Args p)
 {
@@ -232,12 +212,6 @@ __global__ __launch_bounds__(256) void conv1_s3_kernel(Conv1Args p)
         poff[i] = (U8 && tid < 252 && e >= 0 && e < 54) ? (e % 3) * C1_PL + r0 * 18 + e / 3 : C1_PL - 1;
     }
     auto fetch = [&](int bx, Raw &raw) {
-        if (C1_ABLATE & 2) {
-            raw.dw = 0x01020304u * (unsigned)(bx + 1);
-#pragma unroll
-            for (int c = 0; c < 3; ++c) { raw.v[0][c] = (float)(bx + c); raw.v[1][c] = (float)(bx - c); }
-            return;
-        }
         if (U8) {
             // an out-of-image dword is read from the zero words behind the weight table: no select after the load (it would wait for it)
             const int xb = 48 * bx - 4 + 4 * c0;
@@ -255,7 +229,6 @@ __global__ __launch_bounds__(256) void conv1_s3_kernel(Conv1Args p)
         }
     };
     auto stage = [&](const Raw &raw) {
-        if (C1_ABLATE & 8) { if (raw.dw == 0x12345u && raw.v[0][0] == -1.0f) s_pl[tid] = 1; return; }
         if (U8) {
 #pragma unroll
             for (int i = 0; i < 4; ++i)      // 0..255 has at most 8 significant bits: the float's high half is the exact bf16
@@ -313,7 +286,7 @@ __global__ __launch_bounds__(256) void conv1_s3_kernel(Conv1Args p)
     // One tile: planes -> LDS, barrier, the tile C1_PF ahead requested into the register set just freed, MFMAs + epilogue, barrier.
     // The barriers order LDS traffic only (C1_SYNC: lgkmcnt(0) + s_barrier): __syncthreads() also drains vmcnt, i.e. waits at
     // EVERY tile for the frame loads just issued and for the write acknowledgements of the tile's stores -- measured (round 4,
-    // tools/c1_time.py ablations): 4.47 ms with, against 1.9 ms without the loads and 1.5 ms of compute alone.
+    // ablation builds): 4.47 ms with, against 1.9 ms without the loads and 1.5 ms of compute alone.
     auto tile = [&](int bx, Raw &raw) {
         stage(raw);
         C1_SYNC();
@@ -334,7 +307,7 @@ __global__ __launch_bounds__(256) void conv1_s3_kernel(Conv1Args p)
                     for (int t = 0; t < NT; ++t) {
                         c1_us8 v;
 #pragma unroll
-                        for (int e = 0; e < 8; ++e) v[e] = (C1_ABLATE & 4) ? (unsigned short)(0x3f80 + e + gi) : s_pl[3 * t * C1_PL + aoff[kb][e] + 36 * gi];
+                        for (int e = 0; e < 8; ++e) v[e] = s_pl[3 * t * C1_PL + aoff[kb][e] + 36 * gi];
                         a[kb][t] = __builtin_bit_cast(c1_bf8, v);
                     }
 #pragma unroll
@@ -344,8 +317,7 @@ __global__ __launch_bounds__(256) void conv1_s3_kernel(Conv1Args p)
 #define C1_MM(ta, tb)                                                                                                  \
                 acc[gi] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[0][ta], bw[0][tb], acc[gi], 0, 0, 0);               \
                 acc[gi] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[1][ta], bw[1][tb], acc[gi], 0, 0, 0);
-                if (C1_ABLATE & 4) { acc[gi][0] = bias * (float)(bx + gi); }
-                else if (U8) { C1_MM(0, 2) C1_MM(0, 1) C1_MM(0, 0) }
+                if (U8) { C1_MM(0, 2) C1_MM(0, 1) C1_MM(0, 0) }
                 else { C1_MM(2 % NT, 0) C1_MM(1 % NT, 1) C1_MM(0, 2) C1_MM(1 % NT, 0) C1_MM(0, 1) C1_MM(0, 0) }
 #undef C1_MM
             }
@@ -359,9 +331,9 @@ __global__ __launch_bounds__(256) void conv1_s3_kernel(Conv1Args p)
                     const float mx = fmaxf(fmaxf(acc[gi][4 * j], acc[gi][4 * j + 1]), fmaxf(acc[gi][4 * j + 2], acc[gi][4 * j + 3])) + bias;
                     const float v = mx > 0.0f ? mx : mx * p.slope;
                     const int ox = bx * 8 + h + 2 * j;
-                    if ((C1_ABLATE & 1) ? v == 12345.678f : (FULL || (oy < H2 && ox < W2))) {
+                    if (FULL || (oy < H2 && ox < W2)) {
                         out_am = fmaxf(out_am, fabsf(v));
-                        C1_STORE(&p.out[(((long long)b * H2 + oy) * W2 + ox) * 32 + n], v);
+                        __builtin_nontemporal_store(v, &p.out[(((long long)b * H2 + oy) * W2 + ox) * 32 + n]);   // output rows stream past the caches
                     }
                 }
             }
@@ -370,7 +342,7 @@ __global__ __launch_bounds__(256) void conv1_s3_kernel(Conv1Args p)
     };
     Raw rawA, rawB;
     fetch(bx_first, rawA);
-    if (FULL && C1_PF == 2) {
+    if (FULL) {
         // Whole tiles: a loop over PAIRS of tiles in which nothing is conditional (one load and eight stores per tile), entered with
         // both prefetched tiles LANDED (one wait per workgroup walk).  The wait in front of a tile's staging then counts the stores
         // and the load issued since its own load -- vmcnt(17) -- instead of draining them: the loop head's vmcnt(0) of the guarded
@@ -387,11 +359,11 @@ __global__ __launch_bounds__(256) void conv1_s3_kernel(Conv1Args p)
         if (p.amax_out) dt_amax_publish(p.amax_out, out_am);
         return;
     }
-    if (C1_PF == 2 && bx_first + 1 < bx_last) fetch(bx_first + 1, rawB);
+    if (bx_first + 1 < bx_last) fetch(bx_first + 1, rawB);
 #pragma unroll 1
     for (int bx = bx_first; bx < bx_last; bx += C1_PF) {
         tile(bx, rawA);
-        if (C1_PF == 2 && bx + 1 < bx_last) tile(bx + 1, rawB);
+        if (bx + 1 < bx_last) tile(bx + 1, rawB);
     }
     if (p.amax_out) dt_amax_publish(p.amax_out, out_am);
 }

@@ -27,9 +27,7 @@ typedef unsigned c3_u2 __attribute__((ext_vector_type(2)));
 typedef __attribute__((address_space(3))) void c3_lptr_t;
 typedef const __attribute__((address_space(1))) void c3_gptr_t;
 
-#ifndef C3_PW
-#define C3_PW 18          // pixels per patch row in LDS (16 + 2 halo; a build switch for bank-conflict experiments)
-#endif
+constexpr int C3_PW = 18;   // pixels per patch row in LDS (16 + 2 halo)
 #define C3_THREADS 256
 #define C3_NS 3           // weight stages in the LDS ring
 

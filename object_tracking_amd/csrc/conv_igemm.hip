@@ -17,7 +17,7 @@
 //     contiguous floats per pixel (128 B, coalesced); chunk order is channel-slice
 //     outer / tap inner (k = ((ci/32)*taps + tap)*32 + ci%32) so the nine shifted
 //     re-reads of a slice hit L1/L2.
-//   * Staging (default, DT_GLDS=1): asynchronous global->LDS DMA, 1 KiB per
+//   * Staging: asynchronous global->LDS DMA, 1 KiB per
 //     wave-instruction, no staging registers and no ds_write.  LDS tiles are
 //     unpadded [rows][32] floats; the DMA writes LDS lane-linearly, so the bank
 //     conflict fix is an XOR swizzle of the 16-byte slot applied on the SOURCE
@@ -39,62 +39,17 @@
 //     channels, so the LSTM cell update happens in registers.
 //   * EPI_PARTIAL: split-K partial sums for small-M layers, combined in split
 //     order by splitk_reduce_kernel (deterministic, no atomics).
-// Build options kept for A/B (profiles/README.md): -DDT_GLDS=0 register staging
-// (global_load -> VGPR -> ds_write, rows padded to 36 floats), -DDT_BK=16 16-deep
-// chunks with three LDS stages and three workgroups per CU (same speed), and the
-// timing-only -DDT_ABLATE=mask builds of tools/ablate.sh.
 #include <cstdlib>
 
 #include "dt_internal.h"
 
-#ifndef DT_GLDS
-#define DT_GLDS 1   // 1: async global->LDS DMA staging (global_load_lds), XOR-swizzled unpadded tiles
-#endif              // 0: register staging (global_load -> VGPR -> ds_write), rows padded to 36 floats
-#ifndef DT_BK
-#define DT_BK 32    // floats of K per chunk (one barrier per chunk): 32 -> 2 LDS stages, 2 workgroups/CU;
-#endif              // 16 -> 3 LDS stages of 16 KiB (48 KiB), <= 168 registers, 3 workgroups/CU
-#define KCH DT_BK
+#define KCH 32              // floats of K per chunk (one barrier per chunk): 2 LDS stages, 2 workgroups/CU
 #define SLOTS (KCH / 4)     // 16-byte slots per LDS row
 #define RPP (64 / SLOTS)    // rows covered by one 1 KiB DMA piece (64 lanes x 16 B)
-#define KKC (KCH / 8)       // fragment reads (8 k each) per chunk
-#if DT_GLDS
-#define LDK KCH
-#define NSTAGE (DT_BK == 16 ? 3 : 2)
-#define SWZ(r) (SLOTS == 8 ? (((r) >> 1) & 7) : (((r) >> 2) & 3))   // rows sharing a 256 B bank row get distinct slots
-#else
-#if DT_BK != 32
-#error "register staging is only built for DT_BK=32"
-#endif
-#define LDK 36  // LDS row stride in floats (32 + 4 pad)
+#define LDK KCH             // LDS row stride: unpadded, the swizzle below keeps the fragment reads conflict-free
 #define NSTAGE 2
-#endif
-#define WAVES_PER_SIMD (DT_BK == 16 ? 3 : 2)
+#define SWZ(r) (((r) >> 1) & 7)   // rows sharing a 256 B bank row get distinct slots
 
-#ifndef DT_DMA_AUX
-#define DT_DMA_AUX 0   // cache-policy bits of the global_load_lds instructions (0 = default)
-#endif
-#ifdef DT_TILE_TIMING
-// debug build only (tools/tile_timing.py): per-workgroup, per-tile timestamps of the persistent loop
-#define DT_TT_BLOCKS 512
-#define DT_TT_TILES 48
-__device__ unsigned long long g_tile_times[DT_TT_BLOCKS * DT_TT_TILES * 4];
-extern "C" __attribute__((visibility("default"))) int dt_debug_tile_times(unsigned long long *dst, int clear)
-{
-    if (clear) {
-        void *p = nullptr;
-        if (hipGetSymbolAddress(&p, HIP_SYMBOL(g_tile_times)) != hipSuccess) return 1;
-        return hipMemset(p, 0, sizeof(unsigned long long) * DT_TT_BLOCKS * DT_TT_TILES * 4) == hipSuccess ? 0 : 1;
-    }
-    return hipMemcpyFromSymbol(dst, HIP_SYMBOL(g_tile_times), sizeof(unsigned long long) * DT_TT_BLOCKS * DT_TT_TILES * 4) == hipSuccess ? 0 : 1;
-}
-#define TT_STAMP(slot)                                                                                   \
-    do {                                                                                                  \
-        if (tid == 0 && blockIdx.x < DT_TT_BLOCKS && tt_i < DT_TT_TILES)                                  \
-            g_tile_times[((size_t)blockIdx.x * DT_TT_TILES + tt_i) * 4 + (slot)] = __builtin_readcyclecounter(); \
-    } while (0)
-#else
-#define TT_STAMP(slot) do { } while (0)
-#endif
 typedef __attribute__((address_space(1))) const void gptr_t;
 typedef __attribute__((address_space(3))) void lptr_t;
 
@@ -129,16 +84,12 @@ __device__ __forceinline__ void decode_row(int m, int H, int W, int &b, int &h, 
 }
 
 template <int KS, int BM, int BN, int WGM, int WGN, int ORDER, int EPI, bool PERSIST = false>
-__global__ __launch_bounds__(64 * WGM * WGN, (WGM * WGN > 4 ? (WGM * WGN) / 4 : WAVES_PER_SIMD)) void conv_igemm_f32(ConvArgs p)
+__global__ __launch_bounds__(64 * WGM * WGN, (WGM * WGN > 4 ? (WGM * WGN) / 4 : 2)) void conv_igemm_f32(ConvArgs p)
 {
     constexpr int NW = WGM * WGN;                  // wavefronts per workgroup (4, or 8 for the 256x128 tile)
     constexpr int WTM = BM / WGM, WTN = BN / WGN;  // wave tile
     constexpr int TM = WTM / 32, TN = WTN / 32;    // MFMA tiles per wave
-#if DT_GLDS
     constexpr int RPASS = NW * RPP;                // rows filled per pass of the NW waves
-#else
-    constexpr int RPASS = NW * 8;
-#endif
     constexpr int PA = BM / RPASS, PB = BN / RPASS;   // loader passes
     constexpr int TAPS = KS * KS;
 
@@ -191,19 +142,13 @@ __global__ __launch_bounds__(64 * WGM * WGN, (WGM * WGN > 4 ? (WGM * WGN) / 4 : 
     };
 
     // ---- loader set-up ----------------------------------------------------
-    // Register staging: thread -> row lr + 32*i, 16-byte slot tid&7 of the 128-byte chunk row.
     // DMA staging (global_load_lds writes LDS at wave-uniform base + lane*16): wave w, pass i
     // fills the 8 consecutive rows of group g = 4*i + w; lane -> row g*8 + lane/8, PHYSICAL
     // slot lane&7, and loads the LOGICAL slot (lane&7) ^ ((row>>1)&7) from global memory, i.e.
     // the XOR swizzle is applied on the source side and again on the fragment reads, which makes
     // the unpadded 128-byte rows conflict-free for ds_read_b128.
-#if DT_GLDS
     const int lr = wave * RPP + lane / SLOTS;              // + RPASS*i
     const int lc = ((lane % SLOTS) ^ SWZ(lr)) * 4;         // SWZ(row) does not depend on i (RPASS*i)
-#else
-    const int lr = tid >> 3;        // 0..31 row within pass
-    const int lc = (tid & 7) * 4;   // float offset within the 32-float chunk
-#endif
     const float *a_ptr[PA];
     unsigned a_mask[PA];
     const float *b_ptr[PB];
@@ -251,7 +196,6 @@ __global__ __launch_bounds__(64 * WGM * WGN, (WGM * WGN > 4 ? (WGM * WGN) / 4 : 
     const int k0 = (int)(((long long)nk_all * blockIdx.y) / gridDim.y);
     const int nk = (int)(((long long)nk_all * (blockIdx.y + 1)) / gridDim.y) - k0;
 
-#if DT_GLDS
     // one 1 KiB DMA piece per (wave, pass): 8 rows x 128 B, LDS destination wave-uniform
     const int wave_u = __builtin_amdgcn_readfirstlane(wave);
     auto dma = [&](int buf, int tap, int cc, int kc) {
@@ -265,39 +209,13 @@ __global__ __launch_bounds__(64 * WGM * WGN, (WGM * WGN > 4 ? (WGM * WGN) / 4 : 
             const bool ok = (a_mask[i] >> tap) & 1u;
             const float *src = ok ? a_ptr[i] + aoff : p.zeros;   // branch-free 'same' padding
             float *dst = sA + (buf * BM + (NW * i + wave_u) * RPP) * LDK;
-            __builtin_amdgcn_global_load_lds((gptr_t *)src, (lptr_t *)dst, 16, 0, DT_DMA_AUX);
+            __builtin_amdgcn_global_load_lds((gptr_t *)src, (lptr_t *)dst, 16, 0, 0);
         }
 #pragma unroll
         for (int i = 0; i < PB; ++i) {
             float *dst = sB + (buf * BN + (NW * i + wave_u) * RPP) * LDK;
-            __builtin_amdgcn_global_load_lds((gptr_t *)(b_ptr[i] + kc * KCH), (lptr_t *)dst, 16, 0, DT_DMA_AUX);
+            __builtin_amdgcn_global_load_lds((gptr_t *)(b_ptr[i] + kc * KCH), (lptr_t *)dst, 16, 0, 0);
         }
-    };
-#endif
-    f32x4 ra[PA], rb[PB];
-    auto gload = [&](int tap, int cc, int kc) {
-        int aoff;
-        if (KS == 1)
-            aoff = cc * 32;
-        else
-            aoff = ((tap / 3 - 1) * p.W + (tap % 3 - 1)) * p.in_ld + cc * 32;
-#pragma unroll
-        for (int i = 0; i < PA; ++i) {
-            // branch-free 'same' padding: out-of-image taps read a 16-byte block of zeros
-            const bool ok = (a_mask[i] >> tap) & 1u;
-            const float *src = ok ? a_ptr[i] + aoff : p.zeros;
-            ra[i] = *reinterpret_cast<const f32x4 *>(src);
-        }
-#pragma unroll
-        for (int i = 0; i < PB; ++i) rb[i] = *reinterpret_cast<const f32x4 *>(b_ptr[i] + kc * 32);
-    };
-    auto lstore = [&](int buf) {
-#pragma unroll
-        for (int i = 0; i < PA; ++i)
-            *reinterpret_cast<f32x4 *>(&sA[(buf * BM + lr + 32 * i) * LDK + lc]) = ra[i];
-#pragma unroll
-        for (int i = 0; i < PB; ++i)
-            *reinterpret_cast<f32x4 *>(&sB[(buf * BN + lr + 32 * i) * LDK + lc]) = rb[i];
     };
 
     f32x16 acc[TM][TN];
@@ -313,28 +231,21 @@ __global__ __launch_bounds__(64 * WGM * WGN, (WGM * WGN > 4 ? (WGM * WGN) / 4 : 
 
     // ---- main loop ----------------------------------------------------------
     // Rotated software pipeline, one barrier per 32-deep K chunk:
-    //   MFMA(kk=0) || read frags kk=1, write chunk t+1 to the other LDS buffer
-    //   MFMA(kk=1) || read frags kk=2, issue global loads of chunk t+2
+    //   MFMA(kk=0) || read frags kk=1, DMA of chunk t+1 into the other LDS buffer
+    //   MFMA(kk=1) || read frags kk=2
     //   MFMA(kk=2) || read frags kk=3
-    //   barrier
+    //   wait for the DMA, barrier
     //   MFMA(kk=3) || read frags kk=0 of chunk t+1
-    // so LDS/global instructions always issue under a queue of 16 independent
+    // so LDS/global instructions always issue under a queue of independent
     // 64-cycle MFMAs and the matrix pipe only idles for barrier skew.
     const int fr = lane & 31;          // fragment row within a 32-row tile
-    const int fk = (lane >> 5) * 4;    // k sub-slot: lanes 0-31 -> 0..3, 32-63 -> 4..7
-    (void)fk;
     struct Frag {
         f32x4 a[TM], b[TN];
     };
     auto lfrag = [&](Frag &f, int buf, int kk) {
-#if DT_GLDS
         const int ko = (((kk * 2 + (lane >> 5)) ^ SWZ(fr)) * 4);   // swizzled 16-byte slot
         const float *cA = sA + (buf * BM + wm * WTM + fr) * LDK + ko;
         const float *cB = sB + (buf * BN + wn * WTN + fr) * LDK + ko;
-#else
-        const float *cA = sA + (buf * BM + wm * WTM + fr) * LDK + fk + kk * 8;
-        const float *cB = sB + (buf * BN + wn * WTN + fr) * LDK + fk + kk * 8;
-#endif
 #pragma unroll
         for (int i = 0; i < TM; ++i) f.a[i] = *reinterpret_cast<const f32x4 *>(cA + i * 32 * LDK);
 #pragma unroll
@@ -351,15 +262,6 @@ __global__ __launch_bounds__(64 * WGM * WGN, (WGM * WGN > 4 ? (WGM * WGN) / 4 : 
                     for (int j = 0; j < TN; ++j)
                         acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x2f32(f.a[i][s], f.b[j][s], acc[i][j], 0, 0, 0);
     };
-    auto mma = [&](const Frag &f) {
-#pragma unroll
-        for (int s = 0; s < 4; ++s)
-#pragma unroll
-            for (int i = 0; i < TM; ++i)
-#pragma unroll
-                for (int j = 0; j < TN; ++j)
-                    acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x2f32(f.a[i][s], f.b[j][s], acc[i][j], 0, 0, 0);
-    };
 
     // K order is channel-chunk OUTER, tap INNER (k = (cc*TAPS + tap)*32 + c): the nine taps of one
     // 32-channel slice are consumed back to back, so their shifted re-reads of the same activation
@@ -372,11 +274,6 @@ __global__ __launch_bounds__(64 * WGM * WGN, (WGM * WGN > 4 ? (WGM * WGN) / 4 : 
         if (++gtap == TAPS) { gtap = 0; ++gcc; }
     };
     const int last_tap = (k_end - 1) % TAPS, last_cc = (k_end - 1) / TAPS;
-#ifndef DT_ABLATE
-#define DT_ABLATE 0   // timing-only ablation builds (tools/ablate.sh): results are WRONG when != 0
-#endif
-    constexpr bool AB_BARRIER = (DT_ABLATE & 1) != 0, AB_GLOAD = (DT_ABLATE & 2) != 0;
-    constexpr bool AB_LSTORE = (DT_ABLATE & 4) != 0, AB_LFRAG = (DT_ABLATE & 8) != 0;
     // ---- epilogue (per tile) --------------------------------------------------
     const int hi = lane >> 5;
     float out_am = 0.0f;      // the largest |value| this lane stored (ConvArgs::amax_out), over all its tiles
@@ -412,7 +309,7 @@ __global__ __launch_bounds__(64 * WGM * WGN, (WGM * WGN > 4 ? (WGM * WGN) / 4 : 
             return;
         }
         // Raw GEMM output (the batched Winograd GEMMs: no bias, linear): the epilogue of a 256x256 tile is VALU-issue
-        // bound (tools/tile_timing.py: 6 us), so skip the activation arithmetic and walk the rows with one pointer
+        // bound (6 us, from per-tile cycle stamps), so skip the activation arithmetic and walk the rows with one pointer
         if (EPI == EPI_PLAIN && PERSIST && p.bias == nullptr && p.slope == 1.0f && p.act == 0) {
     #pragma unroll
             for (int i = 0; i < TM; ++i)
@@ -485,58 +382,9 @@ __global__ __launch_bounds__(64 * WGM * WGN, (WGM * WGN > 4 ? (WGM * WGN) / 4 : 
             }
     };
     Frag f0, f1;
-#if DT_GLDS && DT_BK == 16
-    // 16-deep chunks, THREE 16 KiB LDS stages (48 KiB -> three workgroups per CU, three waves per
-    // SIMD within 168 registers).  The DMA of chunk t+2 is issued while chunk t is multiplied and
-    // stays in flight across the barrier (raw s_barrier + counted vmcnt: only chunk t+1's pieces
-    // are waited for), so every DMA has a whole chunk of MFMAs of cover.
-    (void)ra; (void)rb; (void)gload; (void)lstore; (void)AB_LSTORE;
-    constexpr int NPIECE = PA + PB;                       // DMA pieces per wave per chunk
-    static_assert(NPIECE >= 1 && NPIECE <= 15, "vmcnt(NPIECE) must fit the 4 low bits of the immediate");
-    constexpr int WAIT_PREV = 0x0f70 | NPIECE;            // s_waitcnt vmcnt(NPIECE): all but the newest chunk landed
-    dma(0, gtap, gcc, gk);
-    gadvance();
-    {
-        const bool in = gk < k_end;
-        dma(1, in ? gtap : last_tap, in ? gcc : last_cc, in ? gk : k_end - 1);
-        gadvance();
-    }
-    __builtin_amdgcn_s_waitcnt(WAIT_PREV);   // chunk 0 landed, chunk 1 may still fly
-    __builtin_amdgcn_s_barrier();
-    __builtin_amdgcn_sched_barrier(0);
-    lfrag(f0, 0, 0);
-    int b_cur = 0, b_nxt = 1, b_nn = 2;
-#define SB() __builtin_amdgcn_sched_barrier(0)
-    for (int kc = 0; kc < nk; ++kc) {
-        mma_part(f0, 0, 1);
-        SB();
-        if (!AB_LFRAG) lfrag(f1, b_cur, 1);
-        if (!AB_GLOAD) {
-            const bool in = gk < k_end;          // past the end: re-fetch the last chunk into a dead buffer
-            dma(b_nn, in ? gtap : last_tap, in ? gcc : last_cc, in ? gk : k_end - 1);
-            gadvance();
-        }
-        __builtin_amdgcn_sched_barrier(0x16);
-        mma_part(f0, 1, 4);
-        SB();
-        __builtin_amdgcn_s_waitcnt(WAIT_PREV);  // everything but the newest chunk has landed -> chunk t+1 ready
-        __builtin_amdgcn_s_waitcnt(0xc07f);    // lgkmcnt(0): my reads of buffer b_cur are done (it is refilled next chunk)
-        if (!AB_BARRIER) __builtin_amdgcn_s_barrier();
-        SB();
-        mma_part(f1, 0, 1);
-        SB();
-        if (!AB_LFRAG) lfrag(f0, b_nxt, 0);
-        SB();
-        mma_part(f1, 1, 4);
-        const int t = b_cur; b_cur = b_nxt; b_nxt = b_nn; b_nn = t;
-    }
-#undef SB
-    __builtin_amdgcn_s_waitcnt(0x0f70);    // drain the dead trailing DMAs before the LDS is released
-    epilogue(cur_t);   // this staging variant is launched one tile per workgroup
-#elif DT_GLDS
-    // DMA variant: chunk t+1 streams straight into the other LDS buffer while chunk t is
-    // multiplied; no staging registers, no ds_write.  The drain (vmcnt(0)) sits right before
-    // the one barrier of the iteration, a full chunk of MFMAs after the DMA was issued.
+    // Chunk t+1 streams straight into the other LDS buffer while chunk t is multiplied; no staging
+    // registers, no ds_write.  The drain (vmcnt(0)) sits right before the one barrier of the
+    // iteration, a full chunk of MFMAs after the DMA was issued.
     //
     // Every block of LDS reads / DMA issues sits AFTER the first k-step of an MFMA group and
     // BEFORE its other three (pinned with sched_barrier): hipcc waits lgkmcnt(0) ahead of the
@@ -549,7 +397,6 @@ __global__ __launch_bounds__(64 * WGM * WGN, (WGM * WGN > 4 ? (WGM * WGN) / 4 : 
     // is re-fetched into the dead buffer, which keeps the body branch-free); the fragment read
     // after the barrier is then already the next tile's first one, and the epilogue stores of this
     // tile drain underneath the next tile's MFMAs.
-    (void)ra; (void)rb; (void)gload; (void)lstore; (void)AB_LSTORE; 
     dma(0, gtap, gcc, gk);
     gadvance();
     __builtin_amdgcn_s_waitcnt(0x0f70);   // vmcnt(0)
@@ -562,125 +409,101 @@ __global__ __launch_bounds__(64 * WGM * WGN, (WGM * WGN > 4 ? (WGM * WGN) / 4 : 
             const int cur = kc & 1;
             mma_part(f0, 0, 1);
             SB();
-            if (!AB_LFRAG) lfrag(f1, cur, 1);
-            if (!AB_GLOAD) {
-                const bool in = gk < k_end;          // past the end: re-fetch the last chunk into the dead buffer
-                dma(cur ^ 1, in ? gtap : last_tap, in ? gcc : last_cc, in ? gk : k_end - 1);
-                gadvance();
-            }
+            lfrag(f1, cur, 1);
+            const bool in = gk < k_end;          // past the end: re-fetch the last chunk into the dead buffer
+            dma(cur ^ 1, in ? gtap : last_tap, in ? gcc : last_cc, in ? gk : k_end - 1);
+            gadvance();
             __builtin_amdgcn_sched_barrier(0x16);   // DS reads and MFMAs stay put; the DMA issues and their address
                                                     // VALU/SALU may sink in between the twelve MFMAs that follow
             mma_part(f0, 1, 4);
             mma_part(f1, 0, 1);
             SB();
-            if (!AB_LFRAG) lfrag(f0, cur, 2);
+            lfrag(f0, cur, 2);
             SB();
             mma_part(f1, 1, 4);
             mma_part(f0, 0, 1);
             SB();
-            if (!AB_LFRAG) lfrag(f1, cur, 3);
+            lfrag(f1, cur, 3);
             SB();
             mma_part(f0, 1, 4);
             SB();
             __builtin_amdgcn_s_waitcnt(0x0f70);   // vmcnt(0): this wave's DMA pieces of chunk t+1 have landed
-            if (!AB_BARRIER) __syncthreads();
+            __syncthreads();
             SB();
             mma_part(f1, 0, 1);
             SB();
-            if (!AB_LFRAG) lfrag(f0, cur ^ 1, 0);
+            lfrag(f0, cur ^ 1, 0);
             SB();
             mma_part(f1, 1, 4);
-        }
-        if (AB_LFRAG) {   // keep the fragments formally live
-            lfrag(f1, 0, 1);
-            mma(f1);
         }
         epilogue(cur_t);
     } else {
         int cur = 0;
-#ifdef DT_TILE_TIMING
-        int tt_i = 0;
-#endif
         for (;;) {
-            TT_STAMP(0);
             for (int kc = 0; kc < nk - 1; ++kc) {
                 mma_part(f0, 0, 1);
                 SB();
-                if (!AB_LFRAG) lfrag(f1, cur, 1);
-                if (!AB_GLOAD) {
-                    dma(cur ^ 1, gtap, gcc, gk);
-                    gadvance();
-                }
+                lfrag(f1, cur, 1);
+                dma(cur ^ 1, gtap, gcc, gk);
+                gadvance();
                 __builtin_amdgcn_sched_barrier(0x16);   // DS reads and MFMAs stay put; the DMA issues and their address
                                                         // VALU/SALU may sink in between the twelve MFMAs that follow
                 mma_part(f0, 1, 4);
                 mma_part(f1, 0, 1);
                 SB();
-                if (!AB_LFRAG) lfrag(f0, cur, 2);
+                lfrag(f0, cur, 2);
                 SB();
                 mma_part(f1, 1, 4);
                 mma_part(f0, 0, 1);
                 SB();
-                if (!AB_LFRAG) lfrag(f1, cur, 3);
+                lfrag(f1, cur, 3);
                 SB();
                 mma_part(f0, 1, 4);
                 SB();
                 __builtin_amdgcn_s_waitcnt(0x0f70);   // vmcnt(0): this wave's DMA pieces of chunk t+1 have landed
-                if (!AB_BARRIER) __syncthreads();
+                __syncthreads();
                 SB();
                 mma_part(f1, 0, 1);
                 SB();
-                if (!AB_LFRAG) lfrag(f0, cur ^ 1, 0);
+                lfrag(f0, cur ^ 1, 0);
                 SB();
                 mma_part(f1, 1, 4);
                 cur ^= 1;
             }
-            TT_STAMP(1);
             // last chunk of this tile: same body, the DMA belongs to the next tile
             const int Lnext = Lcur + (int)gridDim.x;
             const bool more = Lnext < total;
             const Tile next_t = tile_of(more ? Lnext : Lcur);
             mma_part(f0, 0, 1);
             SB();
-            if (!AB_LFRAG) lfrag(f1, cur, 1);
+            lfrag(f1, cur, 1);
             setup(next_t);
             gtap = k0 % TAPS; gcc = k0 / TAPS; gk = k0;
-            if (!AB_GLOAD) {
-                dma(cur ^ 1, gtap, gcc, gk);
-                gadvance();
-            }
+            dma(cur ^ 1, gtap, gcc, gk);
+            gadvance();
             __builtin_amdgcn_sched_barrier(0x16);
             mma_part(f0, 1, 4);
             mma_part(f1, 0, 1);
             SB();
-            if (!AB_LFRAG) lfrag(f0, cur, 2);
+            lfrag(f0, cur, 2);
             SB();
             mma_part(f1, 1, 4);
             mma_part(f0, 0, 1);
             SB();
-            if (!AB_LFRAG) lfrag(f1, cur, 3);
+            lfrag(f1, cur, 3);
             SB();
             mma_part(f0, 1, 4);
             SB();
             __builtin_amdgcn_s_waitcnt(0x0f70);
-            if (!AB_BARRIER) __syncthreads();
+            __syncthreads();
             SB();
             mma_part(f1, 0, 1);
             SB();
-            if (!AB_LFRAG) lfrag(f0, cur ^ 1, 0);
+            lfrag(f0, cur ^ 1, 0);
             SB();
             mma_part(f1, 1, 4);
             cur ^= 1;
-            if (AB_LFRAG) {   // keep the fragments formally live
-                lfrag(f1, 0, 1);
-                mma(f1);
-            }
-            TT_STAMP(2);
             epilogue(cur_t);
-            TT_STAMP(3);
-#ifdef DT_TILE_TIMING
-            ++tt_i;
-#endif
             if (!more) break;
             Lcur = Lnext;
             cur_t = next_t;
@@ -688,38 +511,6 @@ __global__ __launch_bounds__(64 * WGM * WGN, (WGM * WGN > 4 ? (WGM * WGN) / 4 : 
         }
     }
 #undef SB
-#else
-    gload(gtap, gcc, gk);
-    gadvance();
-    lstore(0);
-    if (nk > 1) { gload(gtap, gcc, gk); gadvance(); }
-    __syncthreads();
-    lfrag(f0, 0, 0);
-    // The body is branch-free so that the scheduler can interleave it with the MFMAs:
-    // past the end of K the loads re-read the last chunk and the LDS traffic goes to
-    // the buffer nobody reads again.
-    for (int kc = 0; kc < nk; ++kc) {
-        const int cur = kc & 1;
-        if (!AB_LFRAG) lfrag(f1, cur, 1);
-        if (!AB_LSTORE) lstore(cur ^ 1);                // chunk kc+1 (in registers since last iteration)
-        mma(f0);
-        if (!AB_LFRAG) lfrag(f0, cur, 2);
-        if (!AB_GLOAD) {
-            const bool in = gk < k_end;
-            gload(in ? gtap : last_tap, in ? gcc : last_cc, in ? gk : k_end - 1);
-            gadvance();
-        }
-        mma(f1);
-        if (!AB_LFRAG) lfrag(f1, cur, 3);
-        mma(f0);
-        if (!AB_BARRIER) __syncthreads();
-        __builtin_amdgcn_sched_barrier(0);   // keep the kk=3 MFMAs BELOW the barrier: they cover the reads that follow it
-        if (!AB_LFRAG) lfrag(f0, cur ^ 1, 0);
-        __builtin_amdgcn_sched_barrier(0);   // ...and keep those reads ABOVE them
-        mma(f1);
-    }
-    epilogue(cur_t);   // this staging variant is launched one tile per workgroup
-#endif
     if ((EPI == EPI_PLAIN || EPI == EPI_POOL || EPI == EPI_POOL_BOTH || EPI == EPI_S2D) && p.amax_out) dt_amax_publish(p.amax_out, out_am);
 }
 
@@ -737,7 +528,6 @@ static int launch_one(hipStream_t st, const ConvArgs &a, int ksplit = 1)
     // one workgroup per tile, or -- with more tiles than resident slots -- a persistent grid of one
     // workgroup per slot (256 CUs x 2 four-wave workgroups, or x 1 of the 8/16-wave ones) that walks the tiles
     int grid = ntm * ntn * (a.zbatch > 1 ? a.zbatch : 1);
-#if DT_GLDS && DT_BK == 32
     static const int cus = [] {
         int dev = 0, n = 0;
         if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || n <= 0)
@@ -746,7 +536,6 @@ static int launch_one(hipStream_t st, const ConvArgs &a, int ksplit = 1)
     }();
     const int slots = ((cus * (WGM * WGN > 4 ? 1 : 2)) / 8) * 8;   // multiple of 8: L % 8 stays the XCD
     if (PERSIST && ksplit == 1 && slots > 0 && grid > slots) grid = slots;
-#endif
     hipLaunchKernelGGL(kern, dim3((unsigned)grid, (unsigned)ksplit), dim3(64 * WGM * WGN), lds, st, a);
     return hipGetLastError() == hipSuccess ? 0 : 1;
 }
@@ -757,7 +546,7 @@ static int launch_cfg(hipStream_t st, const ConvArgs &a, int cfg)
     // The GEMM-shaped launches (1x1 layers and the batched Winograd GEMMs: short K, many tiles) use the
     // persistent form of the kernel; the 3x3 layers keep one tile per workgroup (long K per tile, and the
     // extra live state of the tile loop costs them registers).
-    constexpr bool P = (KS == 1 && ORDER == ORD_LINEAR && EPI == EPI_PLAIN) && DT_GLDS && DT_BK == 32;
+    constexpr bool P = (KS == 1 && ORDER == ORD_LINEAR && EPI == EPI_PLAIN);
     if (cfg == CFG_128x64) return launch_one<KS, 128, 64, 4, 1, ORDER, EPI, P>(st, a);
     if (cfg == CFG_64x128) return launch_one<KS, 64, 128, 2, 2, ORDER, EPI, P>(st, a);       // few rows (a handful of Winograd tiles)
     if (cfg == CFG_256x128) return launch_one<KS, 256, 128, 4, 2, ORDER, EPI, P>(st, a);   // 8 waves, 1 workgroup per CU

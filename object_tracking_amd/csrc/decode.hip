@@ -103,18 +103,6 @@ __device__ __forceinline__ int block_flag_scan(bool flag, int *s_wave_tot /*[DEC
     return base + within;
 }
 
-#ifdef DT_DEC_TIMING
-// debug build only (tools/dec_timing.py): phase timestamps of frame 0's workgroup
-__device__ unsigned long long g_dec_times[16];
-extern "C" __attribute__((visibility("default"))) int dt_debug_dec_times(unsigned long long *dst)
-{
-    return hipMemcpyFromSymbol(dst, HIP_SYMBOL(g_dec_times), sizeof(g_dec_times)) == hipSuccess ? 0 : 1;
-}
-#define DEC_STAMP(k) do { if (threadIdx.x == 0 && blockIdx.x == 0) g_dec_times[k] = __builtin_readcyclecounter(); } while (0)
-#else
-#define DEC_STAMP(k) do { } while (0)
-#endif
-
 struct DecodeArgs {
     const float *netout;
     long long frame_stride;
@@ -174,7 +162,6 @@ __global__ __launch_bounds__(DEC_THREADS) void decode_nms_kernel(DecodeArgs p)
     // (cell, class, score) list once that has been bucketed (8 nzcap >= 8 MC bytes: launch_decode)
     unsigned long long *s_key = BIG ? reinterpret_cast<unsigned long long *>(cand + 7 * MC) : reinterpret_cast<unsigned long long *>(s_nzk);
 
-    DEC_STAMP(0);
     // ---- phase 1: global max / min of the class logits (utils.py:263-264) ----
     float vmax = -INFINITY, vmin = INFINITY;
     const int nelem = ncell * S;
@@ -230,7 +217,6 @@ __global__ __launch_bounds__(DEC_THREADS) void decode_nms_kernel(DecodeArgs p)
     const float gmin = gmn - gmax;  // min(x - max)
     const bool rescale = gmin < -100.0f;   // utils.py:265-266
 
-    DEC_STAMP(1);
     // ---- phase 2: conf / class scores / threshold, candidate boxes -----------
     // Per staged chunk: (a) exp / sigmoid element-parallel, (b) the softmax denominator per cell, summed in class
     // order like the reference's row sum, (c) conf * (e / sum) and the threshold element-parallel -- kept scores also
@@ -263,7 +249,6 @@ __global__ __launch_bounds__(DEC_THREADS) void decode_nms_kernel(DecodeArgs p)
             if (e < ne) cbuf[e] = src[e];
         }
         __syncthreads();
-        if (c0 == 0) DEC_STAMP(9);
         const int nce = cn * p.NC;                               // class elements of the chunk: (cell lc, class c) <- e2 = lc * NC + c
         // (p) objectness first: conf * softmax <= conf, so a cell with conf <= threshold keeps no class whatever its
         // logits are -- its scores are written as 0 without evaluating a single exp (most cells of a frame)
@@ -287,7 +272,6 @@ __global__ __launch_bounds__(DEC_THREADS) void decode_nms_kernel(DecodeArgs p)
             cbuf[e] = v;
         }
         __syncthreads();
-        if (c0 == 0) DEC_STAMP(10);
         if (tid < cn && s_sum[tid] >= 0.0f) {                   // (b)
             const float *r = cbuf + tid * S + 5;
             float sum = 0.0f;
@@ -303,7 +287,6 @@ __global__ __launch_bounds__(DEC_THREADS) void decode_nms_kernel(DecodeArgs p)
             s_sum[tid] = sum;                                   // >= 0 (or NaN, which is not < 0: the cell is still scored, like the reference)
         }
         __syncthreads();
-        if (c0 == 0) DEC_STAMP(11);
         for (int e2 = tid; e2 < nce; e2 += DEC_THREADS) {       // (c)
             const int lc = p.NC == 1 ? e2 : (int)__umulhi((unsigned)e2, c_magic);
             const float sum = s_sum[lc];
@@ -321,7 +304,6 @@ __global__ __launch_bounds__(DEC_THREADS) void decode_nms_kernel(DecodeArgs p)
             }
         }
         __syncthreads();
-        if (c0 == 0) DEC_STAMP(12);
         {                                                       // (d): chunk_cells <= DEC_THREADS
             const int lc = tid;
             const bool any = lc < cn && s_kof[c0 + lc] != 0;
@@ -350,16 +332,13 @@ __global__ __launch_bounds__(DEC_THREADS) void decode_nms_kernel(DecodeArgs p)
             }
             ncand += tot;
         }
-        if (c0 == 0) DEC_STAMP(13);
         {
             float *dst = post + (long long)c0 * S;
             for (int e = tid; e < ne; e += DEC_THREADS) dst[e] = cbuf[e];
         }
-        if (c0 == 0) DEC_STAMP(14);
     }
     __syncthreads();   // post[] and candidate arrays visible to the whole workgroup
 
-    DEC_STAMP(2);
     // ---- phase 3: greedy NMS, one class per wavefront (utils.py:239-252) -----
     const int nzn = s_nzn[0];
     if (nzn <= p.nzcap) {
@@ -533,7 +512,6 @@ __global__ __launch_bounds__(DEC_THREADS) void decode_nms_kernel(DecodeArgs p)
     }
     __syncthreads();
 
-    DEC_STAMP(3);
     // ---- phase 4: final filter, output in creation order (utils.py:255) ------
     int nout = 0;
     for (int k0 = 0; k0 < ncand; k0 += DEC_THREADS) {
@@ -581,10 +559,6 @@ __global__ __launch_bounds__(DEC_THREADS) void decode_nms_kernel(DecodeArgs p)
         float *o = p.boxes + (long long)frame * total;
         for (int e = first + tid; e < total; e += DEC_THREADS) o[e] = 0.0f;
     }
-    DEC_STAMP(4);
-#ifdef DT_DEC_TIMING
-    if (tid == 0 && frame == 0) g_dec_times[8] = (unsigned long long)ncand;
-#endif
 }
 
 // floats of global scratch per frame the BIG instance needs (0: the grid fits the LDS-resident instance)

@@ -202,8 +202,6 @@ struct GemmS3Args {
     int act;
     float slope;
     int half;                  // 0: the launcher chooses between 256-row tiles (one workgroup per CU) and 128-row tiles (two per CU); 1 / -1: force
-    int waves;                 // 8 / 4 waves per workgroup (64 x BN/2 or 128 x BN/2 per wave); 0 = the default (Policy::s3_waves)
-    unsigned long long *dbg;   // -DS3_TIMING builds of the micro-benchmark only: per-wave wait cycles; otherwise null
     // the fp16 form (round 6): nt = 2 -- a / b hold TWO fp16 terms (hi, lo) of SCALED operands, [P][2][K/16][rows][16], three products per multiply
     int nt;                    // 0 / 3: three bf16 terms; 2: two fp16 terms
     const float *pscale;       // nt = 2: [P] epilogue factor of position p = 1 / (U's scale[p] * the static part of V's scale[p])

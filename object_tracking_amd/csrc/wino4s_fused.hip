@@ -38,33 +38,6 @@
 typedef __attribute__((address_space(1))) const void s4_gptr_t;
 typedef __attribute__((address_space(3))) void s4_lptr_t;
 
-#ifdef DT_S4_TIMING
-// debug build only (tools/s4_timing.py): per workgroup / wave / item cycle stamps and per-phase cycle sums
-#define S4_TT_WG 64
-#define S4_TT_ITEMS 8
-#define S4_TT_SLOTS 10     // 0 start, 1 prologue end, 2 loop end, 3 epilogue end, 4 sum(transform), 5 sum(mfma block), 6 sum(vmcnt wait, data-movement
-                           // stages), 7 sum(dma issue), 8 sum(barrier wait, data-movement stages), 9 sum(vmcnt + barrier wait, transform stages)
-__device__ unsigned long long g_s4_times[S4_TT_WG * 8 * S4_TT_ITEMS * S4_TT_SLOTS];
-extern "C" __attribute__((visibility("default"))) int dt_debug_s4_times(unsigned long long *dst, int clear)
-{
-    if (clear) {
-        void *p = nullptr;
-        if (hipGetSymbolAddress(&p, HIP_SYMBOL(g_s4_times)) != hipSuccess) return 1;
-        return hipMemset(p, 0, sizeof(g_s4_times)) == hipSuccess ? 0 : 1;
-    }
-    return hipMemcpyFromSymbol(dst, HIP_SYMBOL(g_s4_times), sizeof(g_s4_times)) == hipSuccess ? 0 : 1;
-}
-#define S4_NOW() __builtin_readcyclecounter()
-#define S4_PUT(k, v)                                                                                              \
-    do {                                                                                                          \
-        if (lane == 0 && blockIdx.x < S4_TT_WG && tt_i < S4_TT_ITEMS)                                             \
-            g_s4_times[((blockIdx.x * 8 + wave) * S4_TT_ITEMS + tt_i) * S4_TT_SLOTS + (k)] = (v);                 \
-    } while (0)
-#else
-#define S4_NOW() 0ull
-#define S4_PUT(k, v) do { } while (0)
-#endif
-
 #define S4_THREADS 512
 #define S4_UBUF (36 * 4 * 64)          // floats per U stage: [pg 9][wn 4][lane 64][4 positions]
 #define S4_VBUF (36 * 2 * 64)          // floats per V stage: [pg2 18][blk 2][lane 64][2 positions]
@@ -84,8 +57,7 @@ __device__ __forceinline__ void s4_at(T *m, int st)      // At (4x6): 6 inputs -
     m[0] = y0; m[st] = y1; m[2 * st] = y2; m[3 * st] = y3;
 }
 
-// Bt d B restricted to three xi rows (HALF 0: rows 0-2, HALF 1: rows 3-5) of one 6x6 window, in two steps so that the LDS round trip
-// of the window reads can be taken BEFORE the wave's MFMA block and the arithmetic after it (S4_TLOAD_EARLY):
+// Bt d B restricted to three xi rows (HALF 0: rows 0-2, HALF 1: rows 3-5) of one 6x6 window, in two steps:
 //   s4_window_load: the five window rows the half needs (HALF 0: rows 0-4, HALF 1: rows 1-5; 30 values); pl = window pixel (0,0) of
 //                   this lane's channel in the padded patch image
 //   s4_transform_half: column pass, row pass, stores; o = this lane's slot of pair 0 of the half in the V stage
@@ -132,37 +104,7 @@ __device__ __forceinline__ void s4_transform_half(const float (&w5)[5][6], float
     }
 }
 
-#ifndef S4_NTS
-#define S4_NTS 1            // 1: the epilogue's activation stores as nontemporal stores (A/B builds)
-#endif
-#if S4_NTS
-#define S4_STORE(ptr, val) __builtin_nontemporal_store((val), (ptr))
-#else
-#define S4_STORE(ptr, val) (*(ptr) = (val))
-#endif
-#ifndef S4_ABLATE
-#define S4_ABLATE 0         // timing-only ablation builds (results WRONG): 1 no U DMA, 2 no patch DMA, 4 no input transform, 8 no operand reads,
-                            // 16 patch addresses as for a channel-blocked input, 32 patch pieces from a contiguous source
-#endif
-#ifndef S4_SRD
-#define S4_SRD 0            // 1: patch pieces through a per-frame buffer descriptor (buffer_load ... lds): an out-of-range offset reads
-#endif                      //    zeros, so padding needs no zero-source select and an interior block costs ONE add per piece; 0: global_load_lds
-                            //    with a zero-block source.  Both pass the parity tests; measured 1.5 % SLOWER with the descriptor
-                            //    (conv_2 / 3 / 5: 8.30 / 9.94 / 9.33 against 8.17 / 9.79 / 9.17 ms): the pieces' cost is not their address work
-#ifndef S4_PRIO
-#define S4_PRIO 1           // raise the wave's issue priority while it does side work (DMA issue, input transform) beside its
-#endif                      // partner's MFMA block
-#ifndef S4_PATCH_FIRST
-#define S4_PATCH_FIRST 0    // 1: the data-movement set issues its three patch pieces (HBM: the longest latency) BEFORE its nine U pieces (L2 hits).
-#endif                      // Measured in round 4: 30.0 against 26.3 ms per step for conv_2 + 3 + 5 (and the vmcnt wait it was meant to shorten
-                            // is 50-70 cycles per stage: the pieces have long landed when a wave reaches its end-of-stage wait)
-#ifndef S4_TLOAD_EARLY
-#define S4_TLOAD_EARLY 0    // 1: the transforming set requests its 30 window values BEFORE its MFMA block and computes after it (the LDS round
-#endif                      // trip under the MFMAs).  Measured in round 4: 26.9-27.0 against 25.7-26.0 ms per step for conv_2 + 3 + 5 -- slower
-                            // (30 more live registers across the MFMA block, and the block's first operand reads queue behind the 30 requests)
-#ifndef S4_PF
-#define S4_PF 2             // MFMA operand prefetch distance in quads (1 or 2)
-#endif
+constexpr int S4_PF = 2;    // MFMA operand prefetch distance in quads
 
 template <bool POOL>
 __global__ __launch_bounds__(S4_THREADS) void wino4s_fused_kernel(Wino4FusedArgs p)
@@ -205,20 +147,9 @@ __global__ __launch_bounds__(S4_THREADS) void wino4s_fused_kernel(Wino4FusedArgs
         const int px = 4 * g + (r9 >> 1), hf = r9 & 1;
         pgeo[i] = (py << 8) | (px << 2) | (hf << 1) | ((py < 18 && r9 < 8 && px < 18) ? 1 : 0);
     }
-#if S4_SRD
-    // byte offset of the lane's 16 bytes from the block's patch origin (channel 0), or far out of range for the slots no
-    // pixel maps to: with the frame as a raw buffer (num_records = its byte size) such lanes read zeros
-    constexpr int S4_OOB = 0x40000000;
-    int pstat[3];
-#pragma unroll
-    for (int i = 0; i < 3; ++i) {
-        const int py = pgeo[i] >> 8, px = (pgeo[i] >> 2) & 63, hf = (pgeo[i] >> 1) & 1;
-        pstat[i] = (pgeo[i] & 1) ? ((py * p.W + px) * p.in_ld + hf * 4) * 4 : S4_OOB;
-    }
-    const unsigned frame_bytes = (unsigned)(((long long)(p.H - 1) * p.W + p.W - 1) * p.in_ld + p.Cin) * 4u;   // last pixel's channels end here
-#endif
     // an item = (64-channel slice nq, block pair j0, j0 + 1).  The geometry of its two block images is decoded ONCE here (the
     // integer divisions cost hundreds of cycles): origin pixel of the patch, its address for channel 0, existence.
+    // (frame, boff and interior are not read: without them hipcc spills one more SGPR, so they stay)
     struct Blk { const float *base; const float *frame; int boff; int y0, x0; bool ok, interior; };   // named members only: arrays indexed at run time land in scratch
     struct Item { int nq, j0; const float *u; Blk b0, b1; };
     auto blk_of = [&](int j, bool exists) {
@@ -243,37 +174,19 @@ __global__ __launch_bounds__(S4_THREADS) void wino4s_fused_kernel(Wino4FusedArgs
         I.b1 = blk_of(I.j0 + 1, exists);
         return I;
     };
-    // pieces w4 + 4 i (i = 0..2) of block image b01 of patch stage c (channels 8c .. 8c+7) of item I -> patch buffer buf
+    // pieces w4 + 4 i (i = 0..2) of block image b01 of patch stage c (channels 8c .. 8c+7) of item I -> patch buffer buf; the padding
+    // reads a zero block.  Through a per-frame buffer descriptor instead (buffer_load ... lds: an out-of-range offset reads zeros, an
+    // interior block costs one add per piece) it measured 1.5 % slower (conv_2 / 3 / 5: 8.30 / 9.94 / 9.33 against 8.17 / 9.79 /
+    // 9.17 ms): the pieces' cost is not their address work
     auto patch_half = [&](const Blk &B, int b01, int c, int buf, bool exists) {
         const int y0 = B.y0, x0 = B.x0;
         const float *base = B.base + 8 * c;
         const bool blk_ok = exists && B.ok;
-#if S4_SRD
-        if (!(S4_ABLATE & 48)) {
-            // raw buffer over the block's frame (word 3: 32-bit data format, no swizzle); the stage's channel offset rides in soffset
-            const __amdgpu_buffer_rsrc_t rs = __builtin_amdgcn_make_buffer_rsrc(const_cast<float *>(B.frame), 0, blk_ok ? frame_bytes : 0u, 0x00020000);
-            const bool fast = B.interior;        // wave-uniform: every pixel of the 18x18 window is inside the image
-#pragma unroll
-            for (int i = 0; i < 3; ++i) {
-                int voff = pstat[i] + B.boff;
-                if (!fast) {
-                    const int py = pgeo[i] >> 8, px = (pgeo[i] >> 2) & 63;
-                    const bool in = y0 + py >= 0 && y0 + py < p.H && x0 + px >= 0 && x0 + px < p.W;
-                    voff = in ? voff : S4_OOB;
-                }
-                __builtin_amdgcn_raw_ptr_buffer_load_lds(rs, (s4_lptr_t *)(Pb + buf * S4_PBUF + (b01 * 12 + w4 + 4 * i) * 256), 16, voff, 32 * c, 0, 0);
-            }
-            return;
-        }
-#endif
 #pragma unroll
         for (int i = 0; i < 3; ++i) {
             const int py = pgeo[i] >> 8, px = (pgeo[i] >> 2) & 63, hf = (pgeo[i] >> 1) & 1;
             const bool ok = blk_ok && (pgeo[i] & 1) && y0 + py >= 0 && y0 + py < p.H && x0 + px >= 0 && x0 + px < p.W;
             const float *src = ok ? base + (py * p.W + px) * p.in_ld + hf * 4 : p.zeros;
-            if (S4_ABLATE & 16)     // timing probe: the access pattern of a channel-blocked [C/8][H][W][8] input (values wrong)
-                src = ok ? base + (long long)c * (p.H * p.W * 8 - 8) - (long long)(y0 * p.W + x0) * (p.in_ld - 8) + (py * p.W + px) * 8 + hf * 4 : p.zeros;
-            if (S4_ABLATE & 32) src = p.u + (w4 + 4 * i) * 256 + lane * 4;                          // timing probe: a contiguous, always-valid source
             __builtin_amdgcn_global_load_lds((s4_gptr_t *)src, (s4_lptr_t *)(Pb + buf * S4_PBUF + (b01 * 12 + w4 + 4 * i) * 256), 16, 0, 0);
         }
     };
@@ -313,7 +226,6 @@ __global__ __launch_bounds__(S4_THREADS) void wino4s_fused_kernel(Wino4FusedArgs
         f32x2 a0[NB], a1[NB];
         f32x4 bq[NB];
         auto request = [&](int g, int slot) {
-            if (S4_ABLATE & 8) { a0[slot] = f32x2{1.0f, 2.0f}; a1[slot] = f32x2{3.0f, 4.0f}; bq[slot] = f32x4{1.0f, 1.0f, 1.0f, 1.0f}; return; }
             a0[slot] = *reinterpret_cast<const f32x2 *>(va + (2 * g) * 256);
             a1[slot] = *reinterpret_cast<const f32x2 *>(va + (2 * g + 1) * 256);
             bq[slot] = *reinterpret_cast<const f32x4 *>(ua + g * 1024);
@@ -338,10 +250,6 @@ __global__ __launch_bounds__(S4_THREADS) void wino4s_fused_kernel(Wino4FusedArgs
     int item = blockIdx.x;
     float out_am = 0.0f;      // the largest |value| this lane stored (Wino4FusedArgs::amax_out)
     Item cur = item_of(item, true);
-#ifdef DT_S4_TIMING
-    int tt_i = 0;
-    S4_PUT(0, S4_NOW());
-#endif
     if (vset == 0) { patch_half(cur.b0, 0, 0, 0, true); u_pieces(cur.u, 0, 0, 5); }
     else { patch_half(cur.b1, 1, 0, 0, true); u_pieces(cur.u, 0, 5, 9); patch_half(cur.b0, 0, 1, 1, npatch > 1); }
     __builtin_amdgcn_s_waitcnt(0x0f70);     // vmcnt(0)
@@ -354,28 +262,25 @@ __global__ __launch_bounds__(S4_THREADS) void wino4s_fused_kernel(Wino4FusedArgs
         const int nxt = item + (int)gridDim.x;
         const bool has_next = nxt < nitems;
         const Item nx = item_of(has_next ? nxt : item, has_next);
-#ifdef DT_S4_TIMING
-        unsigned long long tt_tr = 0, tt_mm = 0, tt_bw = 0, tt_dm = 0, tt_bd = 0, tt_wt = 0;
-#endif
-        S4_PUT(1, S4_NOW());
 #pragma unroll
         for (int i = 0; i < 36; ++i) acc[i] = f32x4{0.0f, 0.0f, 0.0f, 0.0f};
 
 #pragma unroll 1
         for (int s = 0; s < nst; ++s) {
-            [[maybe_unused]] const unsigned long long c0 = S4_NOW();
             const bool last = s + 1 == nst;
             const bool dset = vset == (s & 1);
             if (dset) {
-                if (S4_PRIO) __builtin_amdgcn_s_setprio(2);
+                __builtin_amdgcn_s_setprio(2);      // side work beside the partner's MFMA block goes at raised issue priority
                 // ---- data-movement set: U of the next stage (of this item, or stage 0 of the next item), then half a patch
                 // stage: odd s -> block image 0 of patch stage (s+3)/2, even s -> block image 1 of patch stage (s+2)/2 (the
                 // stage whose first half went out one stage earlier).  Past this item's patches the numbering continues
-                // into the next item's (npatch is even, so the buffers line up). ----
-                if (!S4_PATCH_FIRST && (!last || has_next) && !(S4_ABLATE & 1)) u_pieces(last ? nx.u : cur.u + (long long)(s + 1) * S4_UBUF, (s + 1) & 1, 0, 9);
+                // into the next item's (npatch is even, so the buffers line up).  The U pieces (L2 hits) go first: the patch
+                // pieces (HBM) first measured 30.0 against 26.3 ms per step for conv_2 + 3 + 5 in round 4, and the vmcnt wait
+                // that order was meant to shorten is 50-70 cycles per stage. ----
+                if (!last || has_next) u_pieces(last ? nx.u : cur.u + (long long)(s + 1) * S4_UBUF, (s + 1) & 1, 0, 9);
                 const int pc_all = (s + 2 + (s & 1)) >> 1;
                 const bool pnx = pc_all >= npatch;
-                if (!(S4_ABLATE & 2)) {
+                {
                     // block image (s & 1) ^ 1 of this item or the next: four wave-uniform candidates, selected on scalars
                     Blk B;
 #define S4_SEL(m) B.m = (s & 1) ? (pnx ? nx.b0.m : cur.b0.m) : (pnx ? nx.b1.m : cur.b1.m)
@@ -383,36 +288,24 @@ __global__ __launch_bounds__(S4_THREADS) void wino4s_fused_kernel(Wino4FusedArgs
 #undef S4_SEL
                     patch_half(B, (s & 1) ^ 1, pnx ? pc_all - npatch : pc_all, pc_all & 1, !pnx || has_next);
                 }
-                if (S4_PATCH_FIRST && (!last || has_next) && !(S4_ABLATE & 1)) u_pieces(last ? nx.u : cur.u + (long long)(s + 1) * S4_UBUF, (s + 1) & 1, 0, 9);
-                if (S4_PRIO) __builtin_amdgcn_s_setprio(0);
+                __builtin_amdgcn_s_setprio(0);
             }
-            [[maybe_unused]] const unsigned long long c1 = S4_NOW();
             // ---- the other set: the input transform of stage s + 1 (stage 0 of the next item after the last stage) around its MFMAs:
-            // patch buffer ((s+1)/2) & 1, channel half (s+1) & 1 (landed before the last barrier) -> V buffer (s+1) & 1 ----
-            const bool do_tr = !dset && (!last || has_next) && !(S4_ABLATE & 4);
+            // patch buffer ((s+1)/2) & 1, channel half (s+1) & 1 (landed before the last barrier) -> V buffer (s+1) & 1.  The window
+            // reads go out after the MFMA block: requested before it, they measured 26.9-27.0 against 25.7-26.0 ms per step for
+            // conv_2 + 3 + 5 in round 4 (30 more live registers across the block, whose first operand reads queue behind them). ----
+            const bool do_tr = !dset && (!last || has_next);
             const int s1 = s + 1;
-            if (S4_TLOAD_EARLY && do_tr) transform_load((s1 >> 1) & 1, s1 & 1);
             mfma_block(s & 1);
-            [[maybe_unused]] const unsigned long long c2 = S4_NOW();
             if (do_tr) {
-                if (S4_PRIO) __builtin_amdgcn_s_setprio(2);
-                if (!S4_TLOAD_EARLY) transform_load((s1 >> 1) & 1, s1 & 1);
+                __builtin_amdgcn_s_setprio(2);
+                transform_load((s1 >> 1) & 1, s1 & 1);
                 transform_compute(s1 & 1);
-                if (S4_PRIO) __builtin_amdgcn_s_setprio(0);
+                __builtin_amdgcn_s_setprio(0);
             }
-#ifdef DT_S4_TIMING
-            tt_dm += c1 - c0; tt_mm += c2 - c1; tt_tr += S4_NOW() - c2;
-#endif
-            [[maybe_unused]] const unsigned long long c3 = S4_NOW();
             __builtin_amdgcn_s_waitcnt(0x0f70);     // this wave's DMA pieces have landed
-            [[maybe_unused]] const unsigned long long c4 = S4_NOW();
             __syncthreads();
-#ifdef DT_S4_TIMING
-            if (dset) { tt_bw += c4 - c3; tt_bd += S4_NOW() - c4; }
-            else tt_wt += S4_NOW() - c3;
-#endif
         }
-        S4_PUT(2, S4_NOW());
 
         // ---- epilogue: At M' A per (tile, channel) in registers; C/D row = 4 kq + e -> tile (ty = kq, tx = e), col = channel.
         // The DMAs of the next item's first stages are already in flight / landed; nothing here touches LDS. ----
@@ -462,7 +355,7 @@ __global__ __launch_bounds__(S4_THREADS) void wino4s_fused_kernel(Wino4FusedArgs
 #pragma unroll
                                 for (int c = 0; c < 4; ++c) {
                                     if (p.amax_out) out_am = fmaxf(out_am, fabsf(m[6 * a + c][h]));
-                                    S4_STORE(&ob[a * rs + c * p.out_ld], m[6 * a + c][h]);
+                                    __builtin_nontemporal_store(m[6 * a + c][h], &ob[a * rs + c * p.out_ld]);
                                 }
                         } else {
 #pragma unroll
@@ -471,7 +364,7 @@ __global__ __launch_bounds__(S4_THREADS) void wino4s_fused_kernel(Wino4FusedArgs
                                 for (int c = 0; c < 4; ++c)
                                     if (y0 + a < p.H && x0 + 4 * e + c < p.W) {
                                         if (p.amax_out) out_am = fmaxf(out_am, fabsf(m[6 * a + c][h]));
-                                        S4_STORE(&ob[a * rs + c * p.out_ld], m[6 * a + c][h]);
+                                        __builtin_nontemporal_store(m[6 * a + c][h], &ob[a * rs + c * p.out_ld]);
                                     }
                         }
                     } else {
@@ -491,7 +384,7 @@ __global__ __launch_bounds__(S4_THREADS) void wino4s_fused_kernel(Wino4FusedArgs
 #pragma unroll
                                 for (int c2 = 0; c2 < 2; ++c2) {
                                     if (p.amax_out) out_am = fmaxf(out_am, fabsf(mx[a2][c2]));
-                                    S4_STORE(&ob[a2 * rs + c2 * p.out2_ld], mx[a2][c2]);
+                                    __builtin_nontemporal_store(mx[a2][c2], &ob[a2 * rs + c2 * p.out2_ld]);
                                 }
                         } else {
 #pragma unroll
@@ -500,18 +393,13 @@ __global__ __launch_bounds__(S4_THREADS) void wino4s_fused_kernel(Wino4FusedArgs
                                 for (int c2 = 0; c2 < 2; ++c2)
                                     if ((y0 >> 1) + a2 < H2 && (x0 >> 1) + 2 * e + c2 < W2) {
                                         if (p.amax_out) out_am = fmaxf(out_am, fabsf(mx[a2][c2]));
-                                        S4_STORE(&ob[a2 * rs + c2 * p.out2_ld], mx[a2][c2]);
+                                        __builtin_nontemporal_store(mx[a2][c2], &ob[a2 * rs + c2 * p.out2_ld]);
                                     }
                         }
                     }
                 }
             }
         }
-#ifdef DT_S4_TIMING
-        S4_PUT(3, S4_NOW()); S4_PUT(4, tt_tr); S4_PUT(5, tt_mm); S4_PUT(6, tt_bw); S4_PUT(7, tt_dm); S4_PUT(8, tt_bd); S4_PUT(9, tt_wt);
-        ++tt_i;
-        S4_PUT(0, S4_NOW());
-#endif
         if (!has_next) break;
         item = nxt;
         cur = nx;

@@ -21,8 +21,13 @@
 // Kernel: persistent; tile = BM rows of V x BN (256 | 128) rows of U; k in stages of 16 through an LDS ring filled by
 // global_load_lds_dwordx4 in 1 KiB pieces, the next tile's first stages in flight during a tile's epilogue.  Two forms:
 // BM = 256, eight waves, three stages (144 KiB, one workgroup per CU) -- or BM = 128, four waves, two stages (72 KiB, two
-// workgroups per CU) where that saves a round of tiles.  Wave (wm, wn) owns 64 rows of V x BN/2 rows of U; the MFMA takes U
-// as its A operand, so a lane holds 4 consecutive n of one m and the epilogue stores 16 B.
+// workgroups per CU) where that saves a round of tiles.  Wave (wm, wn) owns 64 rows of V x BN/2 rows of U; the MFMA takes V
+// as its A operand, so a lane holds ONE column n and 16 rows of a block, and a store instruction writes 4 bytes per lane = two
+// whole 128-byte lines (32 consecutive n of rows m, m + 4).  With U as the A operand (16-byte stores, but each instruction touches
+// 32 lines with 32 bytes) the address path of 64 scattered pieces held the accumulators (a register an in-flight store reads
+// cannot be reset) longer than four times as many line-sized stores do.  Measured (tools/micro/gemm_s3_bench,
+// profiles/r04_gemm_s3_epilogue.txt): K = 1024 5.06 -> 5.00 ms, K = 512 2.89 -> 2.78, K = 256 3.19 -> 2.96, K = 128 3.93 -> 3.43,
+// the recurrent step 0.315 -> 0.295.
 // LDS image of one (operand, term, stage): [row][2 granules of 8 bf16], granule index XOR (row >> 3) & 1 -- with the
 // ds_read_b128 lane groups of gfx950 ({0-3,12-15,20-27}, ...) every group then covers all 64 banks once
 // (SQ_LDS_BANK_CONFLICT = 0 measured).
@@ -47,20 +52,6 @@ typedef float s3_f16 __attribute__((ext_vector_type(16)));
 typedef float s3_f4 __attribute__((ext_vector_type(4)));
 typedef __attribute__((address_space(3))) void s3_lptr_t;
 typedef const __attribute__((address_space(1))) void s3_gptr_t;
-
-#ifndef S3_DEFAULT_WAVES
-#define S3_DEFAULT_WAVES 8
-#endif
-#ifndef S3_EPI_ROWS
-#define S3_EPI_ROWS 1    // 1 (default since round 4) = V is the MFMA's A operand: a lane holds ONE column n and 16 rows of a block, and a store
-#endif                   //   instruction writes 4 bytes per lane = two whole 128-byte lines (32 consecutive n of rows m, m + 4).  0 = U is the A
-                         //   operand: 16-byte stores, but each instruction touches 32 lines with 32 bytes -- the address path of 64 scattered pieces
-                         //   held the accumulators (a register an in-flight store reads cannot be reset) longer than four times as many
-                         //   line-sized stores do.  Measured (tools/micro/gemm_s3_bench, profiles/r04_gemm_s3_epilogue.txt): K = 1024 5.06 -> 5.00 ms,
-                         //   K = 512 2.89 -> 2.78, K = 256 3.19 -> 2.96, K = 128 3.93 -> 3.43, the recurrent step 0.315 -> 0.295
-#ifndef S3_ABLATE
-#define S3_ABLATE 0      // probes (tools/micro/gemm_s3_bench.hip): 1 no DMA, 2 no operand reads, 4 no barrier, 8 DMA from one tile's panels only
-#endif
 
 // ---- the 1x1 layers' A operand arrives as plain fp32 rows (the producing layer's NHWC activation) and is split here ------------------
 typedef float s3_f2 __attribute__((ext_vector_type(2)));
@@ -99,11 +90,7 @@ __device__ __forceinline__ void s3_mfma(s3_f16 &c, const s3_bf8 &a, const s3_bf8
     if constexpr (NT == 2) {
         c = __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(s3_h8, b), __builtin_bit_cast(s3_h8, a), c, 0, 0, 0);      // D[i = m][j = n]
     } else {
-#if S3_EPI_ROWS
         c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(b, a, c, 0, 0, 0);      // D[i = m][j = n]
-#else
-        c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a, b, c, 0, 0, 0);      // D[i = n][j = m]
-#endif
     }
 }
 // the partial products of one multiply, smallest first: term of U, term of V
@@ -111,13 +98,11 @@ template <int NT> struct S3Prod;
 template <> struct S3Prod<3> { static constexpr int N = 6; static constexpr int UT[6] = {2, 1, 0, 1, 0, 0}; static constexpr int VT[6] = {0, 1, 2, 0, 1, 0}; };
 template <> struct S3Prod<2> { static constexpr int N = 3; static constexpr int UT[3] = {1, 0, 0}; static constexpr int VT[3] = {0, 1, 0}; };
 
-// NW waves per workgroup: 8 = 4 (m) x 2 (n) waves of 64 x BN/2 at two waves per SIMD (<= 256 registers each);
-//                         4 = 2 x 2 waves of 128 x BN/2, one wave per SIMD with the whole 512-entry register file (256 accumulators
-//                             in AGPRs): a third fewer LDS fragment reads per MFMA (0.25 instead of 0.375 ds_read_b128).  Built
-//                             with -DS3_WITH_4WAVES only (tools/micro/gemm_s3_bench.hip, S3_WAVES=4): with one read or DMA piece
-//                             placed between every two MFMAs it runs exactly as fast as the 8-wave form -- 5.10 vs 5.03 ms, 70 %
-//                             MFMA-busy at 1.63 GHz either way.  Two very different issue streams ending at the same busy share
-//                             and clock says the matrix pipe is being throttled (power), not starved
+// NW waves per workgroup: 8 = 4 (m) x 2 (n) waves of 64 x BN/2 at two waves per SIMD (<= 256 registers each); 4 in the 128-row
+//   form.  A one-wave-per-SIMD form of the 256-row tile (2 x 2 waves of 128 x BN/2 with the whole 512-entry register file: a third
+//   fewer LDS fragment reads per MFMA) ran exactly as fast, with one read or DMA piece placed between every two MFMAs -- 5.10 vs
+//   5.03 ms, 70 % MFMA-busy at 1.63 GHz either way.  Two very different issue streams ending at the same busy share and clock says
+//   the matrix pipe is being throttled (power), not starved
 //   ACT: LeakyReLU(p.slope) on the accumulators before the epilogue's stores (the 1x1 layers); a template parameter, so that
 //   the Winograd instances carry none of it
 //   BM rows of V per tile, NS LDS stages: 256 x 3 (one workgroup per CU, 144 KiB) or 128 x 2 with four waves (72 KiB: TWO workgroups
@@ -127,7 +112,6 @@ template <> struct S3Prod<2> { static constexpr int N = 3; static constexpr int 
 template <int BN, int NW, bool ACT, int BM = 256, int NS = 3, int NT = 3>
 __device__ __forceinline__ void s3_body(const GemmS3Args &p)
 {
-    static_assert(NT == 3 || (NT == 2 && S3_EPI_ROWS), "the fp16 form has the row epilogue only");
     constexpr int NPROD = S3Prod<NT>::N;
     constexpr int WM = NW / 2;                        // waves along m (two along n)
     constexpr int MB = BM / (WM * 32);             // 32-high m blocks per wave
@@ -199,8 +183,8 @@ __device__ __forceinline__ void s3_body(const GemmS3Args &p)
     const int KBX = KB + ((NT == 3 && p.bias_s3) ? 1 : 0);      // (the fp16 form adds the bias in its epilogue: h2_bias below)
     auto issue_src = [&](const Tile &t) {
         ta = a_term; tb = b_term;
-        src_b = p.b + ((S3_ABLATE & 8) ? 0 : t.b0) + (long long)(32 * PU * wave + lrow) * 16 + dgran * 8;   // probe 8: every tile streams the same panels (L2 hits only)
-        src_a = p.a + ((S3_ABLATE & 8) ? 0 : t.a0) + (long long)(32 * PV * wave + lrow) * 16 + dgran * 8;
+        src_b = p.b + t.b0 + (long long)(32 * PU * wave + lrow) * 16 + dgran * 8;
+        src_a = p.a + t.a0 + (long long)(32 * PV * wave + lrow) * 16 + dgran * 8;
         if (VF) {
 #pragma unroll
             for (int sp = 0; sp < PVF; ++sp) {
@@ -212,7 +196,6 @@ __device__ __forceinline__ void s3_body(const GemmS3Args &p)
     };
     // one stage = PT pieces per wave (term 0..2 x {U x PU, V x PV}); pieces [lo, hi) of the stage going to buffer `buf`
     auto issue_pieces = [&](int buf, int lo, int hi) {
-        if (S3_ABLATE & 1) return;
         unsigned char *dst = s3_lds + buf * STAGE;
         int k = 0;
 #pragma unroll
@@ -299,14 +282,7 @@ __device__ __forceinline__ void s3_body(const GemmS3Args &p)
     // issuing waves (and with them the MFMA pipe) for ~400 cycles per stage.
     bool iss_go = false;       // a stage is being issued piecewise
     int iss_buf = 0;
-    auto frag = [&](const unsigned char *sb, int off) {
-        if (S3_ABLATE & 2) {
-            typedef int s3_i4 __attribute__((ext_vector_type(4)));
-            const s3_i4 x = {0x3f803f80 + (off & 1), 0x3f803f80 + (lane & 1), 0x3f003f80, 0x3f803f00 + (int)(sb - s3_lds)};
-            return __builtin_bit_cast(s3_bf8, x);
-        }
-        return *reinterpret_cast<const s3_bf8 *>(sb + off);
-    };
+    auto frag = [&](const unsigned char *sb, int off) { return *reinterpret_cast<const s3_bf8 *>(sb + off); };
     auto fragf = [&](const unsigned char *sb, int off) { return *reinterpret_cast<const s3_f4 *>(sb + off); };
     // wait until at most `keep` of this wave's DMA stages are still in flight (PT pieces per stage; 3 PV for the waves
     // that move no U rows when BN = 128 at eight waves)
@@ -325,7 +301,7 @@ __device__ __forceinline__ void s3_body(const GemmS3Args &p)
 #pragma unroll
     for (int q = 0; q < NS; ++q) issue_next();
     wait_dma(n_ahead - 1);
-    if (!(S3_ABLATE & 4)) __builtin_amdgcn_s_barrier();
+    __builtin_amdgcn_s_barrier();
     s3_bf8 v[MB][NT], vn[MB][NT], ua[NT], ub[NT];
     // VF: one pair of a fragment -> its NT terms (the fp16 form scales by the tensor's power of two first)
     auto split_to = [&](const s3_f2 x, unsigned (*t)[4], int e) {
@@ -356,10 +332,6 @@ __device__ __forceinline__ void s3_body(const GemmS3Args &p)
     [[maybe_unused]] s3_f4 vraw[MB][2];             // VF: the next stage's fp32 fragments ...
     [[maybe_unused]] unsigned vnu[MB][NT][4];       // ... and their terms, built pair by pair
     bool drain = false;       // global stores were issued since the last full wait
-#ifdef S3_TIMING
-    unsigned long long tm_lgkm = 0, tm_vm = 0, tm_bar = 0, tm_n = 0;
-    const unsigned long long tm_start = __builtin_readcyclecounter();
-#endif
 
     for (;;) {
         s3_f16 acc[NBW][MB];
@@ -381,27 +353,14 @@ __device__ __forceinline__ void s3_body(const GemmS3Args &p)
                 if (j == NBW - 1) {
                     // every read of this stage has been issued: once they are back the buffer can be refilled.  The
                     // stage after this one must have landed before its first fragments are read below.
-#ifdef S3_TIMING
-                    const unsigned long long t0 = __builtin_readcyclecounter();
-#endif
                     __builtin_amdgcn_s_waitcnt(0xc07f);                  // lgkmcnt(0)
-#ifdef S3_TIMING
-                    const unsigned long long t1 = __builtin_readcyclecounter();
-#endif
                     --n_ahead;                                           // this stage is consumed
                     // (after an epilogue: vmcnt(0).  vmcnt(63) -- "all but the newest 63 operations", i.e. the pieces issued before the
                     // epilogue's stores -- was tried in round 4: 0.5 % at best, and WRONG in the two-stage ring of the 128-row form,
                     // where a needed piece can be younger than the stores)
                     wait_dma(drain ? 0 : n_ahead - 1);
                     drain = false;
-#ifdef S3_TIMING
-                    const unsigned long long t2 = __builtin_readcyclecounter();
-#endif
-                    if (!(S3_ABLATE & 4)) __builtin_amdgcn_s_barrier();  // (no fence: a release fence would wait for the DMA in flight)
-#ifdef S3_TIMING
-                    const unsigned long long t3 = __builtin_readcyclecounter();
-                    tm_lgkm += t1 - t0; tm_vm += t2 - t1; tm_bar += t3 - t2; ++tm_n;
-#endif
+                    __builtin_amdgcn_s_barrier();  // (no fence: a release fence would wait for the DMA in flight)
                 }
                 // the group's first MFMA goes ahead of the loads for the NEXT group: the wait the compiler puts in front of
                 // it (for this group's fragments, read one group ago) then does not cover those fresh loads
@@ -416,7 +375,7 @@ __device__ __forceinline__ void s3_body(const GemmS3Args &p)
                 // accumulators (block by block in runs that share the V fragment measured the same: the kernel's clock does not care
                 // which operand repeats, profiles/r04_experiments.txt) -- with the side work placed between them in source order and frozen there (sched_barrier): one
                 // LDS fragment read or one DMA piece per MFMA slot, so that the issuing wave never leaves the pipe idle for
-                // longer than one instruction (it matters when the wave has the SIMD to itself, NW = 4).
+                // longer than one instruction.
                 //   side work: next group's U fragments (3 reads; last group: the next stage's V and first U fragments,
                 //   3 MB + 3 reads), then this group's share of the DMA pieces
                 constexpr int per = (PT + NBW - 1) / NBW, ng = (PT + per - 1) / per;   // pieces per group, groups that carry pieces
@@ -507,7 +466,6 @@ __device__ __forceinline__ void s3_body(const GemmS3Args &p)
                     for (int e = 0; e < 16; ++e) acc[j][i][e] = acc[j][i][e] > 0.0f ? acc[j][i][e] : acc[j][i][e] * p.slope;
             __builtin_amdgcn_sched_barrier(0);
         }
-#if S3_EPI_ROWS
         // ---- epilogue: lane holds, per block, column n = n0 + (lane & 31) of rows m = m0 + 8 (r / 4) + 4 (lane >> 5) + r % 4 ----
         float *cz = p.c + (long long)cur.pz * p.c_ps + cur.n0 + wn * (BN / 2) + rl;
         const int ncol = ACT ? p.N - (cur.n0 + wn * (BN / 2) + rl) : BN;      // columns of this lane's 32-column blocks that exist: 32 j < ncol
@@ -528,36 +486,7 @@ __device__ __forceinline__ void s3_body(const GemmS3Args &p)
                 }
             }
         }
-#else
-        // ---- epilogue: lane holds, per block, n = n0 + 8q + 4*(lane>>5) + (0..3) of row m = m0 + (lane & 31) ----
-        float *cz = p.c + (long long)cur.pz * p.c_ps;
-#pragma unroll
-        for (int i = 0; i < MB; ++i) {
-            const int m = cur.m0 + wm * (MB * 32) + 32 * i + rl;
-            if (m < p.Mt) {
-                float *row = cz + (long long)m * p.ldc + cur.n0 + wn * (BN / 2) + 4 * gl;
-#pragma unroll
-                for (int j = 0; j < NBW; ++j)
-#pragma unroll
-                    for (int q = 0; q < 4; ++q) {
-                        s3_f4 o;
-                        o[0] = acc[j][i][4 * q]; o[1] = acc[j][i][4 * q + 1]; o[2] = acc[j][i][4 * q + 2]; o[3] = acc[j][i][4 * q + 3];
-#if S3_ABLATE & 16
-                        *reinterpret_cast<s3_f4 *>(row + 32 * j + 8 * q) = o;      // probe 16: plain stores
-#else
-                        __builtin_nontemporal_store(o, reinterpret_cast<s3_f4 *>(row + 32 * j + 8 * q));
-#endif
-                    }
-            }
-        }
-#endif
         Lcur += G;
-#ifdef S3_TIMING
-        if (Lcur >= ntiles && lane == 0 && p.dbg) {
-            unsigned long long *d = p.dbg + ((long long)blockIdx.x * NW + wave) * 5;
-            d[0] = tm_lgkm; d[1] = tm_vm; d[2] = tm_bar; d[3] = tm_n; d[4] = __builtin_readcyclecounter() - tm_start;
-        }
-#endif
         if (Lcur >= ntiles) break;
         drain = true;
         cur = tile_of(Lcur);
@@ -565,14 +494,10 @@ __device__ __forceinline__ void s3_body(const GemmS3Args &p)
     if (ACT && p.amax_out) dt_amax_publish(p.amax_out, out_am);
 }
 
-#ifndef S3_H2_NS
-#define S3_H2_NS 4           // LDS stages of the fp16 form (32 KiB each at 256-row tiles: 128 KiB)
-#endif
-#ifndef S3_H2_HALF_NS
-#define S3_H2_HALF_NS 3      // ... of its 128-row form (24 KiB each, two workgroups per CU: 144 KiB)
-#endif
-template <int NT> constexpr int s3_ns() { return NT == 2 ? S3_H2_NS : 3; }
-template <int NT> constexpr int s3_ns_half() { return NT == 2 ? S3_H2_HALF_NS : 2; }
+// LDS stages of the fp16 form: 4 (32 KiB each at 256-row tiles: 128 KiB), 3 in its 128-row form (24 KiB each, two workgroups per
+// CU: 144 KiB)
+template <int NT> constexpr int s3_ns() { return NT == 2 ? 4 : 3; }
+template <int NT> constexpr int s3_ns_half() { return NT == 2 ? 3 : 2; }
 template <int BN, int NW, bool ACT, int NT>
 __global__ __launch_bounds__(NW * 64) void wino_gemm_s3_kernel(GemmS3Args p)
 {
@@ -584,14 +509,6 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
 {
     s3_body<BN, 4, ACT, 128, s3_ns_half<NT>(), NT>(p);
 }
-#ifdef S3_WITH_4WAVES
-// the one-wave-per-SIMD form: told so, or the register allocator budgets for two waves and spills the accumulators
-template <int BN, bool ACT, int NT>
-__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) void wino_gemm_s3_kernel_w4(GemmS3Args p)
-{
-    s3_body<BN, 4, ACT, 256, s3_ns<NT>(), NT>(p);
-}
-#endif
 
 // executed 16-bit MFMA FLOPs of one launch (six partial products per multiply in the bf16 form, three in the fp16 form)
 double wino_gemm_s3_flops(const GemmS3Args &a) { return (a.nt == 2 ? 6.0 : 12.0) * a.P * (double)a.Mt * a.K * a.N; }
@@ -661,7 +578,7 @@ int launch_wino_gemm_s3(hipStream_t st, const GemmS3Args &a, int cus)
 {
     // the Winograd form needs whole 128-column tiles; the 1x1 form (a_f32) any N >= 64 up to its padded weight rows Np
     if (a.a_f32 ? (a.Mt <= 0 || a.K < 32 || a.K % 16 || a.N < 64 || a.N > a.Np) : !wino_gemm_s3_usable(a.Mt, a.K, a.N)) return 2;
-    if (a.Mp % 256 || a.Mp < a.Mt || (!S3_EPI_ROWS && a.ldc % 4) || a.P <= 0) return 2;      // (the row-form epilogue stores 4 bytes per lane: any ldc)
+    if (a.Mp % 256 || a.Mp < a.Mt || a.P <= 0) return 2;      // (the epilogue stores 4 bytes per lane: any ldc)
     if ((a.bias_s3 != nullptr) != (a.ones != nullptr)) return 2;
     if (a.nt != 0 && a.nt != 2 && a.nt != 3) return 2;
     const bool h2 = a.nt == 2;      // the fp16 form: scaled operands, its bias (1x1 form) as plain floats for the epilogue
@@ -691,31 +608,11 @@ int launch_wino_gemm_s3(hipStream_t st, const GemmS3Args &a, int cus)
     }
     long long grid = cus;      // one workgroup per CU (108 / 144 KiB of LDS), persistent over the tiles
     if (grid > tiles) grid = tiles;
-    const int nw = a.waves == 8 ? 8 : (a.waves == 4 ? 4 : S3_DEFAULT_WAVES);
-#ifdef S3_WITH_4WAVES      // the one-wave-per-SIMD form (micro-benchmark builds)
-    if (nw == 4 && !act) {
-        static PerDeviceOnce attr4[4];
-        const size_t lds = h2 ? (size_t)s3_ns<2>() * (2 * BN * 32 + 2 * 256 * 32) + 256 : (size_t)3 * (3 * BN * 32 + 3 * 256 * 32);
-        const void *fn = h2 ? (wide ? reinterpret_cast<const void *>(wino_gemm_s3_kernel_w4<256, false, 2>) : reinterpret_cast<const void *>(wino_gemm_s3_kernel_w4<128, false, 2>))
-                            : (wide ? reinterpret_cast<const void *>(wino_gemm_s3_kernel_w4<256, false, 3>) : reinterpret_cast<const void *>(wino_gemm_s3_kernel_w4<128, false, 3>));
-        if (attr4[wide + 2 * h2].ensure(nullptr, [&](int) { return hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess; }))
-            return 1;
-        if (h2) {
-            if (wide) hipLaunchKernelGGL((wino_gemm_s3_kernel_w4<256, false, 2>), dim3((unsigned)grid), dim3(256), lds, st, a);
-            else hipLaunchKernelGGL((wino_gemm_s3_kernel_w4<128, false, 2>), dim3((unsigned)grid), dim3(256), lds, st, a);
-        } else {
-            if (wide) hipLaunchKernelGGL((wino_gemm_s3_kernel_w4<256, false, 3>), dim3((unsigned)grid), dim3(256), lds, st, a);
-            else hipLaunchKernelGGL((wino_gemm_s3_kernel_w4<128, false, 3>), dim3((unsigned)grid), dim3(256), lds, st, a);
-        }
-        return hipGetLastError() == hipSuccess ? 0 : 1;
-    }
-#endif
     if (h2) {
         if (act) return wide ? s3_launch<256, 8, true, 2>(st, a, grid) : s3_launch<128, 8, true, 2>(st, a, grid);
         return wide ? s3_launch<256, 8, false, 2>(st, a, grid) : s3_launch<128, 8, false, 2>(st, a, grid);
     }
     if (act) return wide ? s3_launch<256, 8, true, 3>(st, a, grid) : s3_launch<128, 8, true, 3>(st, a, grid);
-    (void)nw;
     return wide ? s3_launch<256, 8, false, 3>(st, a, grid) : s3_launch<128, 8, false, 3>(st, a, grid);
 }
 

@@ -26,10 +26,6 @@
 #include "dt_internal.h"
 
 #define WINO_THREADS 256
-#ifndef DT_WINO_NT
-#define DT_WINO_NT 7   // streaming (nontemporal) accesses, A/B per bit: 1 M' loads, 2 activation stores of the output transform (13.95 -> 13.25 ms
-                       // per step), 4 V stores of the input transform (-0.2 ms); 8 = activation loads of the input transform: slower (halo re-reads)
-#endif
 
 template <int V> struct VecOf;
 template <> struct VecOf<1> { typedef float T; };
@@ -44,38 +40,16 @@ template <int V> __device__ __forceinline__ void vstore(float *p, typename VecOf
 {
     *reinterpret_cast<typename VecOf<V>::T *>(p) = v;
 }
-// streaming variants (DT_WINO_NT build switch, A/B): data that is read exactly once / not re-read by this kernel
+// streaming (nontemporal) accesses, for data that this kernel reads exactly once / does not re-read: the M' loads and the activation
+// stores of the output transform (13.95 -> 13.25 ms per step), the V stores of the input transform (-0.2 ms).  The activation
+// loads of the input transform stay plain loads: streamed, they were slower (halo re-reads).
 template <int V> __device__ __forceinline__ typename VecOf<V>::T vload_nt(const float *p)
 {
-#if DT_WINO_NT & 1
     return __builtin_nontemporal_load(reinterpret_cast<const typename VecOf<V>::T *>(p));
-#else
-    return vload<V>(p);
-#endif
 }
 template <int V> __device__ __forceinline__ void vstore_nt(float *p, typename VecOf<V>::T v)
 {
-#if DT_WINO_NT & 2
     __builtin_nontemporal_store(v, reinterpret_cast<typename VecOf<V>::T *>(p));
-#else
-    vstore<V>(p, v);
-#endif
-}
-template <int V> __device__ __forceinline__ void vstore_v(float *p, typename VecOf<V>::T v)   // V planes (A/B bit 4)
-{
-#if DT_WINO_NT & 4
-    __builtin_nontemporal_store(v, reinterpret_cast<typename VecOf<V>::T *>(p));
-#else
-    vstore<V>(p, v);
-#endif
-}
-template <int V> __device__ __forceinline__ typename VecOf<V>::T vload_in(const float *p)     // activations (A/B bit 8)
-{
-#if DT_WINO_NT & 8
-    return __builtin_nontemporal_load(reinterpret_cast<const typename VecOf<V>::T *>(p));
-#else
-    return vload<V>(p);
-#endif
 }
 template <int V> __device__ __forceinline__ float lane_of(const typename VecOf<V>::T &v, int e) { return v[e]; }
 template <> __device__ __forceinline__ float lane_of<1>(const float &v, int) { return v; }
@@ -186,13 +160,10 @@ __device__ __forceinline__ void s3_split4(const VecOf<4>::T x, wino_u2 t[3])
     t[0] = __builtin_bit_cast(wino_u2, h); t[1] = __builtin_bit_cast(wino_u2, m); t[2] = __builtin_bit_cast(wino_u2, l);
 }
 
-#ifndef WINO_S3_NT
-#define WINO_S3_NT 1      // bit 0: the V terms of the input transforms as nontemporal stores (measured, profiles/r04_experiments.txt: 11.6 -> 11.1 ms per step)
-#endif
-template <int BIT, typename T> __device__ __forceinline__ void s3_store(unsigned short *p, const T &v)
+// the V terms of the input transforms as nontemporal stores (measured, profiles/r04_experiments.txt: 11.6 -> 11.1 ms per step)
+template <typename T> __device__ __forceinline__ void s3_store(unsigned short *p, const T &v)
 {
-    if (WINO_S3_NT & BIT) __builtin_nontemporal_store(v, reinterpret_cast<T *>(p));
-    else *reinterpret_cast<T *>(p) = v;
+    __builtin_nontemporal_store(v, reinterpret_cast<T *>(p));
 }
 
 // ---- the fp16 form (wino_gemm_s3.hip, NT = 2): x scaled by a power of two, then  hi = f16(x), lo = f16(x - hi)  (nearest even) ----
@@ -238,7 +209,7 @@ template <int TS, int V, bool S3 = false> __global__ __launch_bounds__(WINO_THRE
             for (int j = 0; j < NI; ++j) {
                 int b, h, w;
                 const bool ok = vpixel(p, t.grp, TS * t.ty - 1 + i, TS * t.tx - 1 + j, b, h, w);
-                d[i][j] = ok ? vload_in<V>(p.in + (long long)b * p.in_bs + (long long)(h * p.W + w) * p.in_ld + c) : vzero<V>();
+                d[i][j] = ok ? vload<V>(p.in + (long long)b * p.in_bs + (long long)(h * p.W + w) * p.in_ld + c) : vzero<V>();
             }
         }
         // Bt d : down the columns
@@ -264,7 +235,7 @@ template <int TS, int V, bool S3 = false> __global__ __launch_bounds__(WINO_THRE
 #pragma unroll
                 for (int j = 0; j < NI; ++j)
 #pragma unroll
-                    for (int k = 0; k < 3; ++k) s3_store<1>(dst + ((long long)(NI * i + j) * 3 + k) * term, tr[j][k]);
+                    for (int k = 0; k < 3; ++k) s3_store(dst + ((long long)(NI * i + j) * 3 + k) * term, tr[j][k]);
             }
         } else {
             float *dst = p.v + (long long)tile * p.C + c;
@@ -272,7 +243,7 @@ template <int TS, int V, bool S3 = false> __global__ __launch_bounds__(WINO_THRE
             for (int i = 0; i < NI; ++i) {
                 bt_1d<TS>(d[i]);
 #pragma unroll
-                for (int j = 0; j < NI; ++j) vstore_v<V>(dst + (long long)(NI * i + j) * plane, d[i][j]);
+                for (int j = 0; j < NI; ++j) vstore_nt<V>(dst + (long long)(NI * i + j) * plane, d[i][j]);
             }
         }
     }
@@ -392,9 +363,6 @@ template <int TS, int V> __global__ __launch_bounds__(WINO_THREADS) void wino_ou
 // N axis packed [j/32][gate][j%32] like EPI_GATES of conv_igemm.hip.  One work item = (tile, V hidden
 // channels): the i,f,c,o pre-activations of the recurrent convolution come out of the transform in
 // registers, the input projection (bias included) is added, c is updated in place and h written.
-#ifndef WINO_GATES_PIN
-#define WINO_GATES_PIN 1
-#endif
 template <int TS, int V> __global__ __launch_bounds__(WINO_THREADS) void wino_output_gates_kernel(WinoArgs p)
 {
     typedef typename VecOf<V>::T T;
@@ -423,14 +391,13 @@ template <int TS, int V> __global__ __launch_bounds__(WINO_THREADS) void wino_ou
         // pixels outside the frame (they re-read pixel 0; nothing is stored for them) -- not pixel by pixel behind the previous
         // pixel's stores, each a round trip of its own (round 3's form: 17 dependent round trips per item).
         constexpr int RG = TS >= 4 ? TS / 2 : TS;          // pixel rows per group (register budget: 5 V (RG TS) values in flight)
-#if WINO_GATES_PIN      // y is materialised HERE (hipcc otherwise sinks the whole transform below the first group's loads: 4 NI NI + 5 RG TS values live)
+        // y is materialised HERE (hipcc otherwise sinks the whole transform below the first group's loads: 4 NI NI + 5 RG TS values live)
 #pragma unroll
         for (int g = 0; g < 4; ++g)
 #pragma unroll
             for (int i = 0; i < TS; ++i)
 #pragma unroll
                 for (int j = 0; j < TS; ++j) asm volatile("" ::"v"(y[g][i][j]));
-#endif
 #pragma unroll
         for (int i0 = 0; i0 < TS; i0 += RG) {
             T xz[RG][TS][4], cpv[RG][TS];
@@ -504,22 +471,12 @@ static unsigned wino_blocks(long long items)
 // so all that is needed between its writes and its reads is that the compiler keeps that order (wavefront-scope fence) -- no
 // s_barrier, the wavefronts of a workgroup never wait for each other.  (Round 3 used __syncthreads() here and two LDS images per
 // item in the 8-channel kernels: 36.8 KB per 128-thread workgroup = 8 wavefronts per CU; with one image reused for both channel
-// halves and no barrier: 16 wavefronts per CU.)  WINO_WAVE_SYNC=0 restores the barriers (A/B).
-#ifndef WINO_WAVE_SYNC
-#define WINO_WAVE_SYNC 1
-#endif
-#ifndef WINO_ONE_IMAGE
-#define WINO_ONE_IMAGE WINO_WAVE_SYNC      // 8-channel kernels: one LDS image reused for both channel halves (needs the wave-local sync)
-#endif
+// halves and no barrier: 16 wavefronts per CU.)
 __device__ __forceinline__ void wino_item_sync()
 {
-#if WINO_WAVE_SYNC
     __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
     __builtin_amdgcn_wave_barrier();
     __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-#else
-    __syncthreads();
-#endif
 }
 #define WINO_COOP_MAX_ITEMS (768 * WINO_THREADS)     // (tile, channel-pair) items below which a launch takes the cooperative kernels
 __global__ __launch_bounds__(WINO_THREADS) void wino_input_coop6_kernel(WinoArgs p)
@@ -542,7 +499,7 @@ __global__ __launch_bounds__(WINO_THREADS) void wino_input_coop6_kernel(WinoArgs
         for (int i = 0; i < 8; ++i) {           // this lane's column `sub` of the 8x8 window
             int b, h, w;
             const bool ok = live && vpixel(p, t.grp, 6 * t.ty - 1 + i, 6 * t.tx - 1 + sub, b, h, w);
-            col[i] = ok ? vload_in<4>(p.in + (long long)b * p.in_bs + (long long)(h * p.W + w) * p.in_ld + c) : vzero<4>();
+            col[i] = ok ? vload<4>(p.in + (long long)b * p.in_bs + (long long)(h * p.W + w) * p.in_ld + c) : vzero<4>();
         }
         bt_1d<6>(col);                           // Bt d : down the column
 #pragma unroll
@@ -555,7 +512,7 @@ __global__ __launch_bounds__(WINO_THREADS) void wino_input_coop6_kernel(WinoArgs
         if (live) {
             float *dst = p.v + (long long)tile * p.C + c;
 #pragma unroll
-            for (int j = 0; j < 8; ++j) vstore_v<4>(dst + (long long)(8 * sub + j) * plane, row[j]);
+            for (int j = 0; j < 8; ++j) vstore_nt<4>(dst + (long long)(8 * sub + j) * plane, row[j]);
         }
         wino_item_sync();
     }
@@ -579,7 +536,7 @@ __global__ __launch_bounds__(WINO_S3IN_THREADS) void wino_input_s3_kernel(WinoAr
     // measured (profiles/r04_transform_ab.txt): the big F(6x6) launches are fastest with round 3's form -- two LDS images and a
     // workgroup barrier (11.5 vs 12.4 ms per step: the serialised halves of the one-image form cost more than its occupancy
     // returns) --, the recurrent step's small F(4x4) launch with the wave-local sync (25 vs 28 us)
-    constexpr bool ONE = WINO_ONE_IMAGE && TS == 4;
+    constexpr bool ONE = TS == 4;      // one LDS image reused for both channel halves (needs the wave-local sync)
     __shared__ __attribute__((aligned(16))) float s_t[ONE ? 1 : 2][IPW * WINO_COOP_ITEM];
     const int mt4 = (p.Mt + 3) & ~3;
     const long long items = (long long)mt4 * (p.C / 8);
@@ -604,8 +561,8 @@ __global__ __launch_bounds__(WINO_S3IN_THREADS) void wino_input_s3_kernel(WinoAr
             int b = 0, h = 0, w = 0;
             const bool ok = live && sub < NI && vpixel(p, t.grp, TS * t.ty - 1 + i, TS * t.tx - 1 + sub, b, h, w);
             const float *src = p.in + (long long)b * p.in_bs + (long long)(h * p.W + w) * p.in_ld + c;
-            ca[i] = ok ? vload_in<4>(src) : vzero<4>();
-            cb[i] = ok ? vload_in<4>(src + 4) : vzero<4>();
+            ca[i] = ok ? vload<4>(src) : vzero<4>();
+            cb[i] = ok ? vload<4>(src + 4) : vzero<4>();
         }
         bt_1d<TS>(ca);                           // Bt d : down the column
         bt_1d<TS>(cb);
@@ -653,7 +610,7 @@ if constexpr (ONE) {      // one LDS image, the two channel halves one after the
 #pragma unroll
             for (int j = 0; j < NI; ++j)
 #pragma unroll
-                for (int k = 0; k < NT; ++k) s3_store<1>(dst + ((long long)(NI * sub + j) * NT + k) * term, o[j][k]);
+                for (int k = 0; k < NT; ++k) s3_store(dst + ((long long)(NI * sub + j) * NT + k) * term, o[j][k]);
         }
         if constexpr (ONE) wino_item_sync(); else __syncthreads();
     }

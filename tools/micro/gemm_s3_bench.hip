@@ -75,17 +75,11 @@ static void run(int P, int Mt, int K, int N, int check_rows, int iters)
     hipMemset(dC, 0xff, (size_t)P * Mt * N * 4);
     GemmS3Args a = {};
     a.a = dV; a.b = dU; a.c = dC; a.c_ps = (long long)Mt * N; a.P = P; a.Mt = Mt; a.Mp = Mp; a.N = N; a.Np = Np; a.K = K; a.ldc = N;
-    a.dbg = nullptr;
     if (NT == 2) { a.nt = 2; a.pscale = dPs; a.amax = dAm; }
-    a.waves = getenv("S3_WAVES") ? atoi(getenv("S3_WAVES")) : 0;
     a.half = getenv("S3_HALF") ? atoi(getenv("S3_HALF")) : 0;
     a.act = getenv("S3_ACT") ? 1 : 0; a.slope = 0.1f;      // timing only (the check below expects the plain product)
     hipDeviceProp_t prop;
     hipGetDeviceProperties(&prop, 0);
-#ifdef S3_TIMING
-    hipMalloc(&a.dbg, 256 * 8 * 5 * 8);
-    hipMemset(a.dbg, 0, 256 * 8 * 5 * 8);
-#endif
     int rc = launch_wino_gemm_s3(0, a, prop.multiProcessorCount);
     if (rc || hipDeviceSynchronize() != hipSuccess) { printf("launch failed rc=%d %s\n", rc, hipGetErrorString(hipGetLastError())); exit(1); }
     std::vector<float> C((size_t)P * Mt * N);
@@ -130,17 +124,6 @@ static void run(int P, int Mt, int K, int N, int check_rows, int iters)
            NT, P, Mt, K, N, ms, eq, eq * (NT == 2 ? 3 : 6), sqrt(e_s3 / cnt), worst, sqrt(e_f32 / cnt), cnt);
     if (cnt_small) printf("  rows 2^-%d: rms %.3g (%lld)", smallk, sqrt(e_small / cnt_small), cnt_small);
     printf("\n");
-#ifdef S3_TIMING
-    {
-        std::vector<unsigned long long> h(256 * 8 * 5);
-        hipMemcpy(h.data(), a.dbg, h.size() * 8, hipMemcpyDeviceToHost);
-        double s[5] = {0, 0, 0, 0, 0}; int n = 0;
-        for (int w = 0; w < 256 * 8; ++w) if (h[w * 5 + 3]) { for (int k = 0; k < 5; ++k) s[k] += (double)h[w * 5 + k]; ++n; }
-        if (n) printf("   timing (mean per wave over %d waves, clock64 ticks): total %.0f; per stage: lgkm wait %.1f, DMA wait %.1f, barrier %.1f, whole stage %.1f (%0.f stages)\n",
-                      n, s[4] / n, s[0] / s[3], s[1] / s[3], s[2] / s[3], s[4] / s[3], s[3] / n);
-        hipFree(a.dbg);
-    }
-#endif
     hipFree(dV); hipFree(dU); hipFree(dC); hipFree(dPs); hipFree(dAm);
 }
 
