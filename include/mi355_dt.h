@@ -48,7 +48,7 @@ DT_API int dt_create(dt_ctx **out);
 DT_API void dt_destroy(dt_ctx *ctx);
 DT_API const char *dt_last_error(dt_ctx *ctx);
 DT_API int dt_set_stream(dt_ctx *ctx, void *hip_stream);
-/* ABI version of this header: major*100+minor (1.07: 1.06 + dt_gemm_split, dt_policy_set) */
+/* ABI version of this header: major*100+minor (1.08: 1.07 + dt_amax_read; 1.07: 1.06 + dt_gemm_split, dt_policy_set) */
 DT_API int dt_abi_version(void);
 
 /* ---- detector: KerasYOLO ---------------------------------------------- */
@@ -300,6 +300,14 @@ DT_API int dt_policy_reload(dt_ctx *ctx);
  * -1 = follow DT_PIN again.  The override persists through dt_policy_reload and the test entry points' re-reads.  Any other
  * name or value fails with DT_ERR_ARG. */
 DT_API int dt_policy_set(dt_ctx *ctx, const char *name, int value);
+/* The max |x| the fp16 form scales a tensor by, as the kernels read it: synchronises the context's stream and returns in *h_out the
+ * maximum over the sub-words of max-|x| slot `slot` (0..127).  Slot map: 0 = 1.0 (the recurrent step's bound |h| <= 1); i in 1..23 =
+ * the output of conv_i as its consumer reads it (pooled where the layer pools, the space_to_depth tensor for conv_21; slot 20 becomes
+ * the whole concat read by conv_22), published by the producing kernel's epilogue and zeroed at the start of every detector forward;
+ * 32 + i = the input of conv_i where conv_i measured it itself; 56 = the tracker's z rows (ConvLSTM input projection); 57, 58 = the
+ * layer-level test entry points' inputs (dt_conv2d / dt_convlstm_step: x, h); 64.. = scratch of the weight packs.  DT_AMAX_MEASURE=1
+ * makes every consumer measure its input (32 + i / 56 / 57) while the producers still publish (tests compare the two). */
+DT_API int dt_amax_read(dt_ctx *ctx, int slot, float *h_out);
 
 /* ---- profiling --------------------------------------------------------- */
 /* When enabled every kernel launch is bracketed by HIP events on the ctx

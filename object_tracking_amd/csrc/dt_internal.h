@@ -435,6 +435,8 @@ struct Policy {
                                   // batch 8 (conv_10 / 12: 5408 rows = 22 workgroups) the fp32 kernel with split-K is faster (0.035 vs 0.061 ms)
     int s3_1x1 = 1;          // DT_S3_1X1: the 1x1 layers with N % 128 == 0 run on wino_gemm_s3.hip straight from the fp32 activation (the kernel splits
                              //            its A fragments itself); 0 = fp32 MFMA
+    int amax_measure = 0;    // DT_AMAX_MEASURE: 1 = every fp16-form consumer measures its input's max |x| into its own slot (32 + i / 56 / 57) and ignores
+                             //                  the producers' tags (the producers still publish): tests compare the published words with the measured ones
 };
 
 struct dt_ctx {

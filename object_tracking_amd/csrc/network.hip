@@ -208,11 +208,15 @@ static int amax_begin(dt_ctx *ctx)
 static int amax_out_slot(const ConvLayer &L) { return L.idx >= 1 && L.idx <= 23 ? L.idx : 0; }
 static const unsigned *ensure_amax(dt_ctx *ctx, const float *x, long long rows, int cols, long long ld, int slot)
 {
-    for (const auto &t : ctx->amax_tag)
-        if (t.lo == x && t.hi == x + rows * ld && t.cols == cols) return amax_slot(ctx, t.slot);
+    if (!ctx->pol.amax_measure)      // (DT_AMAX_MEASURE: measure what a producer published too, so that the two words can be compared)
+        for (const auto &t : ctx->amax_tag)
+            if (t.lo == x && t.hi == x + rows * ld && t.cols == cols) return amax_slot(ctx, t.slot);
     unsigned *s = amax_slot(ctx, slot);
     if (!s) { dt_fail(ctx, DT_ERR_STATE, "max-|x| slots not allocated"); return nullptr; }
-    ProfScope ps(ctx, "absmax", 0.0, 4.0 * (double)rows * cols);
+    char tag[16];      // whose input this is: absmax:conv_i / absmax:trk / absmax:test
+    if (slot > AMAX_IN && slot < AMAX_TRK) snprintf(tag, sizeof(tag), "conv_%d", slot - AMAX_IN);
+    else snprintf(tag, sizeof(tag), "%s", slot == AMAX_TRK ? "trk" : "test");
+    ProfScope ps(ctx, "absmax", 0.0, 4.0 * (double)rows * cols, tag);
     if (launch_absmax(ctx->stream, x, rows, cols, ld, 1, 0, s)) { dt_fail(ctx, DT_ERR_DEVICE, "absmax launch failed"); return nullptr; }
     for (const auto &t : ctx->amax_tag)      // (a slot names ONE tensor)
         if (t.slot == slot) { amax_forget(ctx, t.lo, t.hi - t.lo); break; }
@@ -239,6 +243,7 @@ static const struct { const char *name; int Policy::*field; } k_knobs[] = {
     {"DT_S3", &Policy::s3}, {"DT_S3_CONV1", &Policy::s3_conv1}, {"DT_S3_MINROWS", &Policy::s3_minrows}, {"DT_S3_H2", &Policy::s3_h2},
     {"DT_H2_MINFRAMES", &Policy::h2_minframes}, {"DT_S3_HALF", &Policy::s3_half}, {"DT_S3_REC_MINROWS", &Policy::s3_rec_minrows},
     {"DT_S3_1X1", &Policy::s3_1x1}, {"DT_S3_1X1_MINK", &Policy::s3_1x1_mink}, {"DT_S3_1X1_MINROWS", &Policy::s3_1x1_minrows},
+    {"DT_AMAX_MEASURE", &Policy::amax_measure},
 };
 
 static void policy_from_env(Policy &p)
@@ -279,7 +284,23 @@ static void policy_refresh(dt_ctx *ctx)
 }
 
 // ---------------------------------------------------------------------------
-extern "C" int dt_abi_version(void) { return 107; }   // 1.07: + dt_gemm_split (test entry point of wino_gemm_s3.hip: bf16 x 3 or fp16 x 2 terms), dt_policy_set
+extern "C" int dt_abi_version(void) { return 108; }   // 1.08: + dt_amax_read (1.07: + dt_gemm_split, dt_policy_set)
+
+// the host's view of a max-|x| slot: the maximum over its sub-words, as dt_amax_read (dt_internal.h) takes it on the device
+extern "C" int dt_amax_read(dt_ctx *ctx, int slot, float *h_out)
+{
+    if (!ctx || !h_out) return dt_fail(ctx, DT_ERR_ARG, "null argument");
+    if (slot < 0 || slot >= DT_AMAX_SLOTS) return dt_fail(ctx, DT_ERR_ARG, "max-|x| slot %d out of range [0, %d)", slot, DT_AMAX_SLOTS);
+    if (!ctx->amax) return dt_fail(ctx, DT_ERR_STATE, "max-|x| slots not allocated");
+    if (ctx->capturing) return dt_fail(ctx, DT_ERR_STATE, "dt_amax_read during graph capture");
+    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+    unsigned w[DT_AMAX_WORDS];
+    HIP_TRY(ctx, hipMemcpy(w, amax_slot(ctx, slot), sizeof(w), hipMemcpyDeviceToHost));
+    unsigned v = 0;
+    for (int q = 0; q < DT_AMAX_SUB; ++q) v = w[q * DT_AMAX_LINE] > v ? w[q * DT_AMAX_LINE] : v;
+    memcpy(h_out, &v, sizeof(v));
+    return DT_OK;
+}
 
 extern "C" int dt_create(dt_ctx **out)
 {

@@ -29,7 +29,7 @@ SYMBOLS = [
     "dt_track_row_width", "dt_track_detect", "dt_track_recurrent",
     "dt_packed_row_ints", "dt_pack_detections", "dt_unpack_detections",
     "dt_track_xproj_width", "dt_track_detect_xproj", "dt_track_recurrent_xproj",
-    "dt_gemm_split_bf16", "dt_gemm_split", "dt_policy_set",
+    "dt_gemm_split_bf16", "dt_gemm_split", "dt_policy_set", "dt_amax_read",
 ]
 
 _lib = None
@@ -96,6 +96,7 @@ def load_library():
     L.dt_profile_reset.argtypes = [vp]
     L.dt_policy_reload.argtypes = [vp]
     L.dt_policy_set.argtypes = [vp, ctypes.c_char_p, ci]
+    L.dt_amax_read.argtypes = [vp, ci, ctypes.POINTER(cf)]
     L.dt_profile_names.argtypes = [vp, ctypes.c_char_p, csz]
     L.dt_profile_read.argtypes = [vp, ctypes.c_char_p, ctypes.POINTER(ctypes.c_int64),
                                   ctypes.POINTER(ctypes.c_double), ctypes.POINTER(ctypes.c_double),
@@ -573,6 +574,13 @@ class Context(object):
         self._check(self.lib.dt_profile_read(self.h, name.encode(), ctypes.byref(n), ctypes.byref(ms),
                                              ctypes.byref(fl), ctypes.byref(by)), "dt_profile_read")
         return dict(launches=n.value, ms=ms.value, flops=fl.value, bytes=by.value)
+
+    def amax_read(self, slot):
+        """max |x| held in max-|x| slot `slot` (include/mi355_dt.h: dt_amax_read has the slot map), as a numpy float32"""
+        v = ctypes.c_float(0.0)
+        self._sync_stream()
+        self._check(self.lib.dt_amax_read(self.h, int(slot), ctypes.byref(v)), "dt_amax_read")
+        return np.float32(v.value)
 
 
 _default_ctx = None

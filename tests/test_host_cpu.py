@@ -12,7 +12,7 @@ import pytest
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
-def test_library_exports_every_declared_symbol():
+def test_library_exports_every_declared_symbol_abi_108():
     import mi355_dt
     hdr = open(os.path.join(ROOT, "include", "mi355_dt.h")).read()
     declared = sorted(set(re.findall(r"DT_API[^;(]*?\b(dt_[a-z0-9_]+)\s*\(", hdr)))
@@ -22,7 +22,7 @@ def test_library_exports_every_declared_symbol():
     lib = ctypes.CDLL(mi355_dt.LIB_PATH)
     for s in declared:
         assert hasattr(lib, s), "missing export " + s
-    assert lib.dt_abi_version() == 107
+    assert lib.dt_abi_version() == 108
 
 
 def test_no_cpu_fallback_without_gpu():
