@@ -10,6 +10,7 @@
 #include <mutex>
 #include <functional>
 #include <string>
+#include <type_traits>
 #include <vector>
 
 #include "../../include/mi355_dt.h"
@@ -362,21 +363,64 @@ struct DevBuf {
     size_t bytes = 0;
 };
 
+// Owner of one device allocation: hipFree in the destructor and in reset(); move-only.  It does NOT synchronise: whoever releases memory that
+// queued work may still read synchronises the stream first (network.hip: every loader does so once, before its first release).
+template <class T> class DevMem {
+    T *p = nullptr;
+
+public:
+    DevMem() = default;
+    DevMem(const DevMem &) = delete;
+    DevMem &operator=(const DevMem &) = delete;
+    DevMem(DevMem &&o) noexcept : p(o.p) { o.p = nullptr; }
+    DevMem &operator=(DevMem &&o) noexcept
+    {
+        if (this != &o) { reset(); p = o.p; o.p = nullptr; }
+        return *this;
+    }
+    ~DevMem() { reset(); }
+    void reset()
+    {
+        if (p) (void)hipFree(p);
+        p = nullptr;
+    }
+    hipError_t alloc(size_t n)   // n elements; what was held is released first
+    {
+        reset();
+        const hipError_t e = hipMalloc(reinterpret_cast<void **>(&p), n * sizeof(T));
+        if (e != hipSuccess) p = nullptr;
+        return e;
+    }
+    T *get() const { return p; }
+    explicit operator bool() const { return p != nullptr; }
+};
+static_assert(!std::is_copy_constructible<DevMem<float>>::value && !std::is_copy_assignable<DevMem<float>>::value, "a device allocation has one owner");
+
+// One Winograd-domain weight set in every device form it was built in (network.hip: upload_wino).  The 16-bit forms are the B operands of the split
+// GEMM (wino_gemm_s3.hip); they are built from `u` on the device and live and die with it.
+struct WinoWeights {
+    int ts = 0;                   // output tile size 2 / 4 / 6; 0 = not built
+    int cin = 0, npad = 0;
+    DevMem<float> u;              // [P][npad][cin], P = (ts + 2)^2
+    DevMem<unsigned short> s3;    // three bf16 terms [P][3][cin/16][npad][16], or empty
+    DevMem<unsigned short> h2;    // two fp16 terms of U[p] * 2^su[p], [P][2][cin/16][npad][16], or empty
+    DevMem<float> h2_pscale;      // with h2: the epilogue factors [P]
+};
+
 struct ConvLayer {
-    int idx, ks, cin, cout, npad, pool;  // pool: reference MaxPooling2D after this layer
-    float *wt = nullptr;                 // device, packed
-    unsigned short *wt_s3 = nullptr;     // device, 1x1 layers: wt as split-bf16 terms [3][cin/16][npad][16] (wino_gemm_s3.hip) or null
-    unsigned short *bias_s3 = nullptr;   // device, with wt_s3: the bias as the B rows of one extra K stage, [3][npad][16]
-    unsigned short *wt_h2 = nullptr;     // device, 1x1 layers: wt as two fp16 terms of the scaled weights [2][cin/16][npad][16] (wino_gemm_s3.hip's fp16 form) or null
-    float *pscale_h2 = nullptr;          // device, with wt_h2: [1] the epilogue factor 1 / (the weights' power of two)
-    unsigned short *w3_h2 = nullptr;     // device, narrow 3x3 layers (conv_2 / 3 / 5's shapes): wt as two fp16 terms [2][9 cin / 16][npad][16] for conv3_h2.hip, or null
-    float *pscale_w3 = nullptr;          // device, with w3_h2: [1]
-    float *wino = nullptr;               // device, [P][npad][cin] Winograd-domain weights (wide 3x3 layers) or null
-    int wino_ts = 0;                     // their output tile size (2, 4 or 6)
-    float *wino_alt = nullptr;           // device, F(4x4) weights kept next to F(6x6) ones for small-batch launches, or null
-    float *fused4s = nullptr;            // device, fused F(4x4,3x3) weights (wino4s_fused.hip: conv_2 / 3 / 5 / 6 / 8's shapes) or null
-    float *bias = nullptr;               // device, [npad]
-    float *scale = nullptr;              // device, [cout]: folded BatchNorm scale (dt_detector_extract un-folds with it) or null
+    int idx = 0, ks = 0, cin = 0, cout = 0, npad = 0;
+    DevMem<float> wt;                 // packed
+    DevMem<unsigned short> wt_s3;     // 1x1 layers: wt as split-bf16 terms [3][cin/16][npad][16] (wino_gemm_s3.hip) or empty
+    DevMem<unsigned short> bias_s3;   // with wt_s3: the bias as the B rows of one extra K stage, [3][npad][16]
+    DevMem<unsigned short> wt_h2;     // 1x1 layers: wt as two fp16 terms of the scaled weights [2][cin/16][npad][16] (wino_gemm_s3.hip's fp16 form) or empty
+    DevMem<float> pscale_h2;          // with wt_h2: [1] the epilogue factor 1 / (the weights' power of two)
+    DevMem<unsigned short> w3_h2;     // narrow 3x3 layers (conv_2 / 3 / 5's shapes): wt as two fp16 terms [2][9 cin / 16][npad][16] for conv3_h2.hip, or empty
+    DevMem<float> pscale_w3;          // with w3_h2: [1]
+    WinoWeights wino;                 // Winograd-domain weights (wide 3x3 layers) or not built
+    WinoWeights wino_alt;             // F(4x4) weights kept next to F(6x6) ones for small-batch launches, or not built
+    DevMem<float> fused4s;            // fused F(4x4,3x3) weights (wino4s_fused.hip: conv_2 / 3 / 5 / 6 / 8's shapes) or empty
+    DevMem<float> bias;               // [npad]
+    DevMem<float> scale;              // [cout]: folded BatchNorm scale (dt_detector_extract un-folds with it) or empty
     bool scale_has_zero = false;
 };
 
@@ -448,43 +492,38 @@ struct dt_ctx {
     // detector
     int image_h = 0, image_w = 0, nb_box = 0, nb_class = 0, cb = 0;
     float anchors[64];
-    float *anchors_dev = nullptr;
+    DevMem<float> anchors_dev;
     float dec_anchors_host[64];   // last anchors handed to dt_decode (persistent staging of the caller's host array)
     int dec_anchors_n = 0;
     bool det_loaded = false;
     ConvLayer layers[24];   // 1..23
-    unsigned short *s3_ones = nullptr;   // device, [256][16] FLOATS: the A rows (1, 0, .., 0) that carry a 1x1 layer's bias through wino_gemm_s3.hip
-    std::map<const void *, unsigned short *> wino_s3;   // F(6x6) Winograd weights (device pointer) -> their split-bf16 form (wino_gemm_s3.hip), when built
-    struct H2Weights { unsigned short *terms = nullptr; float *pscale = nullptr; };
-    std::map<const void *, H2Weights> wino_h2;          // ... -> their fp16 form: two terms of U[p] * 2^su[p], and the epilogue factors [P]
+    DevMem<float> s3_ones;   // [256][16]: the A rows (1, 0, .., 0) that carry a 1x1 layer's bias through wino_gemm_s3.hip
     // max-|x| slots of the fp16 form (DT_AMAX_SUB words each; dt_internal.h: dt_h2_base).  Slot 0 holds 1.0 (|h_t| < 1: the ConvLSTM recurrent step);
     // slot i in 1..23: the OUTPUT of conv_i, filled by the epilogue of the kernel that writes it (network.hip: amax_begin zeroes them per forward);
     // 32 + i: the INPUT of conv_i where no producer measured it (absmax_kernel); 56: the tracker's z / conv_feat; 57, 58: test entry points;
     // 64..127: scratch of the weight packs
-    unsigned *amax = nullptr;
+    DevMem<unsigned> amax;
     struct AmaxTag { const float *lo, *hi; int cols, slot; };   // the tensor that occupies [lo, hi), `cols` channels per pixel -> the slot that holds its max |x|
     bool h2_small = false;                   // the running call carries fewer than Policy::h2_minframes frames: no fp16 form, no max-|x| publication (call_begin)
     std::vector<AmaxTag> amax_tag;           // valid inside one API call only (call_begin), and until a layer writes into [lo, hi) (amax_forget)
-    float *conv1_w = nullptr, *conv1_b = nullptr, *lut255 = nullptr;
-    unsigned *conv1_w3 = nullptr, *conv1_w3u8 = nullptr;   // device: split-bf16 weight tables of conv1_s3_kernel: w and w / 255 (conv1.hip:conv1_split_tables)
+    DevMem<float> conv1_w, conv1_b, lut255;
+    DevMem<unsigned> conv1_w3, conv1_w3u8;   // split-bf16 weight tables of conv1_s3_kernel: w and w / 255 (conv1.hip:conv1_split_tables)
     std::vector<float> conv1_hwio32, conv1_scale, conv1_shift;   // host copy of conv_1 as a Cin = 32 layer (dt_detector_extract)
     // tracker head
     bool trk_loaded = false;
     int trk_units = 0, trk_cx = 0 /*padded z channels*/;
-    float *trk_wx = nullptr, *trk_bx = nullptr;   // input conv, N gate-interleaved
-    float *trk_wh = nullptr;                      // recurrent conv
-    float *trk_wx_wino = nullptr, *trk_wh_wino = nullptr;   // their Winograd-domain forms
-    float *trk_wxm_wino = nullptr;                // F(6x6) weights of the MERGED input projection (conv_23 folded in; 1024 input channels) or null
-    float *trk_bx16 = nullptr;                    // its bias: [17][4U] gate-interleaved -- row 0 the interior bias, rows 1 + k the correction of border case k
+    DevMem<float> trk_wx, trk_bx;                 // input conv, N gate-interleaved
+    DevMem<float> trk_wh;                         // recurrent conv
+    WinoWeights trk_wx_wino, trk_wh_wino;         // their Winograd-domain forms, or not built
+    WinoWeights trk_wxm_wino;                     // F(6x6) weights of the MERGED input projection (conv_23 folded in; 1024 input channels) or not built
+    DevMem<float> trk_bx16;                       // its bias: [17][4U] gate-interleaved -- row 0 the interior bias, rows 1 + k the correction of border case k
     std::vector<float> conv23_hwio, conv23_bias;  // host copies of conv_23 ([1024][cb], [cb]) and of the ConvLSTM input kernel / bias (Keras HWIO, x_bbox first):
     std::vector<float> trk_hkernel, trk_hbias;    // what the merge is computed from, whichever of the two loaders runs second
-    int trk_wino_ts = 0, trk_wh_ts = 0;   // tile of the input / recurrent convolution's Winograd weights
-    float *trk_wo = nullptr, *trk_bo = nullptr;   // tconv_2 1x1
-    int trk_wo_npad = 0;
+    ConvLayer trk_out;                            // tconv_2 1x1 (idx 102): wt and bias only, so that it stays on the fp32 MFMA kernel
     // tiny tracker
     bool tiny_loaded = false;
     int tiny_D = 0, tiny_Dpad = 0, tiny_U = 0, tiny_O = 0, tiny_Opad = 0;
-    float *tiny_wx = nullptr, *tiny_bx = nullptr, *tiny_ur = nullptr, *tiny_wd = nullptr, *tiny_bd = nullptr;
+    DevMem<float> tiny_wx, tiny_bx, tiny_ur, tiny_wd, tiny_bd;
     // workspaces (grown on demand)
     std::map<std::string, DevBuf> ws;
     int last_batch = 0;

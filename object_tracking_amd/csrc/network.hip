@@ -162,19 +162,10 @@ ProfScope::~ProfScope()
     ctx->pending.push_back(ev);
 }
 
-// forget (and free) the split-bf16 twin of a Winograd weight buffer that is about to be freed
-static void s3_drop(dt_ctx *ctx, const void *wino)
-{
-    auto it = ctx->wino_s3.find(wino);
-    if (wino && it != ctx->wino_s3.end()) { (void)hipFree(it->second); ctx->wino_s3.erase(it); }
-    auto ih = ctx->wino_h2.find(wino);
-    if (wino && ih != ctx->wino_h2.end()) { (void)hipFree(ih->second.terms); (void)hipFree(ih->second.pscale); ctx->wino_h2.erase(ih); }
-}
-
 // ---- max-|x| slots of the fp16 form (dt_internal.h: dt_ctx::amax) ------------------------------------------------------------------
 #define DT_AMAX_SLOTS 128
 enum { AMAX_ONE = 0, AMAX_IN = 32, AMAX_TRK = 56, AMAX_TEST = 57, AMAX_PACK = 64 };
-static unsigned *amax_slot(dt_ctx *ctx, int slot) { return ctx->amax ? ctx->amax + (size_t)slot * DT_AMAX_WORDS : nullptr; }
+static unsigned *amax_slot(dt_ctx *ctx, int slot) { return ctx->amax ? ctx->amax.get() + (size_t)slot * DT_AMAX_WORDS : nullptr; }
 // every API entry that runs layers starts here: what a previous call knew about a tensor's maximum says nothing about the bytes behind the pointer now,
 // and a call of fewer than Policy::h2_minframes frames takes no fp16 form (frames = 0: a layer-level test entry, never small)
 static void call_begin(dt_ctx *ctx, int frames)
@@ -206,6 +197,8 @@ static int amax_begin(dt_ctx *ctx)
 }
 // slot a layer's epilogue fills with the max |x| of what it writes: conv_1 .. conv_23 only (the test entry points run "layer 0")
 static int amax_out_slot(const ConvLayer &L) { return L.idx >= 1 && L.idx <= 23 ? L.idx : 0; }
+// slot a layer's input is measured into where no producer published it
+static int amax_in_slot(const ConvLayer &L) { return L.idx >= 1 && L.idx <= 23 ? AMAX_IN + L.idx : AMAX_TEST; }
 static const unsigned *ensure_amax(dt_ctx *ctx, const float *x, long long rows, int cols, long long ld, int slot)
 {
     if (!ctx->pol.amax_measure)      // (DT_AMAX_MEASURE: measure what a producer published too, so that the two words can be compared)
@@ -226,11 +219,13 @@ static const unsigned *ensure_amax(dt_ctx *ctx, const float *x, long long rows, 
 // does this launch take the fp16 form of the split GEMM?  (DT_PIN keeps the bf16 form: see Policy::s3_h2)
 static bool h2_wanted(const dt_ctx *ctx) { return ctx->pol.s3 != 0 && ctx->pol.s3_h2 != 0 && !ctx->pol.pin && !ctx->h2_small; }
 
-static int upload(dt_ctx *ctx, float **dst, const std::vector<float> &h)
+// host array -> a fresh device allocation; `dst` takes it (and releases what it held) only when the copy succeeded
+template <class T> static int upload(dt_ctx *ctx, DevMem<T> &dst, const std::vector<T> &h)
 {
-    if (*dst) { (void)hipFree(*dst); *dst = nullptr; }
-    HIP_TRY(ctx, hipMalloc(reinterpret_cast<void **>(dst), h.size() * sizeof(float)));
-    HIP_TRY(ctx, hipMemcpy(*dst, h.data(), h.size() * sizeof(float), hipMemcpyHostToDevice));
+    DevMem<T> d;
+    HIP_TRY(ctx, d.alloc(h.size()));
+    HIP_TRY(ctx, hipMemcpy(d.get(), h.data(), h.size() * sizeof(T), hipMemcpyHostToDevice));
+    dst = std::move(d);
     return DT_OK;
 }
 
@@ -323,7 +318,7 @@ extern "C" int dt_create(dt_ctx **out)
     policy_refresh(c);
     std::vector<float> lut(256);
     for (int i = 0; i < 256; ++i) lut[i] = (float)((double)i / 255.0);   // utils.py:150-153
-    if (upload(c, &c->lut255, lut) != DT_OK) {
+    if (upload(c, c->lut255, lut) != DT_OK) {
         snprintf(g_static_err, sizeof(g_static_err), "%s", c->err.c_str());
         delete c;
         return DT_ERR_DEVICE;
@@ -331,8 +326,7 @@ extern "C" int dt_create(dt_ctx **out)
     {   // max-|x| slots; slot 0 = 1.0
         std::vector<unsigned> am((size_t)DT_AMAX_SLOTS * DT_AMAX_WORDS, 0u);
         for (int q = 0; q < DT_AMAX_SUB; ++q) am[(size_t)q * DT_AMAX_LINE] = 0x3f800000u;
-        if (hipMalloc(reinterpret_cast<void **>(&c->amax), am.size() * sizeof(unsigned)) != hipSuccess ||
-            hipMemcpy(c->amax, am.data(), am.size() * sizeof(unsigned), hipMemcpyHostToDevice) != hipSuccess) {
+        if (upload(c, c->amax, am) != DT_OK) {
             snprintf(g_static_err, sizeof(g_static_err), "dt_create: max-|x| slot allocation failed");
             delete c;
             return DT_ERR_DEVICE;
@@ -348,41 +342,13 @@ extern "C" void dt_destroy(dt_ctx *ctx)
     (void)hipStreamSynchronize(ctx->stream);
     for (auto &kv : ctx->ws)
         if (kv.second.p) (void)hipFree(kv.second.p);
-    for (int i = 0; i <= 23; ++i) {
-        if (ctx->layers[i].wt) (void)hipFree(ctx->layers[i].wt);
-        if (ctx->layers[i].bias) (void)hipFree(ctx->layers[i].bias);
-        s3_drop(ctx, ctx->layers[i].wino);
-        if (ctx->layers[i].wt_s3) (void)hipFree(ctx->layers[i].wt_s3);
-        if (ctx->layers[i].bias_s3) (void)hipFree(ctx->layers[i].bias_s3);
-        if (ctx->layers[i].wt_h2) (void)hipFree(ctx->layers[i].wt_h2);
-        if (ctx->layers[i].pscale_h2) (void)hipFree(ctx->layers[i].pscale_h2);
-        if (ctx->layers[i].w3_h2) (void)hipFree(ctx->layers[i].w3_h2);
-        if (ctx->layers[i].pscale_w3) (void)hipFree(ctx->layers[i].pscale_w3);
-        if (ctx->layers[i].wino) (void)hipFree(ctx->layers[i].wino);
-        if (ctx->layers[i].wino_alt) (void)hipFree(ctx->layers[i].wino_alt);
-        if (ctx->layers[i].fused4s) (void)hipFree(ctx->layers[i].fused4s);
-        if (ctx->layers[i].scale) (void)hipFree(ctx->layers[i].scale);
-    }
-    if (ctx->trk_wxm_wino) { s3_drop(ctx, ctx->trk_wxm_wino); (void)hipFree(ctx->trk_wxm_wino); }
-    if (ctx->trk_bx16) (void)hipFree(ctx->trk_bx16);
-    float *singles[] = {ctx->conv1_w, ctx->conv1_b, ctx->lut255, ctx->anchors_dev, ctx->trk_wx, ctx->trk_bx,
-                        ctx->trk_wh,  ctx->trk_wo,  ctx->trk_bo, ctx->trk_wx_wino, ctx->trk_wh_wino, ctx->tiny_wx,     ctx->tiny_bx, ctx->tiny_ur,
-                        ctx->tiny_wd, ctx->tiny_bd};
-    s3_drop(ctx, ctx->trk_wx_wino);
-    s3_drop(ctx, ctx->trk_wh_wino);
-    if (ctx->s3_ones) (void)hipFree(ctx->s3_ones);
-    if (ctx->amax) (void)hipFree(ctx->amax);
-    if (ctx->conv1_w3) (void)hipFree(ctx->conv1_w3);
-    if (ctx->conv1_w3u8) (void)hipFree(ctx->conv1_w3u8);
-    for (float *p : singles)
-        if (p) (void)hipFree(p);
     for (auto &e : ctx->pending) { (void)hipEventDestroy(e.a); (void)hipEventDestroy(e.b); }
     if (ctx->gstream) {
         graphs_clear(ctx);
         (void)hipEventDestroy(ctx->gev_in); (void)hipEventDestroy(ctx->gev_out);
         (void)hipStreamDestroy(ctx->gstream);
     }
-    delete ctx;
+    delete ctx;      // every weight buffer goes with its owner (DevMem)
 }
 
 extern "C" const char *dt_last_error(dt_ctx *ctx) { return ctx ? ctx->err.c_str() : g_static_err; }
@@ -428,7 +394,7 @@ extern "C" int dt_detector_config(dt_ctx *ctx, int image_h, int image_w, int nb_
     std::vector<float> a(h_anchors, h_anchors + 2 * nb_box);
     memcpy(ctx->anchors, h_anchors, sizeof(float) * 2 * nb_box);
     ctx->det_loaded = false;
-    return upload(ctx, &ctx->anchors_dev, a);
+    return upload(ctx, ctx->anchors_dev, a);
 }
 
 // kernel in the darknet file is (O,I,H,W) (KerasYOLO.py:267-268 reshapes the
@@ -443,29 +409,85 @@ static void oihw_to_hwio(const float *src, int O, int I, int k, std::vector<floa
                     dst[(((size_t)y * k + x) * I + i) * O + o] = src[(((size_t)o * I + i) * k + y) * k + x];
 }
 
-static bool wino_wanted(const dt_ctx *ctx, int ks, int cin, int cout);
-static int wino_tile(const dt_ctx *ctx, bool recurrent);
-static int upload_wino(dt_ctx *ctx, float **dst, int ts, const float *hwio, int cin_src, int cout_src, const int *cin_map,
-                       int cin_dst, const int *n_map, int npad, const float *scale, bool want_s3);
+// Policy::wino: 1 (default) = layers with Cin >= 64 and Cout >= 128 (conv_3 and up: below that the batched
+//          GEMMs have K <= 32 and the transforms' traffic costs more than the MFMA work saved) when a
+//          launch has enough tiles (wino_runs);
+//          0 = never (direct MFMA form everywhere); 2 = every 3x3 layer the transforms support,
+//          at any size (parity tests of the path at small shapes).  Applied when weights are loaded.
+static bool wino_wanted(const dt_ctx *ctx, int ks, int cin, int cout)
+{
+    const Policy &p = ctx->pol;
+    if (ks != 3 || p.wino == 0 || cin % 32 || cout % 4) return false;
+    return p.wino == 2 || (cin >= 64 && cout >= 128);
+}
 
+// Output tile of the Winograd form: 6 = F(6x6,3x3) (default), 4 = F(4x4,3x3), 2 = F(2x2,3x3); Policy::wino_tile
+// forces one size for every layer.  Applied when weights are loaded.
+static int wino_tile(const dt_ctx *ctx, bool recurrent)
+{
+    // The ConvLSTM recurrent convolution keeps F(4x4): its per-step GEMM has only clips/4 * 49 rows, which F(6x6)
+    // (clips/9 * 49) fills no better, and the F(6x6) gate-update transform needs all 256 VGPRs (2.0 vs 5.3 TB/s).
+    const int t = ctx->pol.wino_tile ? ctx->pol.wino_tile : (recurrent ? 4 : 6);
+    return (t == 2 || t == 4) ? t : 6;
+}
+
+// One Winograd weight set: U in fp32 and, where the caller's GEMM can take the split kernel, its 16-bit forms (split on the device from the fp32
+// copy).  Built aside and moved into `dst` when every step succeeded: a failed upload leaves `dst` as it was.
+static int upload_wino(dt_ctx *ctx, WinoWeights &dst, int ts, const float *hwio, int cin_src, int cout_src, const int *cin_map,
+                       int cin_dst, const int *n_map, int npad, const float *scale, bool want_s3)
+{
+    const int P = (ts + 2) * (ts + 2);
+    std::vector<float> u((size_t)P * npad * cin_dst);
+    wino_pack_weights(ts, hwio, cin_src, cout_src, cin_map, cin_dst, n_map, npad, scale, u.data());
+    WinoWeights w;
+    w.ts = ts; w.cin = cin_dst; w.npad = npad;
+    const int rc = upload(ctx, w.u, u);
+    if (rc) return rc;
+    // the split-bf16 form of wino_gemm_s3.hip -- only where run_wino can use it: F(6x6) weights of a plain layer, F(4x4) weights of the
+    // ConvLSTM recurrent convolution (the caller says which)
+    if (want_s3 && ctx->pol.s3 != 0 && cin_dst % 32 == 0 && npad % 128 == 0) {
+        HIP_TRY(ctx, w.s3.alloc(u.size() * 3));
+        if (launch_wino_s3_pack(ctx->stream, w.u.get(), P, npad, cin_dst, w.s3.get()) || hipStreamSynchronize(ctx->stream) != hipSuccess)
+            return dt_fail(ctx, DT_ERR_DEVICE, "split-bf16 weight pack failed");
+        if (ctx->pol.s3_h2 != 0 && P <= 64) {      // ... and the fp16 form next to it (DT_PIN runs take the bf16 one)
+            HIP_TRY(ctx, w.h2.alloc(u.size() * 2));
+            HIP_TRY(ctx, w.h2_pscale.alloc(P));
+            if (launch_wino_h2_pack(ctx->stream, w.u.get(), P, npad, cin_dst, ts, amax_slot(ctx, AMAX_PACK), w.h2.get(), w.h2_pscale.get()) ||
+                hipStreamSynchronize(ctx->stream) != hipSuccess)
+                return dt_fail(ctx, DT_ERR_DEVICE, "fp16-form weight pack failed");
+        }
+    }
+    dst = std::move(w);
+    return DT_OK;
+}
+
+static void gate_interleave_map(int U, std::vector<int> &n_map)
+{
+    // packed column n' = (j/32)*128 + g*32 + j%32  <-  Keras column g*U + j
+    n_map.resize((size_t)4 * U);
+    for (int np = 0; np < 4 * U; ++np) {
+        const int jb = np / 128, g = (np % 128) / 32, jj = np % 32;
+        n_map[np] = g * U + jb * 32 + jj;
+    }
+}
+
+// Every device form of one layer's weights, built into a fresh ConvLayer that replaces ctx->layers[idx] when all of it succeeded.
 static int load_conv_layer(dt_ctx *ctx, int idx, int ks, int cin, int cout, const float *hwio, const float *scale,
                            const float *bias_src)
 {
-    ConvLayer &L = ctx->layers[idx];
+    ConvLayer L;
     L.idx = idx; L.ks = ks; L.cin = cin; L.cout = cout;
     L.npad = round_up(cout, 256);   // weight rows padded to the widest column tile (256)
     std::vector<float> packed((size_t)L.npad * ks * ks * cin);
     pack_conv_weights(hwio, ks, cin, cout, nullptr, cin, nullptr, L.npad, scale, packed.data());
     std::vector<float> bias(L.npad, 0.0f);
     for (int c = 0; c < cout; ++c) bias[c] = bias_src[c];
-    int rc = upload(ctx, &L.wt, packed);
+    int rc = upload(ctx, L.wt, packed);
     if (rc) return rc;
-    if (L.wt_s3) { (void)hipStreamSynchronize(ctx->stream); (void)hipFree(L.wt_s3); L.wt_s3 = nullptr; }
-    if (L.bias_s3) { (void)hipStreamSynchronize(ctx->stream); (void)hipFree(L.bias_s3); L.bias_s3 = nullptr; }
     if (ks == 1 && ctx->pol.s3 != 0 && ctx->pol.s3_1x1 != 0 && cin % 32 == 0 && L.npad % 128 == 0 && cout >= 64) {
         // a 1x1 layer's weights are a plain [npad][cin] matrix: also as the split-bf16 B operand of wino_gemm_s3.hip
-        HIP_TRY(ctx, hipMalloc(reinterpret_cast<void **>(&L.wt_s3), packed.size() * 3 * sizeof(unsigned short)));
-        if (launch_wino_s3_pack(ctx->stream, L.wt, 1, L.npad, cin, L.wt_s3)) return dt_fail(ctx, DT_ERR_DEVICE, "split-bf16 weight pack launch failed");
+        HIP_TRY(ctx, L.wt_s3.alloc(packed.size() * 3));
+        if (launch_wino_s3_pack(ctx->stream, L.wt.get(), 1, L.npad, cin, L.wt_s3.get())) return dt_fail(ctx, DT_ERR_DEVICE, "split-bf16 weight pack launch failed");
         HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
         // the bias as one extra K stage (wino_gemm_s3.hip): B rows (bias[n], 0, .., 0), A rows (1, 0, .., 0)
         std::vector<unsigned short> bs((size_t)3 * L.npad * 16, 0);
@@ -474,65 +496,57 @@ static int load_conv_layer(dt_ctx *ctx, int idx, int ks, int cin, int cout, cons
             wino_s3_split_host(bias_src[n], t);
             for (int t3 = 0; t3 < 3; ++t3) bs[((size_t)t3 * L.npad + n) * 16] = t[t3];
         }
-        HIP_TRY(ctx, hipMalloc(reinterpret_cast<void **>(&L.bias_s3), bs.size() * sizeof(unsigned short)));
-        HIP_TRY(ctx, hipMemcpy(L.bias_s3, bs.data(), bs.size() * sizeof(unsigned short), hipMemcpyHostToDevice));
+        if ((rc = upload(ctx, L.bias_s3, bs))) return rc;
         if (!ctx->s3_ones) {
             std::vector<float> ones((size_t)256 * 16, 0.0f);      // the bias stage's A rows, fp32 like the layer's activation: (1, 0, .., 0)
             for (int r = 0; r < 256; ++r) ones[(size_t)r * 16] = 1.0f;
-            HIP_TRY(ctx, hipMalloc(reinterpret_cast<void **>(&ctx->s3_ones), ones.size() * sizeof(float)));
-            HIP_TRY(ctx, hipMemcpy(ctx->s3_ones, ones.data(), ones.size() * sizeof(float), hipMemcpyHostToDevice));
+            if ((rc = upload(ctx, ctx->s3_ones, ones))) return rc;
         }
     }
-    if (L.wt_h2) { (void)hipStreamSynchronize(ctx->stream); (void)hipFree(L.wt_h2); L.wt_h2 = nullptr; }
-    if (L.pscale_h2) { (void)hipStreamSynchronize(ctx->stream); (void)hipFree(L.pscale_h2); L.pscale_h2 = nullptr; }
     if (L.wt_s3 && ctx->pol.s3_h2 != 0) {
         // ... and in the fp16 form: two terms of wt * 2^s (s from max |wt|), the epilogue factor 2^-s; the bias stays fp32 (L.bias)
-        HIP_TRY(ctx, hipMalloc(reinterpret_cast<void **>(&L.wt_h2), packed.size() * 2 * sizeof(unsigned short)));
-        HIP_TRY(ctx, hipMalloc(reinterpret_cast<void **>(&L.pscale_h2), sizeof(float)));
-        if (launch_wino_h2_pack(ctx->stream, L.wt, 1, L.npad, cin, 0, amax_slot(ctx, AMAX_PACK), L.wt_h2, L.pscale_h2))
+        HIP_TRY(ctx, L.wt_h2.alloc(packed.size() * 2));
+        HIP_TRY(ctx, L.pscale_h2.alloc(1));
+        if (launch_wino_h2_pack(ctx->stream, L.wt.get(), 1, L.npad, cin, 0, amax_slot(ctx, AMAX_PACK), L.wt_h2.get(), L.pscale_h2.get()))
             return dt_fail(ctx, DT_ERR_DEVICE, "fp16-form weight pack launch failed");
         HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
     }
-    if (L.w3_h2) { (void)hipStreamSynchronize(ctx->stream); (void)hipFree(L.w3_h2); L.w3_h2 = nullptr; }
-    if (L.pscale_w3) { (void)hipStreamSynchronize(ctx->stream); (void)hipFree(L.pscale_w3); L.pscale_w3 = nullptr; }
     if (ks == 3 && (cin == 32 || cin == 64) && cout % 64 == 0 && cout <= 128 && ctx->pol.s3 != 0 && ctx->pol.s3_h2 != 0 && ctx->pol.c3h2 != 0) {
         // conv_2 / conv_3 / conv_5's shapes: the packed direct-form weights as two fp16 terms for conv3_h2.hip (the same k order)
-        HIP_TRY(ctx, hipMalloc(reinterpret_cast<void **>(&L.w3_h2), packed.size() * 2 * sizeof(unsigned short)));
-        HIP_TRY(ctx, hipMalloc(reinterpret_cast<void **>(&L.pscale_w3), sizeof(float)));
-        if (launch_wino_h2_pack(ctx->stream, L.wt, 1, L.npad, 9 * cin, 0, amax_slot(ctx, AMAX_PACK), L.w3_h2, L.pscale_w3))
+        HIP_TRY(ctx, L.w3_h2.alloc(packed.size() * 2));
+        HIP_TRY(ctx, L.pscale_w3.alloc(1));
+        if (launch_wino_h2_pack(ctx->stream, L.wt.get(), 1, L.npad, 9 * cin, 0, amax_slot(ctx, AMAX_PACK), L.w3_h2.get(), L.pscale_w3.get()))
             return dt_fail(ctx, DT_ERR_DEVICE, "fp16-form weight pack launch failed");
         HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
     }
-    if (L.scale) { (void)hipStreamSynchronize(ctx->stream); (void)hipFree(L.scale); L.scale = nullptr; }
-    L.scale_has_zero = false;
     if (scale) {
         std::vector<float> sc(scale, scale + cout);
         for (float v : sc) L.scale_has_zero |= (v == 0.0f);
-        if ((rc = upload(ctx, &L.scale, sc))) return rc;
+        if ((rc = upload(ctx, L.scale, sc))) return rc;
     }
-    if (L.wino) { (void)hipStreamSynchronize(ctx->stream); s3_drop(ctx, L.wino); (void)hipFree(L.wino); L.wino = nullptr; }
-    if (L.wino_alt) { (void)hipStreamSynchronize(ctx->stream); (void)hipFree(L.wino_alt); L.wino_alt = nullptr; }
-    if (L.fused4s) { (void)hipStreamSynchronize(ctx->stream); (void)hipFree(L.fused4s); L.fused4s = nullptr; }
     const bool f4_shape = ((cin == 64 || cin == 128) && cout % 128 == 0 && cout <= 256) || (cin == 32 && cout == 64);
     if (ks == 3 && f4_shape && ctx->pol.wino != 0 && ctx->pol.fused4 != 0) {
         // conv_2 / conv_3 / conv_5 / conv_6 / conv_8's shapes: the fused F(4x4,3x3) kernel (wino4s_fused.hip)
         std::vector<float> u36((size_t)36 * L.npad * cin), uf((size_t)36 * cin * cout);
         wino_pack_weights(4, hwio, cin, cout, nullptr, cin, nullptr, L.npad, scale, u36.data());
         wino4s_fused_pack(u36.data(), L.npad, cin, cout, uf.data());
-        if ((rc = upload(ctx, &L.fused4s, uf))) return rc;
+        if ((rc = upload(ctx, L.fused4s, uf))) return rc;
     }
     if (wino_wanted(ctx, ks, cin, cout)) {
-        L.wino_ts = wino_tile(ctx, false);
-        rc = upload_wino(ctx, &L.wino, L.wino_ts, hwio, cin, cout, nullptr, cin, nullptr, L.npad, scale, L.wino_ts == 6);
+        const int ts = wino_tile(ctx, false);
+        rc = upload_wino(ctx, L.wino, ts, hwio, cin, cout, nullptr, cin, nullptr, L.npad, scale, ts == 6);
         if (rc) return rc;
         // small batches of the 13x13 / 26x26 layers: F(4x4) needs 36 GEMMs of ONE (partly filled) row tile where F(6x6)
         // needs 64 -- keep both weight sets and choose per launch (run_conv); only with the default tile policy
-        if (L.wino_ts == 6 && ctx->pol.wino_tile == 0 && cin >= 256) {
-            rc = upload_wino(ctx, &L.wino_alt, 4, hwio, cin, cout, nullptr, cin, nullptr, L.npad, scale, false);
+        if (ts == 6 && ctx->pol.wino_tile == 0 && cin >= 256) {
+            rc = upload_wino(ctx, L.wino_alt, 4, hwio, cin, cout, nullptr, cin, nullptr, L.npad, scale, false);
             if (rc) return rc;
         }
     }
-    return upload(ctx, &L.bias, bias);
+    if ((rc = upload(ctx, L.bias, bias))) return rc;
+    (void)hipStreamSynchronize(ctx->stream);      // the layer this one replaces may still be read by queued work
+    ctx->layers[idx] = std::move(L);
+    return DT_OK;
 }
 
 // The ConvLSTM2D input projection with conv_23 folded in (Policy::trk_merge).  z = [x_bbox | conv_feat] with x_bbox = W23 feat + b23 inside
@@ -541,14 +555,15 @@ static int load_conv_layer(dt_ctx *ctx, int idx, int ks, int cin, int cout, cons
 // -- one 3x3 convolution of conv_feat alone (K = 1024 instead of 1109 -> 1120) with a bias that depends on which of its nine taps lie
 // inside the image (16 border cases).  Merged in float64 on the host whenever both weight sets are present; used by the Winograd path
 // of the projection (convlstm_sequence), the two-step form stays for the small-batch direct path and for DT_TRK_MERGE=0.
-static void gate_interleave_map(int U, std::vector<int> &n_map);
 static int build_merged_xproj(dt_ctx *ctx)
 {
-    if (ctx->trk_wxm_wino) { (void)hipStreamSynchronize(ctx->stream); s3_drop(ctx, ctx->trk_wxm_wino); (void)hipFree(ctx->trk_wxm_wino); ctx->trk_wxm_wino = nullptr; }
-    if (ctx->trk_bx16) { (void)hipStreamSynchronize(ctx->stream); (void)hipFree(ctx->trk_bx16); ctx->trk_bx16 = nullptr; }
+    (void)hipStreamSynchronize(ctx->stream);      // queued work may still read the set this one replaces
+    ctx->trk_wxm_wino = WinoWeights();
+    ctx->trk_bx16.reset();
     const int Cb = ctx->cb, U = ctx->trk_units, N4 = 4 * U, Csrc = Cb + 1024;
     if (!ctx->pol.trk_merge || !U || ctx->conv23_hwio.size() != (size_t)1024 * Cb || ctx->trk_hkernel.size() != (size_t)9 * Csrc * N4) return DT_OK;
-    if (!wino_wanted(ctx, 3, 1024, N4) || wino_tile(ctx, false) != 6 || ctx->trk_wino_ts != 6) return DT_OK;
+    // (F(6x6) only, and not next to an unmerged set that was built with another tile: one tile for both forms of the projection)
+    if (!wino_wanted(ctx, 3, 1024, N4) || wino_tile(ctx, false) != 6 || (ctx->trk_wx_wino.u && ctx->trk_wx_wino.ts != 6)) return DT_OK;
     const float *wk = ctx->trk_hkernel.data(), *w23 = ctx->conv23_hwio.data();
     std::vector<float> merged((size_t)9 * 1024 * N4);
     {   // 9 x 1024 independent rows of Cb x 4U float64 multiply-adds (1.6 G at C = 12): over the host's threads
@@ -598,9 +613,9 @@ static int build_merged_xproj(dt_ctx *ctx)
             if (k == 0) b16[np] = (float)all;
             b16[(size_t)(1 + k) * N4 + np] = (float)(-out);
         }
-    int rc = upload_wino(ctx, &ctx->trk_wxm_wino, 6, merged.data(), 1024, N4, nullptr, 1024, n_map.data(), N4, nullptr, true);
+    int rc = upload_wino(ctx, ctx->trk_wxm_wino, 6, merged.data(), 1024, N4, nullptr, 1024, n_map.data(), N4, nullptr, true);
     if (rc) return rc;
-    return upload(ctx, &ctx->trk_bx16, b16);
+    return upload(ctx, ctx->trk_bx16, b16);
 }
 
 extern "C" int dt_load_darknet_weights(dt_ctx *ctx, const float *h_blob, size_t n_floats, size_t *consumed)
@@ -634,20 +649,15 @@ extern "C" int dt_load_darknet_weights(dt_ctx *ctx, const float *h_blob, size_t 
             std::vector<float> w(27 * 32);
             for (int t = 0; t < 27; ++t)
                 for (int c = 0; c < 32; ++c) w[t * 32 + c] = hwio[(size_t)t * 32 + c] * scale[c];
-            int rc = upload(ctx, &ctx->conv1_w, w);
-            if (rc) return rc;
-            rc = upload(ctx, &ctx->conv1_b, shift);
-            if (rc) return rc;
-            {   // the same weights as three bf16 terms, plain (float32 frames) and with normalize()'s 1/255 folded in (uint8 frames): conv1_s3_kernel
-                std::vector<unsigned> w3(C1_W3_WORDS, 0u), w3u8(C1_W3_WORDS, 0u);   // 1536 table words + 4 zero words (the kernel's source of padding pixels)
-                conv1_split_tables(w.data(), false, w3.data());
-                conv1_split_tables(w.data(), true, w3u8.data());
-                for (auto pr : {std::make_pair(&ctx->conv1_w3, &w3), std::make_pair(&ctx->conv1_w3u8, &w3u8)}) {
-                    if (*pr.first) { (void)hipStreamSynchronize(ctx->stream); (void)hipFree(*pr.first); *pr.first = nullptr; }
-                    HIP_TRY(ctx, hipMalloc(reinterpret_cast<void **>(pr.first), pr.second->size() * sizeof(unsigned)));
-                    HIP_TRY(ctx, hipMemcpy(*pr.first, pr.second->data(), pr.second->size() * sizeof(unsigned), hipMemcpyHostToDevice));
-                }
-            }
+            // the same weights as three bf16 terms, plain (float32 frames) and with normalize()'s 1/255 folded in (uint8 frames): conv1_s3_kernel
+            std::vector<unsigned> w3(C1_W3_WORDS, 0u), w3u8(C1_W3_WORDS, 0u);   // 1536 table words + 4 zero words (the kernel's source of padding pixels)
+            conv1_split_tables(w.data(), false, w3.data());
+            conv1_split_tables(w.data(), true, w3u8.data());
+            (void)hipStreamSynchronize(ctx->stream);      // queued work may still read the tables these replace
+            int rc;
+            if ((rc = upload(ctx, ctx->conv1_w, w)) || (rc = upload(ctx, ctx->conv1_b, shift)) || (rc = upload(ctx, ctx->conv1_w3, w3)) ||
+                (rc = upload(ctx, ctx->conv1_w3u8, w3u8)))
+                return rc;
             ctx->conv1_hwio32.assign((size_t)9 * 32 * 32, 0.0f);   // [3][3][32 (3 used)][32]
             for (int t = 0; t < 9; ++t)
                 for (int ci = 0; ci < 3; ++ci)
@@ -700,31 +710,10 @@ static const int S3_MINK = 128;
 // blocks of 16 x 16 pixels from which a narrow 3x3 layer (conv_2 / 3 / 5) takes the direct fp16-form kernel (conv3_h2.hip) instead of the fused fp32 one:
 static const long long C3H2_MIN_BLOCKS = 1024;
 
-// Policy::wino: 1 (default) = layers with Cin >= 64 and Cout >= 128 (conv_3 and up: below that the batched
-//          GEMMs have K <= 32 and the transforms' traffic costs more than the MFMA work saved) when a
-//          launch has enough tiles (wino_runs);
-//          0 = never (direct MFMA form everywhere); 2 = every 3x3 layer the transforms support,
-//          at any size (parity tests of the path at small shapes).  Applied when weights are loaded.
-static bool wino_wanted(const dt_ctx *ctx, int ks, int cin, int cout)
+static bool wino_runs(const dt_ctx *ctx, const WinoWeights &wts, int B, int H, int W, int N)
 {
-    const Policy &p = ctx->pol;
-    if (ks != 3 || p.wino == 0 || cin % 32 || cout % 4) return false;
-    return p.wino == 2 || (cin >= 64 && cout >= 128);
-}
-
-// Output tile of the Winograd form: 6 = F(6x6,3x3) (default), 4 = F(4x4,3x3), 2 = F(2x2,3x3); Policy::wino_tile
-// forces one size for every layer.  Applied when weights are loaded.
-static int wino_tile(const dt_ctx *ctx, bool recurrent)
-{
-    // The ConvLSTM recurrent convolution keeps F(4x4): its per-step GEMM has only clips/4 * 49 rows, which F(6x6)
-    // (clips/9 * 49) fills no better, and the F(6x6) gate-update transform needs all 256 VGPRs (2.0 vs 5.3 TB/s).
-    const int t = ctx->pol.wino_tile ? ctx->pol.wino_tile : (recurrent ? 4 : 6);
-    return (t == 2 || t == 4) ? t : 6;
-}
-
-static bool wino_runs(const dt_ctx *ctx, const float *wino_wt, int ts, int B, int H, int W, int cin, int N)
-{
-    if (!wino_wt) return false;
+    if (!wts.u) return false;
+    const int ts = wts.ts, cin = wts.cin;
     const long long mt = (long long)B * ((H + ts - 1) / ts) * ((W + ts - 1) / ts);
     if (mt >= (1ll << 31) / 64) return false;
     // V and M' workspaces are (ts+2)^2 * tiles * (Cin + N) floats (27 GB for conv_3 at 1440 frames); a launch
@@ -737,39 +726,6 @@ static bool wino_runs(const dt_ctx *ctx, const float *wino_wt, int ts, int B, in
     // (F(4x4) -- the ConvLSTM recurrent step -- from 16 tiles = ONE clip at 13x13 since round 6: with the step's GEMM on the split kernel a 30-frame clip takes 4.7 instead
     //  of 12.3 ms, two clips 6.5 instead of 14.3, three 7.7 instead of 15.7 (profiles/r06_experiments.txt section 10); on the fp32 kernel too the Winograd form wins there)
     return ctx->pol.wino == 2 || mt >= (mint > 0 ? mint : (ts == 2 ? 256 : (ts == 4 ? 16 : 32)));
-}
-
-static int upload_wino(dt_ctx *ctx, float **dst, int ts, const float *hwio, int cin_src, int cout_src, const int *cin_map,
-                       int cin_dst, const int *n_map, int npad, const float *scale, bool want_s3)
-{
-    std::vector<float> u((size_t)(ts + 2) * (ts + 2) * npad * cin_dst);
-    wino_pack_weights(ts, hwio, cin_src, cout_src, cin_map, cin_dst, n_map, npad, scale, u.data());
-    s3_drop(ctx, *dst);
-    int rc = upload(ctx, dst, u);
-    if (rc) return rc;
-    // also in the split-bf16 form of wino_gemm_s3.hip (the split runs on the device, from the fp32 copy) -- only where run_wino
-    // can use it: F(6x6) weights of a plain layer, F(4x4) weights of the ConvLSTM recurrent convolution (the caller says which)
-    if (want_s3 && ctx->pol.s3 != 0 && cin_dst % 32 == 0 && npad % 128 == 0) {
-        unsigned short *s3 = nullptr;
-        HIP_TRY(ctx, hipMalloc(reinterpret_cast<void **>(&s3), u.size() * 3 * sizeof(unsigned short)));
-        if (launch_wino_s3_pack(ctx->stream, *dst, (ts + 2) * (ts + 2), npad, cin_dst, s3) || hipStreamSynchronize(ctx->stream) != hipSuccess) {
-            (void)hipFree(s3);
-            return dt_fail(ctx, DT_ERR_DEVICE, "split-bf16 weight pack failed");
-        }
-        ctx->wino_s3[*dst] = s3;
-        if (ctx->pol.s3_h2 != 0 && (ts + 2) * (ts + 2) <= 64) {      // ... and the fp16 form next to it (DT_PIN runs take the bf16 one)
-            dt_ctx::H2Weights h;
-            const int P = (ts + 2) * (ts + 2);
-            HIP_TRY(ctx, hipMalloc(reinterpret_cast<void **>(&h.terms), u.size() * 2 * sizeof(unsigned short)));
-            if (hipMalloc(reinterpret_cast<void **>(&h.pscale), P * sizeof(float)) != hipSuccess) { (void)hipFree(h.terms); return dt_fail(ctx, DT_ERR_DEVICE, "hipMalloc failed"); }
-            if (launch_wino_h2_pack(ctx->stream, *dst, P, npad, cin_dst, ts, amax_slot(ctx, AMAX_PACK), h.terms, h.pscale) || hipStreamSynchronize(ctx->stream) != hipSuccess) {
-                (void)hipFree(h.terms); (void)hipFree(h.pscale);
-                return dt_fail(ctx, DT_ERR_DEVICE, "fp16-form weight pack failed");
-            }
-            ctx->wino_h2[*dst] = h;
-        }
-    }
-    return DT_OK;
 }
 
 // Tile configuration of the P batched GEMMs [Mt x Cin] x [Cin x N] (persistent launch, conv_igemm.hip).
@@ -857,10 +813,11 @@ static WinoGeom wino_geometry(const dt_ctx *ctx, int ts, int B, int H, int W, bo
     return q;
 }
 
-static int run_wino(dt_ctx *ctx, const float *wino_wt, int ts, const float *bias, int cin, int N, int npad, int B, int H,
+static int run_wino(dt_ctx *ctx, const WinoWeights &wts, const float *bias, int N, int B, int H,
                     int W, const WinoIO &io, float slope, const char *tag, int cin_alg = 0 /* channels of the reference's layer when cin is padded */,
                     int in_slot = AMAX_TEST /* max-|x| slot of the input tensor (fp16 form); AMAX_ONE: bounded by 1, nothing to measure */)
 {
+    const int ts = wts.ts, cin = wts.cin, npad = wts.npad;
     const double cin_df = cin_alg > 0 ? cin_alg : cin;
     if (io.out) amax_forget(ctx, io.out, (long long)B * H * W * io.out_ld);
     if (io.out2) amax_forget(ctx, io.out2, (long long)B * H * W / 4 * io.out2_ld);
@@ -882,19 +839,14 @@ static int run_wino(dt_ctx *ctx, const float *wino_wt, int ts, const float *bias
     const unsigned short *u_s3 = nullptr;
     const bool rec = ts == 4 && io.cstate;      // the recurrent step: F(4x4), gate update in the output transform
     // (row thresholds: the fp16 form wins from far fewer rows than the bf16 form)
-    const bool h2_avail = h2_wanted(ctx) && ctx->wino_h2.find(wino_wt) != ctx->wino_h2.end();
+    const bool h2_avail = h2_wanted(ctx) && wts.h2;
     const int minrows = h2_avail ? ctx->pol.s3_minrows_h2 : ctx->pol.s3_minrows, rec_minrows = h2_avail ? ctx->pol.s3_rec_minrows_h2 : ctx->pol.s3_rec_minrows;
     if (((ts == 6 && !io.cstate) || rec) && ctx->pol.s3 != 0 && cin % 32 == 0 && N % 128 == 0 && npad % 128 == 0 && wino_gemm_s3_usable(w.Mt, cin, N) &&
-        (ctx->pol.s3 == 2 || (cin >= S3_MINK && (rec ? (rec_minrows > 0 && w.Mt >= rec_minrows) : w.Mt >= minrows)))) {
-        auto it = ctx->wino_s3.find(wino_wt);
-        if (it != ctx->wino_s3.end()) u_s3 = it->second;
-    }
+        (ctx->pol.s3 == 2 || (cin >= S3_MINK && (rec ? (rec_minrows > 0 && w.Mt >= rec_minrows) : w.Mt >= minrows))))
+        u_s3 = wts.s3.get();
     // ... in the fp16 form (two terms of scaled operands, three products) where its weights exist
-    const dt_ctx::H2Weights *h2 = nullptr;
-    if (u_s3 && h2_wanted(ctx)) {
-        auto ih = ctx->wino_h2.find(wino_wt);
-        if (ih != ctx->wino_h2.end()) { h2 = &ih->second; u_s3 = h2->terms; }
-    }
+    const bool h2 = u_s3 && h2_avail;
+    if (h2) u_s3 = wts.h2.get();
     const int NT = h2 ? 2 : 3;
     const size_t mp = (mt + 255) / 256 * 256;
     float *V = ws_get(ctx, "wino_v", u_s3 ? (size_t)P * NT * mp * cin * sizeof(unsigned short) : P * mt * cin * sizeof(float));
@@ -922,7 +874,7 @@ static int run_wino(dt_ctx *ctx, const float *wino_wt, int ts, const float *bias
         memset(&g, 0, sizeof(g));
         g.a = w.v_s3; g.b = u_s3; g.c = Mp; g.c_ps = (long long)mt * N; g.P = P; g.Mt = w.Mt; g.Mp = (int)mp; g.N = N; g.Np = npad;
         g.K = cin; g.ldc = N; g.half = ctx->pol.s3_half;
-        if (h2) { g.nt = 2; g.pscale = h2->pscale; g.amax = amax; }
+        if (h2) { g.nt = 2; g.pscale = wts.h2_pscale.get(); g.amax = amax; }
         // flops = EXECUTED 16-bit MFMA work (six partial products per multiply, three in the fp16 form); bytes = V + U (NT 16-bit terms each) + M'
         ProfScope ps(ctx, "conv_gemm_s3", wino_gemm_s3_flops(g), (double)P * (2.0 * NT * mt * cin + 2.0 * NT * (double)cin * N + 4.0 * (double)mt * N), tag);
         if (ctx->prof && !ctx->capturing) ctx->prof_tab[h2 ? "s3_form:f16x2" : "s3_form:bf16x3"].launches += 1;
@@ -936,7 +888,7 @@ static int run_wino(dt_ctx *ctx, const float *wino_wt, int ts, const float *bias
         ConvArgs a;
         memset(&a, 0, sizeof(a));
         a.in = V; a.in_ld = cin; a.in_bs = (long long)mt * cin;
-        a.wt = wino_wt; a.bias = nullptr;
+        a.wt = wts.u.get(); a.bias = nullptr;
         a.out = Mp; a.out_ld = N; a.out_bs = (long long)mt * N;
         a.B = 1; a.H = 1; a.W = w.Mt; a.Cin = cin; a.N = N; a.M = w.Mt; a.K = cin;
         a.npad = npad; a.slope = 1.0f;
@@ -1014,12 +966,12 @@ static int run_conv(dt_ctx *ctx, const ConvLayer &L, const float *in, int in_ld,
         const bool h2 = L.wt_h2 && L.pscale_h2 && L.npad <= 2048 && h2_wanted(ctx);
         GemmS3Args g;
         memset(&g, 0, sizeof(g));
-        g.a_f32 = in; g.a_ld = in_ld; g.b = L.wt_s3; g.c = out; g.c_ps = 0; g.P = 1; g.Mt = (int)M; g.Mp = (int)((M + 255) / 256 * 256); g.N = L.cout; g.Np = L.npad;
+        g.a_f32 = in; g.a_ld = in_ld; g.b = L.wt_s3.get(); g.c = out; g.c_ps = 0; g.P = 1; g.Mt = (int)M; g.Mp = (int)((M + 255) / 256 * 256); g.N = L.cout; g.Np = L.npad;
         g.half = ctx->pol.s3_half;
-        g.K = L.cin; g.ldc = out_ld; g.ones = ctx->s3_ones; g.bias_s3 = L.bias_s3; g.act = 1; g.slope = slope;
+        g.K = L.cin; g.ldc = out_ld; g.ones = reinterpret_cast<const unsigned short *>(ctx->s3_ones.get()); g.bias_s3 = L.bias_s3.get(); g.act = 1; g.slope = slope;
         if (h2) {      // the fp16 form: scaled operands (the activation's power of two from its max |x|), the bias added in the epilogue
-            g.nt = 2; g.b = L.wt_h2; g.pscale = L.pscale_h2; g.bias = L.bias; g.ones = nullptr; g.bias_s3 = nullptr;
-            g.amax = ensure_amax(ctx, in, M, L.cin, in_ld, L.idx >= 1 && L.idx <= 23 ? AMAX_IN + L.idx : AMAX_TEST);
+            g.nt = 2; g.b = L.wt_h2.get(); g.pscale = L.pscale_h2.get(); g.bias = L.bias.get(); g.ones = nullptr; g.bias_s3 = nullptr;
+            g.amax = ensure_amax(ctx, in, M, L.cin, in_ld, amax_in_slot(L));
             if (!g.amax) return DT_ERR_DEVICE;
         }
         char tag[32];
@@ -1037,7 +989,7 @@ static int run_conv(dt_ctx *ctx, const ConvLayer &L, const float *in, int in_ld,
     ConvArgs a;
     memset(&a, 0, sizeof(a));
     a.in = in; a.in_ld = in_ld; a.in_bs = (long long)H * W * in_ld;
-    a.wt = L.wt; a.bias = L.bias;
+    a.wt = L.wt.get(); a.bias = L.bias.get();
     a.out = out; a.out_ld = out_ld; a.out_bs = (long long)H * W * out_ld;
     a.out2 = out2; a.out2_ld = out2_ld;
     a.B = B; a.H = H; a.W = W; a.Cin = L.cin; a.N = L.cout; a.M = B * H * W; a.K = L.ks * L.ks * L.cin;
@@ -1057,12 +1009,12 @@ static int run_conv(dt_ctx *ctx, const ConvLayer &L, const float *in, int in_ld,
             Conv3H2Args c;
             memset(&c, 0, sizeof(c));
             c.in = in; c.in_bs = a.in_bs; c.in_ld = in_ld; c.B = B; c.H = H; c.W = W; c.Cin = L.cin; c.N = L.cout; c.Np = L.npad;
-            c.w = L.w3_h2; c.pscale = L.pscale_w3; c.bias = L.bias; c.slope = slope;
+            c.w = L.w3_h2.get(); c.pscale = L.pscale_w3.get(); c.bias = L.bias.get(); c.slope = slope;
             if (epi == EPI_POOL) { c.out2 = out; c.out2_ld = out_ld; }
             else { c.out = out; c.out_ld = out_ld; c.out_bs = a.out_bs; }
             c.zeros = ws_get(ctx, "zeros256", 256, /*zero_on_grow=*/true);
             if (!c.zeros) return DT_ERR_DEVICE;
-            c.amax = ensure_amax(ctx, in, (long long)B * H * W, L.cin, in_ld, L.idx >= 1 && L.idx <= 23 ? AMAX_IN + L.idx : AMAX_TEST);
+            c.amax = ensure_amax(ctx, in, (long long)B * H * W, L.cin, in_ld, amax_in_slot(L));
             if (!c.amax) return DT_ERR_DEVICE;
             if (amax_out_slot(L)) c.amax_out = amax_slot(ctx, amax_out_slot(L));
             // executed fp16 MFMA FLOPs (three products per multiply, whole tiles); bytes: the input once per channel tile (+ halo 27 / 41 %) and the output
@@ -1083,7 +1035,7 @@ static int run_conv(dt_ctx *ctx, const ConvLayer &L, const float *in, int in_ld,
             Wino4FusedArgs f;
             memset(&f, 0, sizeof(f));
             f.in = in; f.in_bs = a.in_bs; f.in_ld = in_ld; f.B = B; f.H = H; f.W = W; f.Cin = L.cin; f.N = L.cout;
-            f.u = L.fused4s; f.bias = L.bias; f.slope = slope;
+            f.u = L.fused4s.get(); f.bias = L.bias.get(); f.slope = slope;
             if (epi == EPI_POOL) { f.out2 = out; f.out2_ld = out_ld; }
             else { f.out = out; f.out_ld = out_ld; f.out_bs = a.out_bs; }
             // executed MFMA FLOPs: 36 positions x (whole 4x4 tiles) x Cin x N x 2; bytes: input once per 128 output channels (+ halo 27 %) and the output
@@ -1100,7 +1052,7 @@ static int run_conv(dt_ctx *ctx, const ConvLayer &L, const float *in, int in_ld,
             return DT_OK;
         }
     }
-    if (wino_runs(ctx, L.wino, L.wino_ts, B, H, W, L.cin, L.cout) && ((epi == EPI_PLAIN && order == ORD_LINEAR) || epi == EPI_POOL || epi == EPI_POOL_BOTH)) {
+    if (wino_runs(ctx, L.wino, B, H, W, L.cout) && ((epi == EPI_PLAIN && order == ORD_LINEAR) || epi == EPI_POOL || epi == EPI_POOL_BOTH)) {
         WinoIO io;
         memset(&io, 0, sizeof(io));
         io.in = in; io.in_ld = in_ld; io.in_bs = a.in_bs;
@@ -1109,19 +1061,18 @@ static int run_conv(dt_ctx *ctx, const ConvLayer &L, const float *in, int in_ld,
         io.amax_out_slot = amax_out_slot(L);
         // F(6x6) or F(4x4) for this launch: with many tiles F(6x6)'s fewer multiplies win; with a few frames the choice
         // is about how the positions x row tiles x column tiles spread over the CUs (small_gemm_cost)
-        const float *wt = L.wino;
-        int ts = L.wino_ts;
-        if (L.wino_alt && !ctx->pol.pin) {
+        const WinoWeights *wts = &L.wino;
+        if (L.wino_alt.u && !ctx->pol.pin) {
             const bool pooled = io.out2 != nullptr;
             const WinoGeom q6 = wino_geometry(ctx, 6, B, H, W, pooled), q4 = wino_geometry(ctx, 4, B, H, W, pooled);
             const long long t6 = 64ll * ((q6.Mt + 127) / 128) * ((L.cout + 127) / 128);
             // (the cost model prices the fp32 MFMA kernel's tiles: where the F(6x6) launch takes the split GEMM in the fp16 form -- run_wino's own test -- F(4x4) on the
             //  fp32 kernel is no alternative: at 20 frames it cost the 13x13 layers 0.10-0.24 ms each against 0.05-0.11 on the split kernel)
-            const bool s3_h2_takes_it = ctx->pol.s3 != 0 && h2_wanted(ctx) && ctx->wino_h2.find(L.wino) != ctx->wino_h2.end() && L.cin % 32 == 0 && L.cout % 128 == 0 &&
+            const bool s3_h2_takes_it = ctx->pol.s3 != 0 && h2_wanted(ctx) && L.wino.h2 && L.cin % 32 == 0 && L.cout % 128 == 0 &&
                                         L.npad % 128 == 0 && (ctx->pol.s3 == 2 || (L.cin >= S3_MINK && q6.Mt >= ctx->pol.s3_minrows_h2));
-            if (!s3_h2_takes_it && t6 <= 4096 && small_gemm_cost(q4.Mt, L.cout, 36, nullptr) < small_gemm_cost(q6.Mt, L.cout, 64, nullptr)) { wt = L.wino_alt; ts = 4; }
+            if (!s3_h2_takes_it && t6 <= 4096 && small_gemm_cost(q4.Mt, L.cout, 36, nullptr) < small_gemm_cost(q6.Mt, L.cout, 64, nullptr)) wts = &L.wino_alt;
         }
-        return run_wino(ctx, wt, ts, L.bias, L.cin, L.cout, L.npad, B, H, W, io, slope, tag, 0, L.idx >= 1 && L.idx <= 23 ? AMAX_IN + L.idx : AMAX_TEST);
+        return run_wino(ctx, *wts, L.bias.get(), L.cout, B, H, W, io, slope, tag, 0, amax_in_slot(L));
     }
     // Wave quantisation for small batches (few frames at 13x13 / 26x26): with 512 resident
     // workgroup slots (256 CUs x 2) a layer of a few hundred output tiles leaves the chip
@@ -1158,7 +1109,7 @@ static int run_conv(dt_ctx *ctx, const ConvLayer &L, const float *in, int in_ld,
             if (rc) return dt_fail(ctx, rc == 2 ? DT_ERR_ARG : DT_ERR_DEVICE, "conv_%d split-K launch failed (rc=%d)", L.idx, rc);
         }
         ProfScope ps2(ctx, "splitk_reduce", 0.0, 4.0 * (ksplit + 1.0) * a.M * (double)L.cout, tag);
-        if (launch_splitk_reduce(ctx->stream, slab, ksplit, a.M, L.cout, L.bias, slope, out, out_ld))
+        if (launch_splitk_reduce(ctx->stream, slab, ksplit, a.M, L.cout, L.bias.get(), slope, out, out_ld))
             return dt_fail(ctx, DT_ERR_DEVICE, "conv_%d split-K reduce launch failed", L.idx);
         return DT_OK;
     }
@@ -1195,7 +1146,7 @@ static int extract_layer(dt_ctx *ctx, const ConvLayer &L, const float *in, int i
         return dt_fail(ctx, DT_ERR_ARG, "conv_%d: a BatchNorm gamma of 0 was folded into the kernel; the raw Conv2D output cannot be recovered", L.idx);
     int rc = run_conv(ctx, L, in, in_ld, B, h, w, ex.out, L.cout, ORD_LINEAR, EPI_PLAIN, ex.kind == EX_ACT ? LEAKY : 1.0f);
     if (rc) return rc;
-    if (ex.kind == EX_CONV && L.scale && launch_unfold_bn(ctx->stream, ex.out, (long long)B * h * w, L.cout, L.scale, L.bias))
+    if (ex.kind == EX_CONV && L.scale && launch_unfold_bn(ctx->stream, ex.out, (long long)B * h * w, L.cout, L.scale.get(), L.bias.get()))
         return dt_fail(ctx, DT_ERR_DEVICE, "BatchNorm un-fold launch failed");
     ex.done = true;
     return DT_OK;
@@ -1216,8 +1167,8 @@ static int run_conv34_fused(dt_ctx *ctx, const ConvLayer &L3, const ConvLayer &L
     Conv3H2Args c;
     memset(&c, 0, sizeof(c));
     c.in = in; c.in_bs = (long long)H * W * in_ld; c.in_ld = in_ld; c.B = B; c.H = H; c.W = W; c.Cin = L3.cin; c.N = L3.cout; c.Np = L3.npad;
-    c.w = L3.w3_h2; c.pscale = L3.pscale_w3; c.bias = L3.bias; c.slope = slope;
-    c.w1 = L4.wt_h2; c.pscale1 = L4.pscale_h2; c.bias1 = L4.bias; c.N1 = L4.cout; c.Np1 = L4.npad; c.slope1 = slope;
+    c.w = L3.w3_h2.get(); c.pscale = L3.pscale_w3.get(); c.bias = L3.bias.get(); c.slope = slope;
+    c.w1 = L4.wt_h2.get(); c.pscale1 = L4.pscale_h2.get(); c.bias1 = L4.bias.get(); c.N1 = L4.cout; c.Np1 = L4.npad; c.slope1 = slope;
     c.out = out; c.out_ld = out_ld; c.out_bs = (long long)H * W * out_ld;
     c.zeros = ws_get(ctx, "zeros256", 256, /*zero_on_grow=*/true);
     if (!c.zeros) return DT_ERR_DEVICE;
@@ -1336,9 +1287,9 @@ static int detect_internal(dt_ctx *ctx, const void *frames, int dtype, int B, De
         // (its epilogue takes max |x| of what it writes: conv_2's direct fp16-form kernel scales its input by it)
         // (conv_1 publishes only where conv_2 will read it: the direct fp16-form kernel)
         const bool c2_direct = ctx->pol.c3h2 == 2 || (ctx->pol.c3h2 != 0 && (long long)B * ((H / 2 + 15) / 16) * ((W / 2 + 15) / 16) >= C3H2_MIN_BLOCKS);
-        unsigned *am1 = c1s3 && h2_wanted(ctx) && c2_direct && conv1_direct_fills_amax(frames, dtype, W, ctx->conv1_w3, ctx->conv1_w3u8) ? amax_slot(ctx, 1) : nullptr;
-        if (launch_conv1_direct(ctx->stream, frames, dtype, B, H, W, ctx->conv1_w, ctx->conv1_b, ctx->lut255, LEAKY,
-                                bufA, c1s3 ? ctx->conv1_w3 : nullptr, c1s3 ? ctx->conv1_w3u8 : nullptr, am1))
+        unsigned *am1 = c1s3 && h2_wanted(ctx) && c2_direct && conv1_direct_fills_amax(frames, dtype, W, ctx->conv1_w3.get(), ctx->conv1_w3u8.get()) ? amax_slot(ctx, 1) : nullptr;
+        if (launch_conv1_direct(ctx->stream, frames, dtype, B, H, W, ctx->conv1_w.get(), ctx->conv1_b.get(), ctx->lut255.get(), LEAKY,
+                                bufA, c1s3 ? ctx->conv1_w3.get() : nullptr, c1s3 ? ctx->conv1_w3u8.get() : nullptr, am1))
             return dt_fail(ctx, DT_ERR_DEVICE, "conv_1 launch failed");
         if (am1) amax_note(ctx, bufA, (long long)B * (H / 2) * (W / 2) * 32, 32, 1);
     }
@@ -1449,7 +1400,7 @@ extern "C" int dt_detector_extract(dt_ctx *ctx, const void *d_frames, int frames
     if (idx == 1 && kind <= EX_ACT) {   // conv_1 un-pooled: as a Cin = 32 layer of the MFMA kernel on zero-padded channels
         float *x32 = ws_get(ctx, "extract_x32", (size_t)B * H * W * 32 * sizeof(float));
         if (!x32) return DT_ERR_DEVICE;
-        if (launch_expand_rgb32(ctx->stream, d_frames, frames_dtype, (long long)B * H * W, ctx->lut255, x32))
+        if (launch_expand_rgb32(ctx->stream, d_frames, frames_dtype, (long long)B * H * W, ctx->lut255.get(), x32))
             return dt_fail(ctx, DT_ERR_DEVICE, "channel expansion launch failed");
         int rc = load_conv_layer(ctx, 0, 3, 32, 32, ctx->conv1_hwio32.data(), ctx->conv1_scale.data(), ctx->conv1_shift.data());
         if (rc) return rc;
@@ -1467,8 +1418,8 @@ extern "C" int dt_detector_extract(dt_ctx *ctx, const void *d_frames, int frames
         ctx->tap_feat = ctx->tap_netout = false;
         const bool c1s3 = ctx->pol.s3 != 0 && ctx->pol.s3_conv1 != 0;
         if (int rcz = amax_begin(ctx)) return rcz;
-        if (launch_conv1_direct(ctx->stream, d_frames, frames_dtype, B, H, W, ctx->conv1_w, ctx->conv1_b, ctx->lut255, LEAKY, bufA,
-                                c1s3 ? ctx->conv1_w3 : nullptr, c1s3 ? ctx->conv1_w3u8 : nullptr))
+        if (launch_conv1_direct(ctx->stream, d_frames, frames_dtype, B, H, W, ctx->conv1_w.get(), ctx->conv1_b.get(), ctx->lut255.get(), LEAKY, bufA,
+                                c1s3 ? ctx->conv1_w3.get() : nullptr, c1s3 ? ctx->conv1_w3u8.get() : nullptr))
             return dt_fail(ctx, DT_ERR_DEVICE, "conv_1 launch failed");
         if (idx == 1) {   // max_pooling2d_1
             HIP_TRY(ctx, hipMemcpyAsync(d_out, bufA, need * sizeof(float), hipMemcpyDeviceToDevice, ctx->stream));
@@ -1594,16 +1545,6 @@ extern "C" int dt_associate(dt_ctx *ctx, const float *d_boxes, const int *d_coun
 // ---------------------------------------------------------------------------
 // tracker head (ConvLSTM2D + 1x1)
 // ---------------------------------------------------------------------------
-static void gate_interleave_map(int U, std::vector<int> &n_map)
-{
-    // packed column n' = (j/32)*128 + g*32 + j%32  <-  Keras column g*U + j
-    n_map.resize((size_t)4 * U);
-    for (int np = 0; np < 4 * U; ++np) {
-        const int jb = np / 128, g = (np % 128) / 32, jj = np % 32;
-        n_map[np] = g * U + jb * 32 + jj;
-    }
-}
-
 extern "C" int dt_tracker_load(dt_ctx *ctx, int units, const float *h_kernel, const float *h_recurrent,
                                const float *h_bias, const float *h_out_kernel, const float *h_out_bias)
 {
@@ -1625,25 +1566,25 @@ extern "C" int dt_tracker_load(dt_ctx *ctx, int units, const float *h_kernel, co
     std::vector<float> wo((size_t)npad * U), bo(npad, 0.0f);
     pack_conv_weights(h_out_kernel, 1, U, Cb, nullptr, U, nullptr, npad, nullptr, wo.data());
     for (int c = 0; c < Cb; ++c) bo[c] = h_out_bias[c];
+    (void)hipStreamSynchronize(ctx->stream);      // queued work may still read the weights these replace
+    ConvLayer &Lo = ctx->trk_out;      // tconv_2: wt and bias only -- without the 16-bit forms load_conv_layer builds, it stays on the fp32 MFMA kernel
     int rc;
-    if ((rc = upload(ctx, &ctx->trk_wx, wx))) return rc;
-    if ((rc = upload(ctx, &ctx->trk_wh, wh))) return rc;
-    if ((rc = upload(ctx, &ctx->trk_bx, bx))) return rc;
-    if ((rc = upload(ctx, &ctx->trk_wo, wo))) return rc;
-    if ((rc = upload(ctx, &ctx->trk_bo, bo))) return rc;
-    for (float **w : {&ctx->trk_wx_wino, &ctx->trk_wh_wino})
-        if (*w) { (void)hipStreamSynchronize(ctx->stream); s3_drop(ctx, *w); (void)hipFree(*w); *w = nullptr; }
-    ctx->trk_wino_ts = wino_tile(ctx, false);
-    ctx->trk_wh_ts = wino_tile(ctx, true);
+    if ((rc = upload(ctx, ctx->trk_wx, wx))) return rc;
+    if ((rc = upload(ctx, ctx->trk_wh, wh))) return rc;
+    if ((rc = upload(ctx, ctx->trk_bx, bx))) return rc;
+    if ((rc = upload(ctx, Lo.wt, wo))) return rc;
+    if ((rc = upload(ctx, Lo.bias, bo))) return rc;
+    ctx->trk_wx_wino = WinoWeights();
+    ctx->trk_wh_wino = WinoWeights();
+    const int ts_x = wino_tile(ctx, false), ts_h = wino_tile(ctx, true);
     if (wino_wanted(ctx, 3, Cx, 4 * U) &&
-        (rc = upload_wino(ctx, &ctx->trk_wx_wino, ctx->trk_wino_ts, h_kernel, Csrc, 4 * U, cin_map.data(), Cx, n_map.data(),
-                          4 * U, nullptr, ctx->trk_wino_ts == 6)))
+        (rc = upload_wino(ctx, ctx->trk_wx_wino, ts_x, h_kernel, Csrc, 4 * U, cin_map.data(), Cx, n_map.data(), 4 * U, nullptr, ts_x == 6)))
         return rc;
     if (wino_wanted(ctx, 3, U, 4 * U) &&
-        (rc = upload_wino(ctx, &ctx->trk_wh_wino, ctx->trk_wh_ts, h_recurrent, U, 4 * U, nullptr, U, n_map.data(), 4 * U,
-                          nullptr, ctx->trk_wh_ts == 4)))
+        (rc = upload_wino(ctx, ctx->trk_wh_wino, ts_h, h_recurrent, U, 4 * U, nullptr, U, n_map.data(), 4 * U, nullptr, ts_h == 4)))
         return rc;
-    ctx->trk_units = U; ctx->trk_cx = Cx; ctx->trk_wo_npad = npad;
+    ctx->trk_units = U; ctx->trk_cx = Cx;
+    Lo.idx = 102; Lo.ks = 1; Lo.cin = U; Lo.cout = Cb; Lo.npad = npad;
     ctx->trk_hkernel.assign(h_kernel, h_kernel + (size_t)9 * Csrc * 4 * U);
     ctx->trk_hbias.assign(h_bias, h_bias + (size_t)4 * U);
     graphs_clear(ctx);
@@ -1655,8 +1596,7 @@ extern "C" int dt_tracker_load(dt_ctx *ctx, int units, const float *h_kernel, co
 // may skip conv_23 when the caller does not ask for the detector's grid.
 static bool xproj_merged(const dt_ctx *ctx, int F, int gh, int gw)
 {
-    return ctx->pol.trk_merge && ctx->trk_wxm_wino && ctx->trk_bx16 && ctx->trk_wino_ts == 6 &&
-           wino_runs(ctx, ctx->trk_wxm_wino, 6, F, gh, gw, 1024, 4 * ctx->trk_units);
+    return ctx->pol.trk_merge && ctx->trk_bx16 && wino_runs(ctx, ctx->trk_wxm_wino, F, gh, gw, 4 * ctx->trk_units);      // (a merged set is F(6x6) always)
 }
 
 // xproj = conv3x3(z, Wx) + b for all frames; then the sequential recurrence.
@@ -1666,7 +1606,7 @@ static bool xproj_merged(const dt_ctx *ctx, int F, int gh, int gw)
 //   z == null, xproj_ext != null : the recurrence ONLY, on the caller's stitched projection rows (dt_track_recurrent_xproj)
 static int convlstm_sequence(dt_ctx *ctx, const float *z, int Cx, int n_clips, int T, int gh, int gw, int U,
                              const float *wx, const float *bx, const float *wh, float *hseq /*[n_clips][T][GG][U]*/,
-                             const float *wx_wino = nullptr, const float *wh_wino = nullptr, float *xproj_ext = nullptr)
+                             const WinoWeights &wx_wino, const WinoWeights &wh_wino, float *xproj_ext = nullptr)
 {
     const int GG = gh * gw, F = n_clips * T, N4 = 4 * U;
     float *xproj = xproj_ext ? xproj_ext : ws_get(ctx, "trk_xproj", (size_t)F * GG * N4 * sizeof(float));
@@ -1683,23 +1623,23 @@ static int convlstm_sequence(dt_ctx *ctx, const float *z, int Cx, int n_clips, i
     }
     const std::string shape = std::to_string(n_clips) + "x" + std::to_string(T);
     auto input_projection = [&]() -> int {
-    if (z_owned && xproj_merged(ctx, F, gh, gw) && wx_wino == ctx->trk_wx_wino) {
+    if (z_owned && xproj_merged(ctx, F, gh, gw) && &wx_wino == &ctx->trk_wx_wino) {
         // conv_23 folded into the projection (build_merged_xproj): the 1024 conv_feat channels of z only, border-aware bias -- for the library's OWN z
         // rows only (dt_track_forward, dt_track_detect_xproj): a caller's rows (dt_track_recurrent) may carry any x_bbox and get the two-step form
         WinoIO io;
         memset(&io, 0, sizeof(io));
         io.in = z; io.in_ld = Cx; io.in_bs = (long long)GG * Cx;
         io.out = xproj; io.out_ld = N4; io.out_bs = (long long)GG * N4;
-        io.bias16 = ctx->trk_bx16 + N4;         // corrections of the 16 border cases; row 0 of the table is the interior bias
+        io.bias16 = ctx->trk_bx16.get() + N4;         // corrections of the 16 border cases; row 0 of the table is the interior bias
         if (ctx->prof && !ctx->capturing) ctx->prof_tab["convlstm_xproj:merged_conv23"].launches += 1;
-        const int rc = run_wino(ctx, ctx->trk_wxm_wino, 6, ctx->trk_bx16, 1024, N4, N4, F, gh, gw, io, 1.0f, "convlstm_xproj", ctx->cb + 1024, AMAX_TRK);
+        const int rc = run_wino(ctx, ctx->trk_wxm_wino, ctx->trk_bx16.get(), N4, F, gh, gw, io, 1.0f, "convlstm_xproj", ctx->cb + 1024, AMAX_TRK);
         if (rc) return rc;
-    } else if (wino_runs(ctx, wx_wino, ctx->trk_wino_ts, F, gh, gw, Cx, N4)) {
+    } else if (wino_runs(ctx, wx_wino, F, gh, gw, N4)) {
         WinoIO io;
         memset(&io, 0, sizeof(io));
         io.in = z; io.in_ld = Cx; io.in_bs = (long long)GG * Cx;
         io.out = xproj; io.out_ld = N4; io.out_bs = (long long)GG * N4;
-        const int rc = run_wino(ctx, wx_wino, ctx->trk_wino_ts, bx, Cx, N4, N4, F, gh, gw, io, 1.0f, "convlstm_xproj", ctx->cb + 1024, AMAX_TRK);
+        const int rc = run_wino(ctx, wx_wino, bx, N4, F, gh, gw, io, 1.0f, "convlstm_xproj", ctx->cb + 1024, AMAX_TRK);
         if (rc) return rc;
     } else {
         ConvArgs a;
@@ -1726,7 +1666,7 @@ static int convlstm_sequence(dt_ctx *ctx, const float *z, int Cx, int n_clips, i
             return dt_fail(ctx, DT_ERR_DEVICE, "ConvLSTM t=0 launch failed");
     }
     for (int t = 1; t < T; ++t) {
-        if (wino_runs(ctx, wh_wino, ctx->trk_wh_ts, n_clips, gh, gw, U, N4)) {
+        if (wino_runs(ctx, wh_wino, n_clips, gh, gw, N4)) {
             WinoIO io;
             memset(&io, 0, sizeof(io));
             io.in = hseq + (long long)(t - 1) * GG * U; io.in_ld = U; io.in_bs = h_bs;
@@ -1734,7 +1674,7 @@ static int convlstm_sequence(dt_ctx *ctx, const float *z, int Cx, int n_clips, i
             io.xproj = xproj + (long long)t * GG * N4; io.xp_ld = N4; io.xp_bs = xp_bs;
             io.cstate = cst; io.c_ld = U; io.c_bs = c_bs;
             // (h_{t-1} = o * tanh(c) lies in (-1, 1): the fp16 form's scale is static, nothing is measured)
-            const int rc = run_wino(ctx, wh_wino, ctx->trk_wh_ts, nullptr, U, N4, N4, n_clips, gh, gw, io, 1.0f, "convlstm_step", 0, AMAX_ONE);
+            const int rc = run_wino(ctx, wh_wino, nullptr, N4, n_clips, gh, gw, io, 1.0f, "convlstm_step", 0, AMAX_ONE);
             if (rc) return rc;
             continue;
         }
@@ -1776,7 +1716,7 @@ static int track_recurrent_internal(dt_ctx *ctx, const float *z, int n_clips, in
     const int F = n_clips * T, U = ctx->trk_units, Cx = ctx->trk_cx, Cb = ctx->cb;
     float *hseq = ws_get(ctx, "trk_h", (size_t)F * GG * U * sizeof(float));
     if (!hseq) return DT_ERR_DEVICE;
-    int rc = convlstm_sequence(ctx, z, Cx, n_clips, T, gh, gw, U, ctx->trk_wx, ctx->trk_bx, ctx->trk_wh, hseq, ctx->trk_wx_wino,
+    int rc = convlstm_sequence(ctx, z, Cx, n_clips, T, gh, gw, U, ctx->trk_wx.get(), ctx->trk_bx.get(), ctx->trk_wh.get(), hseq, ctx->trk_wx_wino,
                                ctx->trk_wh_wino);
     if (rc) return rc;
     float *trk = d_trk;
@@ -1785,9 +1725,7 @@ static int track_recurrent_internal(dt_ctx *ctx, const float *z, int n_clips, in
         if (!trk) return DT_ERR_DEVICE;
     }
     // TimeDistributed(Conv2D(Cb,(1,1)))  'tconv_2'  (MultiObjDetTracker.py:182)
-    ConvLayer L;
-    L.idx = 102; L.ks = 1; L.cin = U; L.cout = Cb; L.npad = ctx->trk_wo_npad; L.wt = ctx->trk_wo; L.bias = ctx->trk_bo;
-    return run_conv(ctx, L, hseq, U, F, gh, gw, trk, Cb, ORD_LINEAR, EPI_PLAIN, 1.0f);
+    return run_conv(ctx, ctx->trk_out, hseq, U, F, gh, gw, trk, Cb, ORD_LINEAR, EPI_PLAIN, 1.0f);
 }
 
 extern "C" int dt_track_forward(dt_ctx *ctx, const void *d_frames, int frames_dtype, int n_clips, int T,
@@ -1870,7 +1808,7 @@ extern "C" int dt_track_detect_xproj(dt_ctx *ctx, const void *d_frames, int fram
     if (!z) return DT_ERR_DEVICE;
     int rc = detect_internal(ctx, d_frames, frames_dtype, n_frames, Dest{z, Cx}, Dest{z + 1024, Cx}, /*skip23=*/!d_det && xproj_merged(ctx, n_frames, gh, gw));
     if (rc) return rc;
-    rc = convlstm_sequence(ctx, z, Cx, n_frames, 1, gh, gw, ctx->trk_units, ctx->trk_wx, ctx->trk_bx, ctx->trk_wh, nullptr,
+    rc = convlstm_sequence(ctx, z, Cx, n_frames, 1, gh, gw, ctx->trk_units, ctx->trk_wx.get(), ctx->trk_bx.get(), ctx->trk_wh.get(), nullptr,
                            ctx->trk_wx_wino, ctx->trk_wh_wino, d_xp);
     if (rc) return rc;
     if (d_det && launch_copy_cols(ctx->stream, z + 1024, Cx, d_det, Cb, (long long)n_frames * GG, Cb))
@@ -1888,7 +1826,7 @@ extern "C" int dt_track_recurrent_xproj(dt_ctx *ctx, const float *d_xp, int n_cl
     const int F = n_clips * T, U = ctx->trk_units, Cb = ctx->cb;
     float *hseq = ws_get(ctx, "trk_h", (size_t)F * GG * U * sizeof(float));
     if (!hseq) return DT_ERR_DEVICE;
-    int rc = convlstm_sequence(ctx, nullptr, ctx->trk_cx, n_clips, T, gh, gw, U, ctx->trk_wx, ctx->trk_bx, ctx->trk_wh, hseq,
+    int rc = convlstm_sequence(ctx, nullptr, ctx->trk_cx, n_clips, T, gh, gw, U, ctx->trk_wx.get(), ctx->trk_bx.get(), ctx->trk_wh.get(), hseq,
                                ctx->trk_wx_wino, ctx->trk_wh_wino, const_cast<float *>(d_xp));
     if (rc) return rc;
     float *trk = d_trk;
@@ -1896,9 +1834,8 @@ extern "C" int dt_track_recurrent_xproj(dt_ctx *ctx, const float *d_xp, int n_cl
         trk = ws_get(ctx, "trk_out", (size_t)F * GG * Cb * sizeof(float));
         if (!trk) return DT_ERR_DEVICE;
     }
-    ConvLayer L;       // TimeDistributed(Conv2D(Cb,(1,1)))  'tconv_2'  (MultiObjDetTracker.py:182)
-    L.idx = 102; L.ks = 1; L.cin = U; L.cout = Cb; L.npad = ctx->trk_wo_npad; L.wt = ctx->trk_wo; L.bias = ctx->trk_bo;
-    return run_conv(ctx, L, hseq, U, F, gh, gw, trk, Cb, ORD_LINEAR, EPI_PLAIN, 1.0f);
+    // TimeDistributed(Conv2D(Cb,(1,1)))  'tconv_2'  (MultiObjDetTracker.py:182)
+    return run_conv(ctx, ctx->trk_out, hseq, U, F, gh, gw, trk, Cb, ORD_LINEAR, EPI_PLAIN, 1.0f);
 }
 
 // ---------------------------------------------------------------------------
@@ -1934,12 +1871,13 @@ extern "C" int dt_tiny_load(dt_ctx *ctx, int D, int units, int out_dim, const fl
         bd.assign(Opad, 0.0f);
         for (int o = 0; o < O; ++o) bd[o] = h_dense_bias[o];
     }
+    (void)hipStreamSynchronize(ctx->stream);      // queued work may still read the weights these replace
     int rc;
-    if ((rc = upload(ctx, &ctx->tiny_wx, wx))) return rc;
-    if ((rc = upload(ctx, &ctx->tiny_bx, bx))) return rc;
-    if ((rc = upload(ctx, &ctx->tiny_ur, ur))) return rc;
-    if ((rc = upload(ctx, &ctx->tiny_wd, wd))) return rc;
-    if ((rc = upload(ctx, &ctx->tiny_bd, bd))) return rc;
+    if ((rc = upload(ctx, ctx->tiny_wx, wx))) return rc;
+    if ((rc = upload(ctx, ctx->tiny_bx, bx))) return rc;
+    if ((rc = upload(ctx, ctx->tiny_ur, ur))) return rc;
+    if ((rc = upload(ctx, ctx->tiny_wd, wd))) return rc;
+    if ((rc = upload(ctx, ctx->tiny_bd, bd))) return rc;
     ctx->tiny_D = D; ctx->tiny_Dpad = Dp; ctx->tiny_U = U; ctx->tiny_O = O; ctx->tiny_Opad = Opad;
     graphs_clear(ctx);
     ctx->tiny_loaded = true;
@@ -1985,7 +1923,7 @@ extern "C" int dt_tiny_sequence(dt_ctx *ctx, const float *d_x, int n_seq, int T,
         ConvArgs a;
         memset(&a, 0, sizeof(a));
         a.in = x; a.in_ld = Dp; a.in_bs = Dp;
-        a.wt = ctx->tiny_wx; a.bias = ctx->tiny_bx;
+        a.wt = ctx->tiny_wx.get(); a.bias = ctx->tiny_bx.get();
         a.out = xproj; a.out_ld = N4; a.out_bs = N4;
         a.B = R; a.H = 1; a.W = 1; a.Cin = Dp; a.N = N4; a.M = R; a.K = Dp;
         a.slope = 1.0f;
@@ -2002,7 +1940,7 @@ extern "C" int dt_tiny_sequence(dt_ctx *ctx, const float *d_x, int n_seq, int T,
             rc = launch_lstm_step0(ctx->stream, xproj, xp_bs, cst, hseq, h_bs, n_seq, U);
         else
             rc = launch_lstm_step(ctx->stream, xproj + (long long)t * N4, xp_bs, hseq + (long long)(t - 1) * U, h_bs,
-                                  cst, ctx->tiny_ur, hseq + (long long)t * U, h_bs, n_seq, U);
+                                  cst, ctx->tiny_ur.get(), hseq + (long long)t * U, h_bs, n_seq, U);
         if (rc) return dt_fail(ctx, DT_ERR_DEVICE, "LSTM step launch failed");
     }
     return DT_OK;
@@ -2011,13 +1949,13 @@ extern "C" int dt_tiny_sequence(dt_ctx *ctx, const float *d_x, int n_seq, int T,
     const int O = ctx->tiny_O;
     if (O <= 8) {
         ProfScope ps(ctx, "misc", 2.0 * R * U * (double)O, 4.0 * R * (U + (double)O));
-        if (launch_dense_sigmoid(ctx->stream, hseq, U, ctx->tiny_wd, ctx->tiny_bd, R, U, O, d_out, O))
+        if (launch_dense_sigmoid(ctx->stream, hseq, U, ctx->tiny_wd.get(), ctx->tiny_bd.get(), R, U, O, d_out, O))
             return dt_fail(ctx, DT_ERR_DEVICE, "Dense launch failed");
     } else {   // TimeDistributed(Dense(heatmap_size^2, sigmoid))  (TinyHeatmapTracker.py:43)
         ConvArgs a;
         memset(&a, 0, sizeof(a));
         a.in = hseq; a.in_ld = U; a.in_bs = U;
-        a.wt = ctx->tiny_wd; a.bias = ctx->tiny_bd;
+        a.wt = ctx->tiny_wd.get(); a.bias = ctx->tiny_bd.get();
         a.out = d_out; a.out_ld = O; a.out_bs = O;
         a.B = R; a.H = 1; a.W = 1; a.Cin = U; a.N = O; a.M = R; a.K = U;
         a.slope = 1.0f; a.act = 1;
@@ -2124,17 +2062,11 @@ extern "C" int dt_conv2d(dt_ctx *ctx, const float *d_in, int B, int H, int W, in
 }
 
 namespace {
-struct DevTemps {   // device temporaries of a test entry point: freed on every return path
-    std::vector<float *> p;
+// A test entry point keeps its device temporaries in DevMem / WinoWeights locals and declares one of these BEHIND them: on every return path
+// the stream is idle before they are released
+struct SyncAtExit {
     hipStream_t st;
-    explicit DevTemps(hipStream_t s) : st(s) {}
-    ~DevTemps()
-    {
-        (void)hipStreamSynchronize(st);
-        for (float *q : p)
-            if (q) (void)hipFree(q);
-    }
-    float **add() { p.push_back(nullptr); return &p.back(); }
+    ~SyncAtExit() { (void)hipStreamSynchronize(st); }
 };
 }   // namespace
 
@@ -2154,15 +2086,14 @@ extern "C" int dt_convlstm_step(dt_ctx *ctx, const float *d_x, int B, int H, int
     pack_conv_weights(h_kernel, 3, Cx, N4, nullptr, Cx, n_map.data(), N4, nullptr, wx.data());
     pack_conv_weights(h_recurrent, 3, U, N4, nullptr, U, n_map.data(), N4, nullptr, wh.data());
     for (int np = 0; np < N4; ++np) bx[np] = h_bias[n_map[np]];
-    DevTemps tmp(ctx->stream);
-    tmp.p.reserve(8);
-    float **dwx = tmp.add(), **dwh = tmp.add(), **dbx = tmp.add();
+    DevMem<float> dwx, dwh, dbx;
+    WinoWeights uwx, uwh;
+    SyncAtExit idle{ctx->stream};
     int rc;
     if ((rc = upload(ctx, dwx, wx)) || (rc = upload(ctx, dwh, wh)) || (rc = upload(ctx, dbx, bx))) return rc;
     float *xproj = ws_get(ctx, "cl_xproj", (size_t)B * GG * N4 * sizeof(float));
     if (!xproj) return DT_ERR_DEVICE;
     if (ctx->pol.wino == 2 && wino_wanted(ctx, 3, Cx, N4) && wino_wanted(ctx, 3, U, N4)) {   // the same step through the Winograd path
-        float **uwx = tmp.add(), **uwh = tmp.add();
         const int ts = wino_tile(ctx, false);
         if ((rc = upload_wino(ctx, uwx, ts, h_kernel, Cx, N4, nullptr, Cx, n_map.data(), N4, nullptr, ts == 6)) ||
             (rc = upload_wino(ctx, uwh, ts, h_recurrent, U, N4, nullptr, U, n_map.data(), N4, nullptr, ts == 4)))
@@ -2171,23 +2102,19 @@ extern "C" int dt_convlstm_step(dt_ctx *ctx, const float *d_x, int B, int H, int
         memset(&io, 0, sizeof(io));
         io.in = d_x; io.in_ld = Cx; io.in_bs = (long long)GG * Cx;
         io.out = xproj; io.out_ld = N4; io.out_bs = (long long)GG * N4;
-        struct Twins {      // the split twins of the two temporaries go with them
-            dt_ctx *c; float **a, **b;
-            ~Twins() { (void)hipStreamSynchronize(c->stream); s3_drop(c, *a); s3_drop(c, *b); }
-        } twins{ctx, uwx, uwh};
-        if ((rc = run_wino(ctx, *uwx, ts, *dbx, Cx, N4, N4, B, H, W, io, 1.0f, "convlstm_xproj", 0, AMAX_TEST))) return rc;
+        if ((rc = run_wino(ctx, uwx, dbx.get(), N4, B, H, W, io, 1.0f, "convlstm_xproj", 0, AMAX_TEST))) return rc;
         HIP_TRY(ctx, hipMemcpyAsync(d_c_out, d_c, (size_t)B * GG * U * sizeof(float), hipMemcpyDeviceToDevice, ctx->stream));
         memset(&io, 0, sizeof(io));
         io.in = d_h; io.in_ld = U; io.in_bs = (long long)GG * U;
         io.out = d_h_out; io.out_ld = U; io.out_bs = (long long)GG * U;
         io.xproj = xproj; io.xp_ld = N4; io.xp_bs = (long long)GG * N4;
         io.cstate = d_c_out; io.c_ld = U; io.c_bs = (long long)GG * U;
-        return run_wino(ctx, *uwh, ts, nullptr, U, N4, N4, B, H, W, io, 1.0f, "convlstm_step", 0, AMAX_TEST + 1);      // (a caller's h: measured)
+        return run_wino(ctx, uwh, nullptr, N4, B, H, W, io, 1.0f, "convlstm_step", 0, AMAX_TEST + 1);      // (a caller's h: measured)
     }
     ConvArgs a;
     memset(&a, 0, sizeof(a));
     a.in = d_x; a.in_ld = Cx; a.in_bs = (long long)GG * Cx;
-    a.wt = *dwx; a.bias = *dbx;
+    a.wt = dwx.get(); a.bias = dbx.get();
     a.out = xproj; a.out_ld = N4; a.out_bs = (long long)GG * N4;
     a.B = B; a.H = H; a.W = W; a.Cin = Cx; a.N = N4; a.M = B * GG; a.K = 9 * Cx; a.slope = 1.0f;
     if (launch_igemm(ctx, a, 3, ORD_LINEAR, EPI_PLAIN, CFG_128x128))
@@ -2195,7 +2122,7 @@ extern "C" int dt_convlstm_step(dt_ctx *ctx, const float *d_x, int B, int H, int
     HIP_TRY(ctx, hipMemcpyAsync(d_c_out, d_c, (size_t)B * GG * U * sizeof(float), hipMemcpyDeviceToDevice, ctx->stream));
     memset(&a, 0, sizeof(a));
     a.in = d_h; a.in_ld = U; a.in_bs = (long long)GG * U;
-    a.wt = *dwh;
+    a.wt = dwh.get();
     a.out = d_h_out; a.out_ld = U; a.out_bs = (long long)GG * U;
     a.xproj = xproj; a.xp_ld = N4; a.xp_bs = (long long)GG * N4;
     a.cstate = d_c_out; a.c_ld = U; a.c_bs = (long long)GG * U;
@@ -2218,32 +2145,31 @@ extern "C" int dt_gemm_split(dt_ctx *ctx, const float *d_v, const float *d_u, in
     if (rows_form && P != 1) return dt_fail(ctx, DT_ERR_ARG, "dt_gemm_split: the fp32-rows form is one GEMM (P = 1)");
     if (rows_form) half = 0;
     const size_t Mp = ((size_t)Mt + 255) / 256 * 256, Np = ((size_t)N + 255) / 256 * 256;
-    DevTemps tmp(ctx->stream);
-    tmp.p.reserve(5);
-    float **vpad = tmp.add(), **upad = tmp.add(), **vs = tmp.add(), **us = tmp.add(), **ps = tmp.add();
-    HIP_TRY(ctx, hipMalloc(reinterpret_cast<void **>(vpad), (size_t)P * Mp * K * sizeof(float)));
-    HIP_TRY(ctx, hipMalloc(reinterpret_cast<void **>(upad), (size_t)P * Np * K * sizeof(float)));
-    HIP_TRY(ctx, hipMalloc(reinterpret_cast<void **>(vs), (size_t)P * nt * Mp * K * sizeof(unsigned short)));
-    HIP_TRY(ctx, hipMalloc(reinterpret_cast<void **>(us), (size_t)P * nt * Np * K * sizeof(unsigned short)));
-    HIP_TRY(ctx, hipMalloc(reinterpret_cast<void **>(ps), 64 * sizeof(float)));
-    HIP_TRY(ctx, hipMemsetAsync(*vpad, 0, (size_t)P * Mp * K * sizeof(float), ctx->stream));
-    HIP_TRY(ctx, hipMemsetAsync(*upad, 0, (size_t)P * Np * K * sizeof(float), ctx->stream));
-    HIP_TRY(ctx, hipMemcpy2DAsync(*vpad, Mp * K * sizeof(float), d_v, (size_t)Mt * K * sizeof(float), (size_t)Mt * K * sizeof(float), P,
+    DevMem<float> vpad, upad, ps;
+    DevMem<unsigned short> vs, us;
+    SyncAtExit idle{ctx->stream};
+    HIP_TRY(ctx, vpad.alloc((size_t)P * Mp * K));
+    HIP_TRY(ctx, upad.alloc((size_t)P * Np * K));
+    HIP_TRY(ctx, vs.alloc((size_t)P * nt * Mp * K));
+    HIP_TRY(ctx, us.alloc((size_t)P * nt * Np * K));
+    HIP_TRY(ctx, ps.alloc(64));
+    HIP_TRY(ctx, hipMemsetAsync(vpad.get(), 0, (size_t)P * Mp * K * sizeof(float), ctx->stream));
+    HIP_TRY(ctx, hipMemsetAsync(upad.get(), 0, (size_t)P * Np * K * sizeof(float), ctx->stream));
+    HIP_TRY(ctx, hipMemcpy2DAsync(vpad.get(), Mp * K * sizeof(float), d_v, (size_t)Mt * K * sizeof(float), (size_t)Mt * K * sizeof(float), P,
                                   hipMemcpyDeviceToDevice, ctx->stream));
-    HIP_TRY(ctx, hipMemcpy2DAsync(*upad, Np * K * sizeof(float), d_u, (size_t)N * K * sizeof(float), (size_t)N * K * sizeof(float), P,
+    HIP_TRY(ctx, hipMemcpy2DAsync(upad.get(), Np * K * sizeof(float), d_u, (size_t)N * K * sizeof(float), (size_t)N * K * sizeof(float), P,
                                   hipMemcpyDeviceToDevice, ctx->stream));
     GemmS3Args g;
     memset(&g, 0, sizeof(g));
     if (nt == 2) {
         unsigned *vslot = amax_slot(ctx, AMAX_TEST);
-        if (launch_wino_h2_pack(ctx->stream, *vpad, P, (int)Mp, K, 0, vslot, reinterpret_cast<unsigned short *>(*vs), nullptr) ||
-            launch_wino_h2_pack(ctx->stream, *upad, P, (int)Np, K, 0, amax_slot(ctx, AMAX_PACK), reinterpret_cast<unsigned short *>(*us), *ps))
+        if (launch_wino_h2_pack(ctx->stream, vpad.get(), P, (int)Mp, K, 0, vslot, vs.get(), nullptr) ||
+            launch_wino_h2_pack(ctx->stream, upad.get(), P, (int)Np, K, 0, amax_slot(ctx, AMAX_PACK), us.get(), ps.get()))
             return dt_fail(ctx, DT_ERR_DEVICE, "fp16-form pack launch failed");
-        g.nt = 2; g.pscale = *ps; g.amax = vslot;      // (the fp32-rows form measures the same tensor: the padding rows are zeros)
-    } else if (launch_wino_s3_pack(ctx->stream, *vpad, P, (int)Mp, K, reinterpret_cast<unsigned short *>(*vs)) ||
-               launch_wino_s3_pack(ctx->stream, *upad, P, (int)Np, K, reinterpret_cast<unsigned short *>(*us)))
+        g.nt = 2; g.pscale = ps.get(); g.amax = vslot;      // (the fp32-rows form measures the same tensor: the padding rows are zeros)
+    } else if (launch_wino_s3_pack(ctx->stream, vpad.get(), P, (int)Mp, K, vs.get()) || launch_wino_s3_pack(ctx->stream, upad.get(), P, (int)Np, K, us.get()))
         return dt_fail(ctx, DT_ERR_DEVICE, "split-bf16 pack launch failed");
-    g.a = reinterpret_cast<unsigned short *>(*vs); g.b = reinterpret_cast<unsigned short *>(*us); g.c = d_m;
+    g.a = vs.get(); g.b = us.get(); g.c = d_m;
     if (rows_form) { g.a = nullptr; g.a_f32 = d_v; g.a_ld = K; g.act = 1; g.slope = 1.0f; }      // (no bias, no activation)
     g.c_ps = (long long)Mt * N; g.P = P; g.Mt = Mt; g.Mp = (int)Mp; g.N = N; g.Np = (int)Np; g.K = K; g.ldc = N; g.half = half;
     ProfScope pscope(ctx, "conv_gemm_s3", wino_gemm_s3_flops(g), (double)P * (2.0 * nt * Mt * K + 2.0 * nt * (double)K * N + 4.0 * (double)Mt * N), "test_gemm");

@@ -235,3 +235,57 @@ def test_trainer_entry_points(tmp_path, monkeypatch):
     assert _check_frames(per_frame, rb, rc, ids) > 0
     for name in ("single",):
         assert callable(trainer.ENTRY_POINTS[name])
+
+
+def test_weights_replaced_on_a_live_context(monkeypatch):
+    """Loading weights a second time on a context that has already run: dt_load_darknet_weights and dt_tracker_load with other
+    weights on the SAME context must leave exactly the state a fresh context gets from those weights -- every device form of every
+    layer (packed, Winograd-domain, the bf16 and fp16 terms of the split GEMM, the merged ConvLSTM projection) is replaced together.
+    DT_WINO=2 / DT_S3=2 build the Winograd sets and both 16-bit forms at this small size; the default policy runs the fp16 terms,
+    the pin override the bf16 ones.  Outputs are compared bit for bit: the same weights through the same kernels."""
+    import mi355_dt
+    monkeypatch.setenv("DT_WINO", "2")      # (the policy is read when a context is created)
+    monkeypatch.setenv("DT_S3", "2")
+    H, W, C, T, n_clips, U = 64, 96, 12, 4, 3, 512      # 12 frames: the fp16 form from Policy::h2_minframes up
+    clips = np.stack([synth.synth_clip(T, H, W, 2, seed=300 + i) for i in range(n_clips)])
+    frames = torch.from_numpy(clips).cuda()
+    weights = {"A": (synth.synth_darknet_blob(C, seed=1234), synth.synth_tracker_weights(C, units=U, seed=1235)),
+               "B": (synth.synth_darknet_blob(C, seed=4321), synth.synth_tracker_weights(C, units=U, seed=5321))}
+
+    def load(c, which):
+        blob, tw = weights[which]
+        assert c.load_darknet_weights(blob) == blob.size
+        c.tracker_load(U, tw["kernel"], tw["recurrent"], tw["bias"], tw["out_kernel"], tw["out_bias"])
+
+    def run(c):
+        out = {}
+        for pin, form in ((0, "s3_form:f16x2"), (1, "s3_form:bf16x3")):
+            c.policy_set("pin", pin)
+            c.profile_reset(); c.profile_enable(True)
+            det = c.detect_forward(frames.reshape(n_clips * T, H, W, 3))
+            trk = c.track_forward(frames, want_det=False)
+            c.profile_enable(False)
+            assert c.profile_read(form)["launches"] > 0, "%s did not run: the test would not see its weights" % form
+            assert c.profile_read("convlstm_xproj:merged_conv23")["launches"] == (1 if pin == 0 else 0)      # (DT_PIN: the two-step projection)
+            out["det_pin%d" % pin] = det.cpu().numpy()
+            out["trk_pin%d" % pin] = trk.cpu().numpy()
+        c.policy_set("pin", -1)
+        return out
+
+    live = mi355_dt.Context()
+    live.detector_config(H, W, 5, C, ANCHORS)
+    load(live, "A")
+    out_a = run(live)
+    load(live, "B")
+    out_b_live = run(live)
+    live.close()
+    fresh = mi355_dt.Context()
+    fresh.detector_config(H, W, 5, C, ANCHORS)
+    load(fresh, "B")
+    out_b_fresh = run(fresh)
+    fresh.close()
+    for k in sorted(out_a):
+        assert np.isfinite(out_b_fresh[k]).all(), k
+        assert not np.array_equal(out_a[k], out_b_fresh[k]), "%s: weights A and B give the same output -- the comparison below would be vacuous" % k
+        assert out_b_live[k].tobytes() == out_b_fresh[k].tobytes(), \
+            "%s: weights reloaded on a live context differ from a fresh context's (max |diff| %g)" % (k, np.abs(out_b_live[k] - out_b_fresh[k]).max())
