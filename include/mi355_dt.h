@@ -48,7 +48,8 @@ DT_API int dt_create(dt_ctx **out);
 DT_API void dt_destroy(dt_ctx *ctx);
 DT_API const char *dt_last_error(dt_ctx *ctx);
 DT_API int dt_set_stream(dt_ctx *ctx, void *hip_stream);
-/* ABI version of this header: major*100+minor (1.08: 1.07 + dt_amax_read; 1.07: 1.06 + dt_gemm_split, dt_policy_set) */
+/* ABI version of this header: major*100+minor (1.08: 1.07 + dt_amax_read, and later the four stream entries dt_stream_open, dt_stream_reset,
+ * dt_track_stream_forward, dt_associate_stream -- additions only, the number stayed; 1.07: 1.06 + dt_gemm_split, dt_policy_set) */
 DT_API int dt_abi_version(void);
 
 /* ---- detector: KerasYOLO ---------------------------------------------- */
@@ -172,6 +173,29 @@ DT_API int dt_track_recurrent_xproj(dt_ctx *ctx, const float *d_xp, int n_clips,
 DT_API int dt_associate(dt_ctx *ctx, const float *d_boxes, const int *d_counts,
                  int n_clips, int T, int cap, float assoc_threshold,
                  int *d_ids, int *d_nids);
+
+/* ---- streaming: ConvLSTM state and track ids carried across calls (addition; the reference's predict() sees one window) ---- *
+ * A live stream delivers a frame, or a few, at a time.  The context holds a table of STREAM SLOTS in device memory; per slot the ConvLSTM
+ * state h, c [G*G][U], the last frame's boxes [cap][8], their count and ids [cap], the next free track id, and counters of frames seen.
+ * Contract: a stream fed in chunks of any sizes gives what the stateless calls give on the concatenation of those chunks as one clip.
+ * A FRESH slot (after dt_stream_open / dt_stream_reset, and after dt_tracker_load, dt_load_darknet_weights or dt_detector_config, which make
+ * every slot fresh -- a load that changes the state's shape closes the table) is indistinguishable from a stateless call.
+ * h_slots is a HOST array of n DISTINCT slot numbers in [0, n_slots) (else DT_ERR_ARG; DT_ERR_STATE before dt_stream_open): stream i of the
+ * call lives in slot h_slots[i].  The array is consumed before the call returns; the streams of a call need not be in step.
+ *
+ * dt_stream_open: (re)allocates the table, every slot fresh; needs a loaded tracker.  cap = box capacity of the association state.
+ * dt_stream_reset: the listed slots fresh again (zero state, ids from 0); h_slots == NULL: all of them.  Stream-ordered, no host wait. */
+DT_API int dt_stream_open(dt_ctx *ctx, int n_slots, int cap);
+DT_API int dt_stream_reset(dt_ctx *ctx, const int *h_slots, int n);
+/* dt_track_forward on d_frames [n, T, H, W, 3]: stream i starts from the state in slot h_slots[i] and leaves its state after frame T-1
+ * there.  d_trk / d_det as dt_track_forward.  When any slot of the call is warm, t = 0 is a full recurrent step (the form steps t >= 1 take). */
+DT_API int dt_track_stream_forward(dt_ctx *ctx, const void *d_frames, int frames_dtype, int n, int T, const int *h_slots,
+                            float *d_trk, float *d_det);
+/* dt_associate on d_boxes [n,T,cap,8], d_counts [n,T]: frame 0 of stream i is matched against the slot's stored last frame, new ids
+ * continue from the slot's counter, d_nids[i] = ids the stream has opened since its reset; the slot then holds frame T-1.  cap must be
+ * the table's (DT_ERR_ARG). */
+DT_API int dt_associate_stream(dt_ctx *ctx, const float *d_boxes, const int *d_counts, int n, int T, int cap,
+                        float thr, const int *h_slots, int *d_ids, int *d_nids);
 
 /* ---- cross-stream detection exchange (multi-GPU; the reference has no counterpart) ---- *
  * north_star: "RCCL all-gather of detections over xGMI only for cross-stream association".  Each rank packs its
@@ -314,7 +338,7 @@ DT_API int dt_amax_read(dt_ctx *ctx, int slot, float *h_out);
  * stream.  dt_profile_read synchronises the stream and returns, per kernel
  * family, launches / total ms / algorithmic flops / algorithmic bytes since the
  * last reset.  names: "conv_igemm", "conv1_direct", "convlstm_gates",
- * "decode_nms", "associate", "lstm_step", "pool", "misc"; per-layer tags such as
+ * "decode_nms", "associate", "lstm_step", "pool", "stream_state", "misc"; per-layer tags such as
  * "conv_igemm:conv_19", "conv_igemm:convlstm_step" are listed by dt_profile_names. */
 DT_API int dt_profile_enable(dt_ctx *ctx, int on);
 DT_API int dt_profile_reset(dt_ctx *ctx);

@@ -31,6 +31,7 @@ SOURCES = {
     "decode.hip": ["-ffp-contract=off"],
     "targets.hip": ["-ffp-contract=off"],
     "recurrent.hip": [],
+    "stream_state.hip": [],
     "network.hip": [],
 }
 COMMON = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-fvisibility=hidden",

@@ -650,9 +650,13 @@ int launch_bbox_iou(hipStream_t st, const float *pairs, int n, float *iou)
 // the largest bbox_iou(i,j) >= thr (ties -> lowest j), else opens a new id.
 // One wavefront per clip: t and i are sequential, j is spread over the lanes
 // and reduced with wavefront shuffles.
+// STREAM (dt_associate_stream): the clip continues the stream in slot carry.slots[clip] -- "the previous frame" of frame 0 is
+// the slot's stored last frame (boxes, ids; an empty one for a fresh slot), ids continue from the slot's next free id, and the
+// clip's last frame, its ids and the counter go back to the slot.  The stateless instance compiles none of it.
 // ---------------------------------------------------------------------------
+template <bool STREAM>
 __global__ __launch_bounds__(64) void associate_kernel(const float *boxes, const int *counts, int T, int cap,
-                                                       float thr, int *ids, int *nids)
+                                                       float thr, int *ids, int *nids, AssocCarry carry)
 {
     // LDS: the previous and the current frame's boxes (x,y,w,h,label) and ids, so the
     // strictly sequential greedy loop runs on LDS latency, not on L2 round trips
@@ -667,13 +671,38 @@ __global__ __launch_bounds__(64) void associate_kernel(const float *boxes, const
     int *id = ids + (long long)clip * T * cap;
     int next_id = 0;
     int np = 0;
+    // the slot's stored frame: sb [cap][8], si [cap], sm = meta row
+    float *sb = nullptr;
+    int *si = nullptr, *sm = nullptr;
+    if constexpr (STREAM) {
+        const int slot = carry.slots[clip];
+        sb = carry.boxes + (long long)slot * cap * DT_BOX_FLOATS;
+        si = carry.ids + (long long)slot * cap;
+        sm = carry.meta + slot * STREAM_META;
+        np = min(sm[SM_COUNT], cap);
+        next_id = sm[SM_NEXT_ID];
+    }
+    // what both forms leave in the slot: the last frame as the caller handed it, its ids (from LDS or, register form, lane j's `outv`)
+    auto store_slot = [&](const volatile int *lds_ids, int outv) {
+        const int n = min(cnt[T - 1], cap);
+        const float4 *src = reinterpret_cast<const float4 *>(bx + (long long)(T - 1) * cap * DT_BOX_FLOATS);
+        float4 *dst = reinterpret_cast<float4 *>(sb);
+        for (int q = lane; q < 2 * n; q += 64) dst[q] = src[q];
+        for (int j = lane; j < n; j += 64) si[j] = lds_ids ? lds_ids[j] : outv;
+        if (lane == 0) {
+            sm[SM_COUNT] = n;
+            sm[SM_NEXT_ID] = next_id;
+            const int f = sm[SM_ASSOC_FRAMES];
+            sm[SM_ASSOC_FRAMES] = f > (1 << 30) ? f : f + T;
+        }
+    };
     // ---- register form (every frame of the clip has at most 64 boxes, T <= 64: the tracking workloads) ----
     // Lane j holds box j of the previous and of the current frame and its id in registers; box i reaches the other lanes
     // through v_readlane, the claim is a lane-select.  No LDS, no fence: the frame loop is the wavefront's own program order.
     // The next frame's boxes are requested a whole frame ahead (address selected, not the load: lanes >= n re-read box 0), and
     // a frame's ids are stored one frame late, after the wait for the boxes -- so the loop never waits for a store.
     const int cnt_l = lane < T ? min(cnt[lane], cap) : 0;
-    if (T <= 64 && !__ballot(cnt_l > 64)) {
+    if (T <= 64 && !__ballot(cnt_l > 64) && np <= 64) {      // (np: the stored frame sits in the same registers)
         auto request = [&](int t, float4 &q, float &ql) {
             const int n = __builtin_amdgcn_readlane(cnt_l, t);
             const float *src = bx + ((long long)t * cap + (lane < n ? lane : 0)) * DT_BOX_FLOATS;
@@ -684,6 +713,14 @@ __global__ __launch_bounds__(64) void associate_kernel(const float *boxes, const
         request(0, nq, nl);
         float pbx = 0.0f, pby = 0.0f, pbw = 0.0f, pbh = 0.0f, pbl = 0.0f;
         int pidv = -1, outv = -1;
+        if constexpr (STREAM) {
+            if (lane < np) {
+                const float *q = sb + lane * DT_BOX_FLOATS;
+                const float4 v = *reinterpret_cast<const float4 *>(q);
+                pbx = v.x; pby = v.y; pbw = v.z; pbh = v.w; pbl = q[5];
+                pidv = si[lane];
+            }
+        }
         for (int t = 0; t < T; ++t) {
             const int n = __builtin_amdgcn_readlane(cnt_l, t);
             const float cx = nq.x, cy = nq.y, cw = nq.z, ch = nq.w, cl = nl;        // waits for frame t's boxes
@@ -713,9 +750,17 @@ __global__ __launch_bounds__(64) void associate_kernel(const float *boxes, const
         }
         for (int j = lane; j < cap; j += 64) id[(T - 1) * cap + j] = j < 64 ? outv : -1;
         if (lane == 0) nids[clip] = next_id;
+        if constexpr (STREAM) store_slot(nullptr, outv);
         return;
     }
     // ---- general form (any count up to cap): previous / current frame in LDS ----
+    if constexpr (STREAM) {
+        for (int j = lane; j < np; j += 64) {
+            const float *q = sb + j * 8;
+            pb[j] = q[0]; pb[cap + j] = q[1]; pb[2 * cap + j] = q[2]; pb[3 * cap + j] = q[3]; pb[4 * cap + j] = q[5];
+            pid[j] = si[j];
+        }      // (the fence after frame 0's boxes below orders these too)
+    }
     for (int t = 0; t < T; ++t) {
         const int n = min(cnt[t], cap);
         const float *cur = bx + (long long)t * cap * DT_BOX_FLOATS;
@@ -769,6 +814,7 @@ __global__ __launch_bounds__(64) void associate_kernel(const float *boxes, const
         __builtin_amdgcn_wave_barrier();
     }
     if (lane == 0) nids[clip] = next_id;
+    if constexpr (STREAM) store_slot(pid, -1);
 }
 
 int launch_associate(hipStream_t st, const float *boxes, const int *counts, int n_clips, int T, int cap, float thr,
@@ -779,12 +825,30 @@ int launch_associate(hipStream_t st, const float *boxes, const int *counts, int 
     if (lds > 160 * 1024) return 2;
     static PerDeviceOnce attr;
     if (attr.ensure(nullptr, [](int) {
-            return hipFuncSetAttribute(reinterpret_cast<const void *>(associate_kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
+            return hipFuncSetAttribute(reinterpret_cast<const void *>(associate_kernel<false>), hipFuncAttributeMaxDynamicSharedMemorySize,
                                        160 * 1024) != hipSuccess;
         }))
         return 1;
-    hipLaunchKernelGGL(associate_kernel, dim3((unsigned)n_clips), dim3(64), lds, st, boxes, counts, T, cap, thr, ids,
-                       nids);
+    hipLaunchKernelGGL(associate_kernel<false>, dim3((unsigned)n_clips), dim3(64), lds, st, boxes, counts, T, cap, thr, ids,
+                       nids, AssocCarry{nullptr, nullptr, nullptr, nullptr});
+    return hipGetLastError() == hipSuccess ? 0 : 1;
+}
+
+int launch_associate_stream(hipStream_t st, const float *boxes, const int *counts, int n_clips, int T, int cap, float thr,
+                            int *ids, int *nids, const AssocCarry &carry)
+{
+    if (n_clips <= 0) return 0;
+    if (T <= 0 || !carry.slots) return 2;
+    const size_t lds = (size_t)cap * 12 * sizeof(float);
+    if (lds > 160 * 1024) return 2;
+    static PerDeviceOnce attr;
+    if (attr.ensure(nullptr, [](int) {
+            return hipFuncSetAttribute(reinterpret_cast<const void *>(associate_kernel<true>), hipFuncAttributeMaxDynamicSharedMemorySize,
+                                       160 * 1024) != hipSuccess;
+        }))
+        return 1;
+    hipLaunchKernelGGL(associate_kernel<true>, dim3((unsigned)n_clips), dim3(64), lds, st, boxes, counts, T, cap, thr, ids,
+                       nids, carry);
     return hipGetLastError() == hipSuccess ? 0 : 1;
 }
 

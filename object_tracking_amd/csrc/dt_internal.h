@@ -314,6 +314,37 @@ int launch_bbox_iou(hipStream_t st, const float *pairs, int n, float *iou);
 
 int launch_associate(hipStream_t st, const float *boxes, const int *counts, int n_clips, int T, int cap,
                      float thr, int *ids, int *nids);
+// Association state of the stream slots (dt_associate_stream): clip i of the call continues slot slots[i].  Per slot the last frame it saw --
+// boxes [cap][8] as the caller handed them, ids [cap] -- and meta = STREAM_META ints (stream_state.hip)
+struct AssocCarry {
+    const int *slots;   // [n_clips] on the device; null = the stateless launch
+    float *boxes;       // [n_slots][cap][8]
+    int *ids;           // [n_slots][cap]
+    int *meta;          // [n_slots][STREAM_META]
+};
+int launch_associate_stream(hipStream_t st, const float *boxes, const int *counts, int n_clips, int T, int cap,
+                            float thr, int *ids, int *nids, const AssocCarry &carry);
+
+// ---------------------------------------------------------------------------
+// stream slots: state that outlives a call (stream_state.hip)
+// ---------------------------------------------------------------------------
+// meta row of a slot: boxes in the stored last frame, next free track id, frames the recurrence has seen (0 = the slot's h / c rows
+// read as zeros whatever they hold), frames the association has seen.  A slot whose row is all zero is fresh.
+enum { SM_COUNT = 0, SM_NEXT_ID = 1, SM_FRAMES = 2, SM_ASSOC_FRAMES = 3, STREAM_META = 4 };
+// the call's slot list, from the caller's HOST array into the library-owned device list: the numbers travel as kernel arguments of a
+// launch OUTSIDE any captured graph, so neither a host synchronisation nor pinned staging is needed.  reset_meta != null: the listed slots' meta rows are zeroed too
+int launch_stream_slots(hipStream_t st, const int *h_slots, int n, int *d_list, int *reset_meta);
+struct StateMove {
+    const int *slots;      // [n] device
+    float *tab_h, *tab_c;  // [n_slots][row]
+    int *meta;             // [n_slots][STREAM_META]
+    float *h, *c;          // the call's rows: stream i at h + i * h_bs / c + i * c_bs
+    long long h_bs, c_bs;
+    int n, row;            // row = G*G*U floats, a multiple of 32
+    int scatter;           // 0: table -> call (gather);  1: call -> table, and the slots' frame counters advance by T
+    int T;
+};
+int launch_stream_state_move(hipStream_t st, const StateMove &a);
 
 int launch_heatmap_from_boxes(hipStream_t st, const float *box4, const double *xywh64, int n, int hs, float *out);
 int launch_rect_from_heatmap(hipStream_t st, const float *heat, int n, int hs, float thresh, int *rect);
@@ -483,6 +514,18 @@ struct Policy {
                              //                  the producers' tags (the producers still publish): tests compare the published words with the measured ones
 };
 
+// The stream slots of a context (dt_stream_open): everything a stream carries from one call to the next, in device memory
+struct StreamTable {
+    int n_slots = 0, cap = 0;
+    int row = 0;               // floats per h / c row: G*G*U of the tracker the table was opened under
+    DevMem<float> h, c;        // ConvLSTM state [n_slots][G*G][U]
+    DevMem<float> boxes;       // the last frame's boxes [n_slots][cap][8]
+    DevMem<int> ids;           // ... and their ids [n_slots][cap]
+    DevMem<int> meta;          // [n_slots][STREAM_META]
+    DevMem<int> list;          // [n_slots]: the slot list of the running call, filled before its launches (never a kernel argument of a captured launch)
+    std::vector<char> warm;    // host mirror of meta[SM_FRAMES] != 0: decides between the gates-only launch and a full step at t = 0
+};
+
 struct dt_ctx {
     std::string err;
     Policy pol;
@@ -524,6 +567,7 @@ struct dt_ctx {
     bool tiny_loaded = false;
     int tiny_D = 0, tiny_Dpad = 0, tiny_U = 0, tiny_O = 0, tiny_Opad = 0;
     DevMem<float> tiny_wx, tiny_bx, tiny_ur, tiny_wd, tiny_bd;
+    StreamTable streams;
     // workspaces (grown on demand)
     std::map<std::string, DevBuf> ws;
     int last_batch = 0;

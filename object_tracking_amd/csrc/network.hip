@@ -3,6 +3,7 @@
 //   detector  models_detection/KerasYOLO.py:277-405 (weight order :244-274)
 //   tracker   models_tracking/MultiObjDetTracker.py:160-189
 //   tiny      models_tracking/TinyTracker.py:25-41
+#include <algorithm>
 #include <cmath>
 #include <cstdarg>
 #include <cstdlib>
@@ -279,7 +280,7 @@ static void policy_refresh(dt_ctx *ctx)
 }
 
 // ---------------------------------------------------------------------------
-extern "C" int dt_abi_version(void) { return 108; }   // 1.08: + dt_amax_read (1.07: + dt_gemm_split, dt_policy_set)
+extern "C" int dt_abi_version(void) { return 108; }   // 1.08: + dt_amax_read, the four dt_*stream* entries (1.07: + dt_gemm_split, dt_policy_set)
 
 // the host's view of a max-|x| slot: the maximum over its sub-words, as dt_amax_read (dt_internal.h) takes it on the device
 extern "C" int dt_amax_read(dt_ctx *ctx, int slot, float *h_out)
@@ -378,6 +379,78 @@ extern "C" int dt_set_stream(dt_ctx *ctx, void *hip_stream)
 }
 
 // ---------------------------------------------------------------------------
+// stream slots (dt_stream_open): state that outlives a call
+// ---------------------------------------------------------------------------
+// Every slot fresh again, in stream order: a zero meta row is a fresh slot (the h / c rows of such a slot read as zeros, stream_state.hip).
+// The loaders call this: state computed under other weights means nothing.  A table whose rows no longer fit the model is closed.
+static int streams_fresh(dt_ctx *ctx)
+{
+    StreamTable &S = ctx->streams;
+    if (!S.n_slots) return DT_OK;
+    const int row = (ctx->image_h / 32) * (ctx->image_w / 32) * ctx->trk_units;
+    if (row != S.row) {
+        (void)hipStreamSynchronize(ctx->stream);
+        S = StreamTable();
+        return DT_OK;
+    }
+    HIP_TRY(ctx, hipMemsetAsync(S.meta.get(), 0, (size_t)S.n_slots * STREAM_META * sizeof(int), ctx->stream));
+    std::fill(S.warm.begin(), S.warm.end(), 0);
+    return DT_OK;
+}
+
+// the slot list of a stream call: n distinct numbers in [0, n_slots)
+static int streams_check_list(dt_ctx *ctx, const int *h_slots, int n)
+{
+    const StreamTable &S = ctx->streams;
+    if (!S.n_slots) return dt_fail(ctx, DT_ERR_STATE, "dt_stream_open must be called first");
+    if (!h_slots || n <= 0 || n > S.n_slots) return dt_fail(ctx, DT_ERR_ARG, "a stream call names between 1 and n_slots = %d slots", S.n_slots);
+    std::vector<char> seen((size_t)S.n_slots, 0);
+    for (int i = 0; i < n; ++i) {
+        if (h_slots[i] < 0 || h_slots[i] >= S.n_slots) return dt_fail(ctx, DT_ERR_ARG, "slot %d is outside [0, %d)", h_slots[i], S.n_slots);
+        if (seen[h_slots[i]]) return dt_fail(ctx, DT_ERR_ARG, "slot %d is named twice in one call", h_slots[i]);
+        seen[h_slots[i]] = 1;
+    }
+    return DT_OK;
+}
+
+extern "C" int dt_stream_open(dt_ctx *ctx, int n_slots, int cap)
+{
+    if (!ctx) return DT_ERR_ARG;
+    if (!ctx->trk_loaded) return dt_fail(ctx, DT_ERR_STATE, "tracker weights not loaded");
+    if (n_slots <= 0 || n_slots > 65535 || cap <= 0) return dt_fail(ctx, DT_ERR_ARG, "n_slots must be in [1, 65535] and cap positive");
+    const long long row = (long long)(ctx->image_h / 32) * (ctx->image_w / 32) * ctx->trk_units;
+    if (row <= 0 || row >= (1ll << 31)) return dt_fail(ctx, DT_ERR_ARG, "bad state row size");
+    graphs_clear(ctx);      // captured state moves hold the old table's pointers
+    (void)hipStreamSynchronize(ctx->stream);
+    StreamTable S;
+    HIP_TRY(ctx, S.h.alloc((size_t)n_slots * row));
+    HIP_TRY(ctx, S.c.alloc((size_t)n_slots * row));
+    HIP_TRY(ctx, S.boxes.alloc((size_t)n_slots * cap * DT_BOX_FLOATS));
+    HIP_TRY(ctx, S.ids.alloc((size_t)n_slots * cap));
+    HIP_TRY(ctx, S.meta.alloc((size_t)n_slots * STREAM_META));
+    HIP_TRY(ctx, S.list.alloc((size_t)n_slots));
+    HIP_TRY(ctx, hipMemsetAsync(S.meta.get(), 0, (size_t)n_slots * STREAM_META * sizeof(int), ctx->stream));
+    S.n_slots = n_slots; S.cap = cap; S.row = (int)row;
+    S.warm.assign((size_t)n_slots, 0);
+    ctx->streams = std::move(S);
+    return DT_OK;
+}
+
+extern "C" int dt_stream_reset(dt_ctx *ctx, const int *h_slots, int n)
+{
+    if (!ctx) return DT_ERR_ARG;
+    StreamTable &S = ctx->streams;
+    if (!S.n_slots) return dt_fail(ctx, DT_ERR_STATE, "dt_stream_open must be called first");
+    if (!h_slots) return streams_fresh(ctx);
+    if (n == 0) return DT_OK;
+    const int rc = streams_check_list(ctx, h_slots, n);
+    if (rc) return rc;
+    if (launch_stream_slots(ctx->stream, h_slots, n, S.list.get(), S.meta.get())) return dt_fail(ctx, DT_ERR_DEVICE, "stream reset launch failed");
+    for (int i = 0; i < n; ++i) S.warm[h_slots[i]] = 0;
+    return DT_OK;
+}
+
+// ---------------------------------------------------------------------------
 // detector
 // ---------------------------------------------------------------------------
 extern "C" int dt_detector_config(dt_ctx *ctx, int image_h, int image_w, int nb_box, int nb_class,
@@ -394,7 +467,8 @@ extern "C" int dt_detector_config(dt_ctx *ctx, int image_h, int image_w, int nb_
     std::vector<float> a(h_anchors, h_anchors + 2 * nb_box);
     memcpy(ctx->anchors, h_anchors, sizeof(float) * 2 * nb_box);
     ctx->det_loaded = false;
-    return upload(ctx, ctx->anchors_dev, a);
+    const int rc = streams_fresh(ctx);
+    return rc ? rc : upload(ctx, ctx->anchors_dev, a);
 }
 
 // kernel in the darknet file is (O,I,H,W) (KerasYOLO.py:267-268 reshapes the
@@ -683,6 +757,7 @@ extern "C" int dt_load_darknet_weights(dt_ctx *ctx, const float *h_blob, size_t 
     if (consumed) *consumed = off;
     graphs_clear(ctx);
     ctx->det_loaded = true;
+    if (const int rc = streams_fresh(ctx)) return rc;
     return build_merged_xproj(ctx);
 }
 
@@ -1589,6 +1664,7 @@ extern "C" int dt_tracker_load(dt_ctx *ctx, int units, const float *h_kernel, co
     ctx->trk_hbias.assign(h_bias, h_bias + (size_t)4 * U);
     graphs_clear(ctx);
     ctx->trk_loaded = true;
+    if (const int rc = streams_fresh(ctx)) return rc;
     return build_merged_xproj(ctx);
 }
 
@@ -1604,11 +1680,18 @@ static bool xproj_merged(const dt_ctx *ctx, int F, int gh, int gw)
 //   z != null, xproj_ext != null, hseq == null : the input projection ONLY, into the caller's buffer (dt_track_detect_xproj:
 //       the projection does not depend on the recurrence, so a frame-sharded deployment runs it where the frame is)
 //   z == null, xproj_ext != null : the recurrence ONLY, on the caller's stitched projection rows (dt_track_recurrent_xproj)
+// carry (dt_track_stream_forward): clip i continues the stream in slot ctx->streams.list[i] (a DEVICE list, filled by the caller of this
+// function before it).  CARRY_WARM: h_{-1} and c come from the slots -- gathered into contiguous rows, and t = 0 is a full recurrent step
+// in the form steps t >= 1 take; CARRY_FRESH: every slot of the call is fresh, t = 0 stays the gates-only launch.  Both leave
+// h_{T-1} and c in the slots.
+enum { CARRY_NONE = 0, CARRY_FRESH = 1, CARRY_WARM = 2 };
 static int convlstm_sequence(dt_ctx *ctx, const float *z, int Cx, int n_clips, int T, int gh, int gw, int U,
                              const float *wx, const float *bx, const float *wh, float *hseq /*[n_clips][T][GG][U]*/,
-                             const WinoWeights &wx_wino, const WinoWeights &wh_wino, float *xproj_ext = nullptr)
+                             const WinoWeights &wx_wino, const WinoWeights &wh_wino, float *xproj_ext = nullptr, int carry = CARRY_NONE)
 {
     const int GG = gh * gw, F = n_clips * T, N4 = 4 * U;
+    float *h0 = carry == CARRY_WARM ? ws_get(ctx, "trk_h0", (size_t)n_clips * GG * U * sizeof(float)) : nullptr;   // h_{-1} [n_clips][GG][U]
+    if (carry == CARRY_WARM && !h0) return DT_ERR_DEVICE;
     float *xproj = xproj_ext ? xproj_ext : ws_get(ctx, "trk_xproj", (size_t)F * GG * N4 * sizeof(float));
     float *cst = hseq ? ws_get(ctx, "trk_c", (size_t)n_clips * GG * U * sizeof(float)) : nullptr;
     if (!xproj || (hseq && !cst)) return DT_ERR_DEVICE;
@@ -1621,7 +1704,7 @@ static int convlstm_sequence(dt_ctx *ctx, const float *z, int Cx, int n_clips, i
         auto it = ctx->ws.find("trk_z");
         z_owned = it != ctx->ws.end() && it->second.p == static_cast<const void *>(z);
     }
-    const std::string shape = std::to_string(n_clips) + "x" + std::to_string(T);
+    const std::string shape = std::to_string(n_clips) + "x" + std::to_string(T) + (carry == CARRY_WARM ? ":warm" : (carry == CARRY_FRESH ? ":fresh" : ""));
     auto input_projection = [&]() -> int {
     if (z_owned && xproj_merged(ctx, F, gh, gw) && &wx_wino == &ctx->trk_wx_wino) {
         // conv_23 folded into the projection (build_merged_xproj): the 1024 conv_feat channels of z only, border-aware bias -- for the library's OWN z
@@ -1660,16 +1743,31 @@ static int convlstm_sequence(dt_ctx *ctx, const float *z, int Cx, int n_clips, i
     };
     auto recurrence = [&]() -> int {
     const long long xp_bs = (long long)T * GG * N4, h_bs = (long long)T * GG * U, c_bs = (long long)GG * U;
-    {   // t = 0: h_{-1} = c_{-1} = 0
+    auto state_move = [&](int scatter) -> int {
+        const StreamTable &S = ctx->streams;
+        StateMove m;
+        memset(&m, 0, sizeof(m));
+        m.slots = S.list.get(); m.tab_h = S.h.get(); m.tab_c = S.c.get(); m.meta = S.meta.get();
+        m.h = scatter ? hseq + (long long)(T - 1) * GG * U : h0; m.h_bs = scatter ? h_bs : c_bs;
+        m.c = cst; m.c_bs = c_bs;
+        m.n = n_clips; m.row = GG * U; m.scatter = scatter; m.T = T;
+        ProfScope ps(ctx, "stream_state", 0.0, 16.0 * n_clips * GG * (double)U, scatter ? "scatter" : "gather");
+        return launch_stream_state_move(ctx->stream, m) ? dt_fail(ctx, DT_ERR_DEVICE, "stream state move launch failed") : DT_OK;
+    };
+    if (carry == CARRY_WARM) {
+        if (const int rc = state_move(0)) return rc;
+    } else {   // t = 0: h_{-1} = c_{-1} = 0
         ProfScope ps(ctx, "convlstm_gates", 0.0, 4.0 * n_clips * GG * (3.0 * U + 2.0 * U));
         if (launch_convlstm_gates_only(ctx->stream, xproj, xp_bs, N4, cst, c_bs, U, hseq, h_bs, U, n_clips, GG, U))
             return dt_fail(ctx, DT_ERR_DEVICE, "ConvLSTM t=0 launch failed");
     }
-    for (int t = 1; t < T; ++t) {
+    for (int t = carry == CARRY_WARM ? 0 : 1; t < T; ++t) {
+        const float *hprev = t ? hseq + (long long)(t - 1) * GG * U : h0;      // (t = 0 of a warm call: the gathered rows)
+        const long long hprev_bs = t ? h_bs : c_bs;
         if (wino_runs(ctx, wh_wino, n_clips, gh, gw, N4)) {
             WinoIO io;
             memset(&io, 0, sizeof(io));
-            io.in = hseq + (long long)(t - 1) * GG * U; io.in_ld = U; io.in_bs = h_bs;
+            io.in = hprev; io.in_ld = U; io.in_bs = hprev_bs;
             io.out = hseq + (long long)t * GG * U; io.out_ld = U; io.out_bs = h_bs;
             io.xproj = xproj + (long long)t * GG * N4; io.xp_ld = N4; io.xp_bs = xp_bs;
             io.cstate = cst; io.c_ld = U; io.c_bs = c_bs;
@@ -1680,7 +1778,7 @@ static int convlstm_sequence(dt_ctx *ctx, const float *z, int Cx, int n_clips, i
         }
         ConvArgs a;
         memset(&a, 0, sizeof(a));
-        a.in = hseq + (long long)(t - 1) * GG * U; a.in_ld = U; a.in_bs = h_bs;
+        a.in = hprev; a.in_ld = U; a.in_bs = hprev_bs;
         a.wt = wh; a.bias = nullptr;
         a.out = hseq + (long long)t * GG * U; a.out_ld = U; a.out_bs = h_bs;
         a.xproj = xproj + (long long)t * GG * N4; a.xp_ld = N4; a.xp_bs = xp_bs;
@@ -1694,7 +1792,7 @@ static int convlstm_sequence(dt_ctx *ctx, const float *z, int Cx, int n_clips, i
         if (launch_igemm(ctx, a, 3, ORD_LINEAR, EPI_GATES, pick_cfg(a.M, N4, 3)))
             return dt_fail(ctx, DT_ERR_DEVICE, "ConvLSTM step launch failed");
     }
-    return DT_OK;
+    return carry != CARRY_NONE ? state_move(1) : DT_OK;
     };
     if (xproj_ext) {       // caller-owned projection rows: nothing here may be baked into a replayed graph
         if (z) { const int rc = input_projection(); if (rc || !hseq) return rc; }
@@ -1710,14 +1808,14 @@ static int convlstm_sequence(dt_ctx *ctx, const float *z, int Cx, int n_clips, i
 }
 
 // the recurrent head on z [n_clips][T][G*G][Cx] (library- or caller-owned): ConvLSTM2D over T, then tconv_2
-static int track_recurrent_internal(dt_ctx *ctx, const float *z, int n_clips, int T, float *d_trk)
+static int track_recurrent_internal(dt_ctx *ctx, const float *z, int n_clips, int T, float *d_trk, int carry = CARRY_NONE)
 {
     const int gh = ctx->image_h / 32, gw = ctx->image_w / 32, GG = gh * gw;
     const int F = n_clips * T, U = ctx->trk_units, Cx = ctx->trk_cx, Cb = ctx->cb;
     float *hseq = ws_get(ctx, "trk_h", (size_t)F * GG * U * sizeof(float));
     if (!hseq) return DT_ERR_DEVICE;
     int rc = convlstm_sequence(ctx, z, Cx, n_clips, T, gh, gw, U, ctx->trk_wx.get(), ctx->trk_bx.get(), ctx->trk_wh.get(), hseq, ctx->trk_wx_wino,
-                               ctx->trk_wh_wino);
+                               ctx->trk_wh_wino, nullptr, carry);
     if (rc) return rc;
     float *trk = d_trk;
     if (!trk) {
@@ -1748,6 +1846,56 @@ extern "C" int dt_track_forward(dt_ctx *ctx, const void *d_frames, int frames_dt
         if (launch_copy_cols(ctx->stream, z + 1024, Cx, d_det, Cb, (long long)F * GG, Cb))
             return dt_fail(ctx, DT_ERR_DEVICE, "detection copy launch failed");
     }
+    return DT_OK;
+}
+
+// dt_track_forward on streams that carry their ConvLSTM state from call to call in the context's slots
+extern "C" int dt_track_stream_forward(dt_ctx *ctx, const void *d_frames, int frames_dtype, int n, int T, const int *h_slots,
+                                       float *d_trk, float *d_det)
+{
+    if (ctx) call_begin(ctx, n * T);
+    if (!ctx || !d_frames) return dt_fail(ctx, DT_ERR_ARG, "null argument");
+    if (!ctx->trk_loaded) return dt_fail(ctx, DT_ERR_STATE, "tracker weights not loaded");
+    if (n <= 0 || T <= 0) return dt_fail(ctx, DT_ERR_ARG, "n and T must be positive");
+    int rc = streams_check_list(ctx, h_slots, n);
+    if (rc) return rc;
+    StreamTable &S = ctx->streams;
+    const int gh = ctx->image_h / 32, gw = ctx->image_w / 32, GG = gh * gw;
+    const int F = n * T, Cx = ctx->trk_cx, Cb = ctx->cb;
+    if (S.row != GG * ctx->trk_units) return dt_fail(ctx, DT_ERR_STATE, "the stream table was opened for another model");
+    bool warm = false;
+    for (int i = 0; i < n; ++i) warm = warm || S.warm[h_slots[i]];
+    float *z = ws_get(ctx, "trk_z", (size_t)F * GG * Cx * sizeof(float), /*zero_on_grow=*/true);
+    if (!z) return DT_ERR_DEVICE;
+    rc = detect_internal(ctx, d_frames, frames_dtype, F, Dest{z, Cx}, Dest{z + 1024, Cx}, /*skip23=*/!d_det && xproj_merged(ctx, F, gh, gw));
+    if (rc) return rc;
+    // the slot list reaches the state moves through the library-owned device list: filled here, in stream order and outside the graph
+    if (launch_stream_slots(ctx->stream, h_slots, n, S.list.get(), nullptr)) return dt_fail(ctx, DT_ERR_DEVICE, "slot list launch failed");
+    rc = track_recurrent_internal(ctx, z, n, T, d_trk, warm ? CARRY_WARM : CARRY_FRESH);
+    if (rc) return rc;
+    for (int i = 0; i < n; ++i) S.warm[h_slots[i]] = 1;
+    if (d_det) {
+        ProfScope ps(ctx, "misc", 0.0, 8.0 * F * GG * (double)Cb);
+        if (launch_copy_cols(ctx->stream, z + 1024, Cx, d_det, Cb, (long long)F * GG, Cb))
+            return dt_fail(ctx, DT_ERR_DEVICE, "detection copy launch failed");
+    }
+    return DT_OK;
+}
+
+extern "C" int dt_associate_stream(dt_ctx *ctx, const float *d_boxes, const int *d_counts, int n, int T, int cap,
+                                   float assoc_threshold, const int *h_slots, int *d_ids, int *d_nids)
+{
+    if (!ctx || !d_boxes || !d_counts || !d_ids || !d_nids) return dt_fail(ctx, DT_ERR_ARG, "null argument");
+    if (n <= 0 || T <= 0) return dt_fail(ctx, DT_ERR_ARG, "n and T must be positive");
+    int rc = streams_check_list(ctx, h_slots, n);
+    if (rc) return rc;
+    StreamTable &S = ctx->streams;
+    if (cap != S.cap) return dt_fail(ctx, DT_ERR_ARG, "cap %d differs from the stream table's %d", cap, S.cap);
+    if (launch_stream_slots(ctx->stream, h_slots, n, S.list.get(), nullptr)) return dt_fail(ctx, DT_ERR_DEVICE, "slot list launch failed");
+    ProfScope ps(ctx, "associate", 0.0, 4.0 * n * (double)(T + 2) * cap * 9.0, "stream");
+    rc = launch_associate_stream(ctx->stream, d_boxes, d_counts, n, T, cap, assoc_threshold, d_ids, d_nids,
+                                 AssocCarry{S.list.get(), S.boxes.get(), S.ids.get(), S.meta.get()});
+    if (rc) return dt_fail(ctx, rc == 2 ? DT_ERR_ARG : DT_ERR_DEVICE, "associate launch failed");
     return DT_OK;
 }
 

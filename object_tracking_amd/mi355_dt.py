@@ -30,6 +30,7 @@ SYMBOLS = [
     "dt_packed_row_ints", "dt_pack_detections", "dt_unpack_detections",
     "dt_track_xproj_width", "dt_track_detect_xproj", "dt_track_recurrent_xproj",
     "dt_gemm_split_bf16", "dt_gemm_split", "dt_policy_set", "dt_amax_read",
+    "dt_stream_open", "dt_stream_reset", "dt_track_stream_forward", "dt_associate_stream",
 ]
 
 _lib = None
@@ -69,6 +70,10 @@ def load_library():
     L.dt_tracker_load.argtypes = [vp, ci, vp, vp, vp, vp, vp]
     L.dt_track_forward.argtypes = [vp, vp, ci, ci, ci, vp, vp]
     L.dt_associate.argtypes = [vp, vp, vp, ci, ci, ci, cf, vp, vp]
+    L.dt_stream_open.argtypes = [vp, ci, ci]
+    L.dt_stream_reset.argtypes = [vp, ctypes.POINTER(ci), ci]
+    L.dt_track_stream_forward.argtypes = [vp, vp, ci, ci, ci, ctypes.POINTER(ci), vp, vp]
+    L.dt_associate_stream.argtypes = [vp, vp, vp, ci, ci, ci, cf, ctypes.POINTER(ci), vp, vp]
     L.dt_track_row_width.argtypes = [vp]
     L.dt_track_detect.argtypes = [vp, vp, ci, ci, vp]
     L.dt_track_recurrent.argtypes = [vp, vp, ci, ci, vp, vp]
@@ -348,6 +353,60 @@ class Context(object):
         self._check(self.lib.dt_track_forward(self.h, _dptr(frames), self._frames_dtype(frames), n_clips, T,
                                               _dptr(trk), _dptr(det)), "dt_track_forward")
         return (trk, det) if want_det else trk
+
+    # ---- streaming: state carried across calls ---------------------------
+    @staticmethod
+    def _slot_array(slots):
+        """host list of slot numbers -> (n, ctypes int array)"""
+        slots = [int(v) for v in slots]
+        return len(slots), (ctypes.c_int * max(1, len(slots)))(*slots)
+
+    def stream_open(self, n_slots, cap):
+        """(re)allocate the stream slots, every one fresh; cap = box capacity of the association state"""
+        self._sync_stream()
+        self._check(self.lib.dt_stream_open(self.h, int(n_slots), int(cap)), "dt_stream_open")
+
+    def stream_reset(self, slots=None):
+        """the listed slots (None: all) fresh again: zero ConvLSTM state, track ids from 0"""
+        self._sync_stream()
+        if slots is None:
+            self._check(self.lib.dt_stream_reset(self.h, None, 0), "dt_stream_reset")
+        else:
+            n, arr = self._slot_array(slots)
+            self._check(self.lib.dt_stream_reset(self.h, arr, n), "dt_stream_reset")
+
+    def track_stream_forward(self, frames, slots, want_det=False):
+        """track_forward on frames [n,T,H,W,3] whose stream i continues from -- and leaves its ConvLSTM state in -- slot slots[i]."""
+        if frames is None:
+            raise NativeError("dt_track_stream_forward failed (1): null frames")
+        assert frames.is_cuda and frames.is_contiguous() and frames.dim() == 5
+        n, T = frames.shape[:2]
+        ns, arr = self._slot_array(slots)
+        if ns != n:
+            raise NativeError("dt_track_stream_forward failed (1): %d slots for %d streams" % (ns, n))
+        gh, gw = self.grid
+        trk = self._f32(n, T, gh, gw, self.nb_box, 5 + self.nb_class)
+        det = self._f32(n, T, gh, gw, self.nb_box, 5 + self.nb_class) if want_det else None
+        self._sync_stream()
+        self._check(self.lib.dt_track_stream_forward(self.h, _dptr(frames), self._frames_dtype(frames), n, T, arr,
+                                                     _dptr(trk), _dptr(det)), "dt_track_stream_forward")
+        return (trk, det) if want_det else trk
+
+    def associate_stream(self, boxes, counts, assoc_threshold, slots):
+        """associate on boxes [n,T,cap,8], counts [n,T]: frame 0 of stream i is matched against the last frame slot slots[i] saw,
+        ids continue across calls, nids [n] = ids opened by the stream since its reset."""
+        t = self.torch
+        assert boxes.is_cuda and boxes.is_contiguous() and counts.is_contiguous() and counts.dtype == t.int32
+        n, T, cap, _ = boxes.shape
+        ns, arr = self._slot_array(slots)
+        if ns != n:
+            raise NativeError("dt_associate_stream failed (1): %d slots for %d streams" % (ns, n))
+        ids = t.empty((n, T, cap), dtype=t.int32, device=self.device)
+        nids = t.empty((n,), dtype=t.int32, device=self.device)
+        self._sync_stream()
+        self._check(self.lib.dt_associate_stream(self.h, _dptr(boxes), _dptr(counts), n, T, cap, float(assoc_threshold),
+                                                 arr, _dptr(ids), _dptr(nids)), "dt_associate_stream")
+        return ids, nids
 
     def track_row_width(self):
         return int(self.lib.dt_track_row_width(self.h))

@@ -71,6 +71,9 @@ class NativeTrackerModel(object):
     def forward(self, frames, want_det=True):
         return self.ctx.track_forward(self.owner.detector.model.to_device(frames), want_det=want_det)
 
+    def forward_stream(self, frames, slots, want_det=False):
+        return self.ctx.track_stream_forward(self.owner.detector.model.to_device(frames), slots, want_det=want_det)
+
     def predict(self, inputs, batch_size=None):
         """Keras-style: [x (B,T,H,W,3), b] -> [tracking, detection] numpy grids
         (B,T,G,G,BOX,5+CLASS)  (MultiObjDetTracker.py:307)."""
@@ -193,6 +196,35 @@ class MultiObjDetTracker(object):
         One dt_track_forward (YOLOv2 x T, ConvLSTM recurrence, 1x1), one dt_decode
         over all frames, one dt_associate."""
         return self.decode_and_associate(self.model.forward(frames, want_det=False), cap=cap)
+
+    # ---- streaming (addition): ConvLSTM state and track ids carried across calls ----
+    def open_streams(self, n_slots, cap=None):
+        """Allocate n_slots stream slots on the device (every one fresh).  cap: box capacity per frame, as in track_clips."""
+        if cap is None:
+            cap = self.GRID_H * self.GRID_W * self.BOX
+        self.model.ctx.stream_open(n_slots, cap)
+        self._stream_cap = cap
+
+    def reset_streams(self, slots=None):
+        """The listed slots (None: all) start over: zero recurrent state, track ids from 0."""
+        self.model.ctx.stream_reset(slots)
+
+    def track_stream(self, frames, slots, cap=None):
+        """track_clips for live streams.  frames [n,T,H,W,3]: the next T frames of n streams, stream i living in slot slots[i]
+        (distinct numbers below open_streams' n_slots; see models_tracking/streams.py:StreamTable for a key -> slot map).
+        Returns the track_clips dict; a stream fed in chunks of any sizes gives what track_clips gives on the concatenation:
+        `ids` continue across calls and `nids` counts the ids a stream has opened since its reset."""
+        ctx = self.model.ctx
+        if cap is None:
+            cap = getattr(self, "_stream_cap", None) or self.GRID_H * self.GRID_W * self.BOX
+        trk = self.model.forward_stream(frames, slots, want_det=False)
+        n, T = trk.shape[:2]
+        flat = trk.reshape((n * T,) + tuple(trk.shape[2:]))
+        r = ctx.decode(flat, self.OBJ_THRESHOLD, self.NMS_THRESHOLD, self.ANCHORS, len(self.LABELS), cap=cap)
+        boxes = r["boxes"].reshape(n, T, cap, mi355_dt.DT_BOX_FLOATS)
+        counts = r["counts"].reshape(n, T)
+        ids, nids = ctx.associate_stream(boxes, counts, self.ASSOC_THRESHOLD, slots)
+        return dict(boxes=boxes, counts=counts, ids=ids, nids=nids, netout=trk)
 
     def decode_and_associate(self, trk, cap=None):
         """tracking grid [n_clips,T,G,G,BOX,5+C] (device) -> the track_clips result dict: one dt_decode over all frames
