@@ -531,11 +531,8 @@ struct dt_ctx {
     Policy pol;
     int pin_override = -1;   // dt_policy_set("pin"): 0 / 1 instead of DT_PIN, -1 = follow DT_PIN
     hipStream_t stream = nullptr;
-    int device_ok = 0;
     // detector
-    int image_h = 0, image_w = 0, nb_box = 0, nb_class = 0, cb = 0;
-    float anchors[64];
-    DevMem<float> anchors_dev;
+    int image_h = 0, image_w = 0, cb = 0;   // cb = nb_box * (5 + nb_class): channels of conv_23
     float dec_anchors_host[64];   // last anchors handed to dt_decode (persistent staging of the caller's host array)
     int dec_anchors_n = 0;
     bool det_loaded = false;
@@ -576,7 +573,6 @@ struct dt_ctx {
     // hipGraph replay of the launch-bound inner sequences (dt_graph_enable; network.hip:graphed)
     bool graph_on = false, capturing = false;
     hipStream_t gstream = nullptr;
-    hipEvent_t gev_in = nullptr, gev_out = nullptr;
     std::map<std::string, hipGraphExec_t> graphs;
     std::map<std::string, int> graph_seen;
     std::map<std::string, std::vector<AmaxTag>> graph_tags;   // amax_tag as a graphed sequence left it (re-applied on replay)

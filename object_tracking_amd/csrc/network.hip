@@ -100,11 +100,7 @@ static int graphed(dt_ctx *ctx, const std::string &key_in, const std::function<i
 extern "C" int dt_graph_enable(dt_ctx *ctx, int on)
 {
     if (!ctx) return DT_ERR_ARG;
-    if (on && !ctx->gstream) {
-        HIP_TRY(ctx, hipStreamCreateWithFlags(&ctx->gstream, hipStreamNonBlocking));
-        HIP_TRY(ctx, hipEventCreateWithFlags(&ctx->gev_in, hipEventDisableTiming));
-        HIP_TRY(ctx, hipEventCreateWithFlags(&ctx->gev_out, hipEventDisableTiming));
-    }
+    if (on && !ctx->gstream) HIP_TRY(ctx, hipStreamCreateWithFlags(&ctx->gstream, hipStreamNonBlocking));
     if (!on) graphs_clear(ctx);
     ctx->graph_on = on != 0;
     return DT_OK;
@@ -162,6 +158,19 @@ ProfScope::~ProfScope()
     (void)hipEventRecord(ev.b, ctx->stream);
     ctx->pending.push_back(ev);
 }
+// a counter without a time: which variant a launch took (the configuration parity tests assert these); the name is only built while profiling
+static void prof_count(dt_ctx *ctx, const char *fmt, ...)
+{
+    if (!ctx->prof || ctx->capturing) return;
+    char name[48];
+    va_list ap;
+    va_start(ap, fmt);
+    vsnprintf(name, sizeof(name), fmt, ap);
+    va_end(ap);
+    ctx->prof_tab[name].launches += 1;
+}
+// what a launcher's non-zero return code means: 2 = it refused the arguments, anything else = the device did
+static int launch_code(int rc) { return rc == 2 ? DT_ERR_ARG : DT_ERR_DEVICE; }
 
 // ---- max-|x| slots of the fp16 form (dt_internal.h: dt_ctx::amax) ------------------------------------------------------------------
 #define DT_AMAX_SLOTS 128
@@ -315,7 +324,6 @@ extern "C" int dt_create(dt_ctx **out)
         return dt_fail(nullptr, DT_ERR_DEVICE, "dt_create: device is %s; this library is built for gfx950 only",
                        prop.gcnArchName);
     dt_ctx *c = new dt_ctx();
-    c->device_ok = 1;
     policy_refresh(c);
     std::vector<float> lut(256);
     for (int i = 0; i < 256; ++i) lut[i] = (float)((double)i / 255.0);   // utils.py:150-153
@@ -346,7 +354,6 @@ extern "C" void dt_destroy(dt_ctx *ctx)
     for (auto &e : ctx->pending) { (void)hipEventDestroy(e.a); (void)hipEventDestroy(e.b); }
     if (ctx->gstream) {
         graphs_clear(ctx);
-        (void)hipEventDestroy(ctx->gev_in); (void)hipEventDestroy(ctx->gev_out);
         (void)hipStreamDestroy(ctx->gstream);
     }
     delete ctx;      // every weight buffer goes with its owner (DevMem)
@@ -462,13 +469,9 @@ extern "C" int dt_detector_config(dt_ctx *ctx, int image_h, int image_w, int nb_
     if (nb_box <= 0 || nb_box > 32 || nb_class <= 0 || !h_anchors)
         return dt_fail(ctx, DT_ERR_ARG, "bad nb_box/nb_class/anchors");
     ctx->image_h = image_h; ctx->image_w = image_w;
-    ctx->nb_box = nb_box; ctx->nb_class = nb_class;
     ctx->cb = nb_box * (5 + nb_class);
-    std::vector<float> a(h_anchors, h_anchors + 2 * nb_box);
-    memcpy(ctx->anchors, h_anchors, sizeof(float) * 2 * nb_box);
     ctx->det_loaded = false;
-    const int rc = streams_fresh(ctx);
-    return rc ? rc : upload(ctx, ctx->anchors_dev, a);
+    return streams_fresh(ctx);
 }
 
 // kernel in the darknet file is (O,I,H,W) (KerasYOLO.py:267-268 reshapes the
@@ -766,11 +769,11 @@ extern "C" int dt_load_darknet_weights(dt_ctx *ctx, const float *h_blob, size_t 
 // (wino_gemm_s3 launches), "conv_direct_form_fused" (the fused Winograd kernel) -- so that bench.py divides each family's
 // algorithmic work by that family's own time and no family is credited with work another kernel did.
 enum { DF_IGEMM = 0, DF_FUSED = 1, DF_S3 = 2, DF_CONV1 = 3, DF_C3H2 = 4 };
+static const char *const k_direct_form[] = {"conv_direct_form", "conv_direct_form_fused", "conv_direct_form_s3", "conv_direct_form_conv1", "conv_direct_form_c3h2"};
 static void prof_direct_form(dt_ctx *ctx, double flops, double bytes, int family = DF_IGEMM)
 {
     if (!ctx->prof) return;
-    ProfEntry &e = ctx->prof_tab[family == DF_FUSED ? "conv_direct_form_fused" : (family == DF_S3 ? "conv_direct_form_s3" : (family == DF_CONV1 ? "conv_direct_form_conv1" :
-                                 (family == DF_C3H2 ? "conv_direct_form_c3h2" : "conv_direct_form")))];
+    ProfEntry &e = ctx->prof_tab[k_direct_form[family]];
     e.flops += flops;
     e.bytes += bytes;   // in + weights + out of the reference's layer, float32
 }
@@ -863,7 +866,7 @@ struct WinoIO {
     const float *xproj; long long xp_bs; int xp_ld;   // gates variant (cstate != null)
     float *cstate; long long c_bs; int c_ld;
     const float *bias16;                              // border-aware bias [16][N] instead of `bias` (WinoArgs::bias16) or null
-    int amax_out_slot;                                // > 0: the output transform takes max |x| of what it stores into this slot (and the tensor is tagged with it)
+    unsigned *amax_out;                               // the output transform takes max |x| of what it stores into this slot, or null (the caller tags the tensor)
 };
 
 // Tile geometry of a Winograd launch.  Mosaic factor g: g x g frames with zero separators share one virtual image
@@ -888,40 +891,53 @@ static WinoGeom wino_geometry(const dt_ctx *ctx, int ts, int B, int H, int W, bo
     return q;
 }
 
-static int run_wino(dt_ctx *ctx, const WinoWeights &wts, const float *bias, int N, int B, int H,
-                    int W, const WinoIO &io, float slope, const char *tag, int cin_alg = 0 /* channels of the reference's layer when cin is padded */,
+// What a launch leaves behind, from its epilogue: the range(s) it overwrites (the pooled epilogues write a quarter of the pixels; the s2d epilogue a quarter with 4x
+// the row) -- amax_forget before the launch -- and among them the tensor the next layer reads, lo[next] with `cols` channels per pixel -- amax_note after a launch that
+// publishes: pooled where the epilogue pools (the unpooled twin of conv_13 feeds conv_21's fp32 kernel), 4 N channels per quarter-resolution pixel after space_to_depth.
+struct Leaves { const float *lo[2]; long long floats[2]; int next, cols; };
+static Leaves conv_leaves(int epi, const float *out, int out_ld, const float *out2, int out2_ld, long long M, int cout)
+{
+    return Leaves{{out, out2}, {(epi == EPI_POOL || epi == EPI_S2D ? M / 4 : M) * out_ld, out2 ? M / 4 * out2_ld : 0}, epi == EPI_POOL_BOTH ? 1 : 0,
+                  epi == EPI_S2D ? 4 * cout : cout};
+}
+static void amax_forget(dt_ctx *ctx, const Leaves &lv) { amax_forget(ctx, lv.lo[0], lv.floats[0]); amax_forget(ctx, lv.lo[1], lv.floats[1]); }
+static void amax_note(dt_ctx *ctx, const Leaves &lv, int slot) { amax_note(ctx, lv.lo[lv.next], lv.floats[lv.next], lv.cols, slot); }
+
+// The form of one Winograd launch: its tile geometry and the kernel its batched GEMMs take -- nt = 0: the fp32 MFMA kernel; 3 / 2: the split GEMM
+// (wino_gemm_s3.hip) with three bf16 / two fp16 terms per operand.  Decided here and nowhere else; run_wino launches what it is handed.
+struct WinoChoice { WinoGeom q; int nt; };
+static WinoChoice choose_wino(const dt_ctx *ctx, const WinoWeights &wts, int N, int B, int H, int W, bool pooled, bool gates)
+{
+    const int ts = wts.ts, cin = wts.cin;
+    WinoChoice c{wino_geometry(ctx, ts, B, H, W, pooled), 0};
+    // the GEMMs on the bf16 pipe with split operands (wino_gemm_s3.hip) where that form exists and wins: long K, enough rows
+    const bool rec = ts == 4 && gates;      // the recurrent step: F(4x4), gate update in the output transform
+    // (row thresholds: the fp16 form wins from far fewer rows than the bf16 form)
+    const bool h2_avail = h2_wanted(ctx) && wts.h2;
+    const int minrows = h2_avail ? ctx->pol.s3_minrows_h2 : ctx->pol.s3_minrows, rec_minrows = h2_avail ? ctx->pol.s3_rec_minrows_h2 : ctx->pol.s3_rec_minrows;
+    if (((ts == 6 && !gates) || rec) && ctx->pol.s3 != 0 && cin % 32 == 0 && N % 128 == 0 && wts.npad % 128 == 0 && wino_gemm_s3_usable(c.q.Mt, cin, N) &&
+        (ctx->pol.s3 == 2 || (cin >= S3_MINK && (rec ? (rec_minrows > 0 && c.q.Mt >= rec_minrows) : c.q.Mt >= minrows))) && wts.s3)
+        c.nt = h2_avail ? 2 : 3;      // ... in the fp16 form (two terms of scaled operands, three products) where its weights exist
+    return c;
+}
+static WinoChoice choose_wino(const dt_ctx *ctx, const WinoWeights &wts, int N, int B, int H, int W, const WinoIO &io) { return choose_wino(ctx, wts, N, B, H, W, io.out2 != nullptr, io.cstate != nullptr); }
+
+static int run_wino(dt_ctx *ctx, const WinoWeights &wts, const WinoChoice &wc, const float *bias, int N, int B, int H, int W, const WinoIO &io, float slope,
+                    const char *tag, int cin_alg = 0 /* channels of the reference's layer when cin is padded */,
                     int in_slot = AMAX_TEST /* max-|x| slot of the input tensor (fp16 form); AMAX_ONE: bounded by 1, nothing to measure */)
 {
     const int ts = wts.ts, cin = wts.cin, npad = wts.npad;
     const double cin_df = cin_alg > 0 ? cin_alg : cin;
-    if (io.out) amax_forget(ctx, io.out, (long long)B * H * W * io.out_ld);
-    if (io.out2) amax_forget(ctx, io.out2, (long long)B * H * W / 4 * io.out2_ld);
-    WinoArgs w;
-    memset(&w, 0, sizeof(w));
+    amax_forget(ctx, io.out ? conv_leaves(io.out2 ? EPI_POOL_BOTH : EPI_PLAIN, io.out, io.out_ld, io.out2, io.out2_ld, (long long)B * H * W, N)
+                            : conv_leaves(EPI_POOL, io.out2, io.out2_ld, nullptr, 0, (long long)B * H * W, N));
+    WinoArgs w{};
     w.B = B; w.H = H; w.W = W; w.ts = ts;
-    {
-        const WinoGeom q = wino_geometry(ctx, ts, B, H, W, io.out2 != nullptr);
-        w.g = q.g; w.th = q.th; w.tw = q.tw; w.Mt = q.Mt;
-    }
-    if (ctx->prof && !ctx->capturing) {   // which mosaic / tile size a launch took (asserted by the configuration parity tests)
-        char mtag[40];
-        snprintf(mtag, sizeof(mtag), "wino_mosaic:g%d_ts%d", w.g, ts);
-        ctx->prof_tab[mtag].launches += 1;
-    }
+    w.g = wc.q.g; w.th = wc.q.th; w.tw = wc.q.tw; w.Mt = wc.q.Mt;
+    prof_count(ctx, "wino_mosaic:g%d_ts%d", w.g, ts);   // which mosaic / tile size a launch took
     const int P = (ts + 2) * (ts + 2);
     const size_t mt = (size_t)w.Mt;
-    // the GEMMs on the bf16 pipe with split operands (wino_gemm_s3.hip) where that form exists and wins: long K, enough rows
-    const unsigned short *u_s3 = nullptr;
-    const bool rec = ts == 4 && io.cstate;      // the recurrent step: F(4x4), gate update in the output transform
-    // (row thresholds: the fp16 form wins from far fewer rows than the bf16 form)
-    const bool h2_avail = h2_wanted(ctx) && wts.h2;
-    const int minrows = h2_avail ? ctx->pol.s3_minrows_h2 : ctx->pol.s3_minrows, rec_minrows = h2_avail ? ctx->pol.s3_rec_minrows_h2 : ctx->pol.s3_rec_minrows;
-    if (((ts == 6 && !io.cstate) || rec) && ctx->pol.s3 != 0 && cin % 32 == 0 && N % 128 == 0 && npad % 128 == 0 && wino_gemm_s3_usable(w.Mt, cin, N) &&
-        (ctx->pol.s3 == 2 || (cin >= S3_MINK && (rec ? (rec_minrows > 0 && w.Mt >= rec_minrows) : w.Mt >= minrows))))
-        u_s3 = wts.s3.get();
-    // ... in the fp16 form (two terms of scaled operands, three products) where its weights exist
-    const bool h2 = u_s3 && h2_avail;
-    if (h2) u_s3 = wts.h2.get();
+    const bool h2 = wc.nt == 2;
+    const unsigned short *u_s3 = h2 ? wts.h2.get() : (wc.nt == 3 ? wts.s3.get() : nullptr);
     const int NT = h2 ? 2 : 3;
     const size_t mp = (mt + 255) / 256 * 256;
     float *V = ws_get(ctx, "wino_v", u_s3 ? (size_t)P * NT * mp * cin * sizeof(unsigned short) : P * mt * cin * sizeof(float));
@@ -942,26 +958,26 @@ static int run_wino(dt_ctx *ctx, const WinoWeights &wts, const float *bias, int 
     {
         ProfScope ps(ctx, "wino_input", 0.0, 4.0 * (double)B * H * W * cin + (u_s3 ? 2.0 * NT : 4.0) * (double)P * mt * cin, tag);
         const int rc = launch_wino_input(ctx->stream, w);
-        if (rc) return dt_fail(ctx, rc == 2 ? DT_ERR_ARG : DT_ERR_DEVICE, "%s: Winograd input transform launch failed", tag);
+        if (rc) return dt_fail(ctx, launch_code(rc), "%s: Winograd input transform launch failed", tag);
     }
+    // direct form of the same layer: in + weights + whatever the output transform writes
+    const double df_flops = 2.0 * B * H * W * 9.0 * cin_df * N;
+    const double df_bytes = 4.0 * ((double)B * H * W * cin_df + 9.0 * cin_df * N + (io.out ? (double)B * H * W * N : 0.0) +
+                                   (io.out2 ? (double)B * H * W * N / 4.0 : 0.0) + (io.cstate ? 4.0 * B * H * W * N / 4.0 : 0.0));
     if (u_s3) {
-        GemmS3Args g;
-        memset(&g, 0, sizeof(g));
+        GemmS3Args g{};
         g.a = w.v_s3; g.b = u_s3; g.c = Mp; g.c_ps = (long long)mt * N; g.P = P; g.Mt = w.Mt; g.Mp = (int)mp; g.N = N; g.Np = npad;
         g.K = cin; g.ldc = N; g.half = ctx->pol.s3_half;
         if (h2) { g.nt = 2; g.pscale = wts.h2_pscale.get(); g.amax = amax; }
         // flops = EXECUTED 16-bit MFMA work (six partial products per multiply, three in the fp16 form); bytes = V + U (NT 16-bit terms each) + M'
         ProfScope ps(ctx, "conv_gemm_s3", wino_gemm_s3_flops(g), (double)P * (2.0 * NT * mt * cin + 2.0 * NT * (double)cin * N + 4.0 * (double)mt * N), tag);
-        if (ctx->prof && !ctx->capturing) ctx->prof_tab[h2 ? "s3_form:f16x2" : "s3_form:bf16x3"].launches += 1;
-        prof_direct_form(ctx, 2.0 * B * H * W * 9.0 * cin_df * N,
-                         4.0 * ((double)B * H * W * cin_df + 9.0 * cin_df * N + (io.out ? (double)B * H * W * N : 0.0) +
-                                (io.out2 ? (double)B * H * W * N / 4.0 : 0.0) + (io.cstate ? 4.0 * B * H * W * N / 4.0 : 0.0)), DF_S3);
-        if (ctx->prof && !ctx->capturing) ctx->prof_tab[wino_gemm_s3_half_chosen(g, 0) ? "s3_tile:128x2" : "s3_tile:256"].launches += 1;
+        prof_count(ctx, h2 ? "s3_form:f16x2" : "s3_form:bf16x3");
+        prof_direct_form(ctx, df_flops, df_bytes, DF_S3);
+        if (ps.on) prof_count(ctx, wino_gemm_s3_half_chosen(g, 0) ? "s3_tile:128x2" : "s3_tile:256");
         const int rc = launch_wino_gemm_s3(ctx->stream, g, 0);
-        if (rc) return dt_fail(ctx, rc == 2 ? DT_ERR_ARG : DT_ERR_DEVICE, "%s: split-bf16 Winograd GEMM launch failed (rc=%d)", tag, rc);
+        if (rc) return dt_fail(ctx, launch_code(rc), "%s: split-bf16 Winograd GEMM launch failed (rc=%d)", tag, rc);
     } else {
-        ConvArgs a;
-        memset(&a, 0, sizeof(a));
+        ConvArgs a{};
         a.in = V; a.in_ld = cin; a.in_bs = (long long)mt * cin;
         a.wt = wts.u.get(); a.bias = nullptr;
         a.out = Mp; a.out_ld = N; a.out_bs = (long long)mt * N;
@@ -970,26 +986,19 @@ static int run_wino(dt_ctx *ctx, const WinoWeights &wts, const float *bias, int 
         a.zbatch = P; a.z_in = (long long)mt * cin; a.z_wt = (long long)npad * cin; a.z_out = (long long)mt * N;
         // flops = executed MFMA work of the P GEMMs (the direct form of the same layer is 9*ts*ts/P times
         // that on whole tiles: 4x for F(4x4,3x3), 2.25x for F(2x2,3x3)); bytes = V + U + M'
-        ProfScope ps(ctx, "conv_igemm", 2.0 * P * mt * (double)cin * N,
-                     4.0 * P * ((double)mt * cin + (double)cin * N + (double)mt * N), tag);
-        prof_direct_form(ctx, 2.0 * B * H * W * 9.0 * cin_df * N,
-                         4.0 * ((double)B * H * W * cin_df + 9.0 * cin_df * N + (io.out ? (double)B * H * W * N : 0.0) +
-                                (io.out2 ? (double)B * H * W * N / 4.0 : 0.0) + (io.cstate ? 4.0 * B * H * W * N / 4.0 : 0.0)));
+        ProfScope ps(ctx, "conv_igemm", 2.0 * P * mt * (double)cin * N, 4.0 * P * ((double)mt * cin + (double)cin * N + (double)mt * N), tag);
+        prof_direct_form(ctx, df_flops, df_bytes);
         const int rc = launch_igemm(ctx, a, 1, ORD_LINEAR, EPI_PLAIN, pick_cfg_gemm(w.Mt, N, P));
-        if (rc) return dt_fail(ctx, rc == 2 ? DT_ERR_ARG : DT_ERR_DEVICE, "%s: Winograd GEMM launch failed (rc=%d)", tag, rc);
+        if (rc) return dt_fail(ctx, launch_code(rc), "%s: Winograd GEMM launch failed (rc=%d)", tag, rc);
     }
     {
         const double outb = (io.out ? (double)B * H * W * N : 0.0) + (io.out2 ? (double)B * H * W * N / 4.0 : 0.0) +
                             (io.cstate ? 3.0 * B * H * W * N / 4.0 + (double)B * H * W * N : 0.0);
         ProfScope ps(ctx, "wino_output", 0.0, 4.0 * ((double)P * mt * N + outb), tag);
-        w.amax_out = io.amax_out_slot > 0 && h2_wanted(ctx) ? amax_slot(ctx, io.amax_out_slot) : nullptr;
-        if (!wino_output_fills_amax(w, io.cstate != nullptr)) w.amax_out = nullptr;
+        w.amax_out = io.amax_out;
+        if (!wino_output_fills_amax(w, io.cstate != nullptr)) w.amax_out = nullptr;      // (the gates transform cannot; choose_conv never asks it to)
         const int rc = launch_wino_output(ctx->stream, w, io.cstate != nullptr);
-        if (rc) return dt_fail(ctx, rc == 2 ? DT_ERR_ARG : DT_ERR_DEVICE, "%s: Winograd output transform launch failed", tag);
-        if (w.amax_out) {      // (the pooled tensor when there is one: its consumer is the next layer; the unpooled twin of conv_13 feeds conv_21's fp32 kernel)
-            if (io.out2) amax_note(ctx, io.out2, (long long)B * H * W / 4 * io.out2_ld, N, io.amax_out_slot);
-            else amax_note(ctx, io.out, (long long)B * H * W * io.out_ld, N, io.amax_out_slot);
-        }
+        if (rc) return dt_fail(ctx, launch_code(rc), "%s: Winograd output transform launch failed", tag);
     }
     return DT_OK;
 }
@@ -1026,180 +1035,219 @@ static bool s3_1x1_eligible(const dt_ctx *ctx, const ConvLayer &L, long long M)
            (ctx->pol.s3 == 2 || (L.cin >= S3_MINK && L.cin >= ctx->pol.s3_1x1_mink && M >= ctx->pol.s3_minrows && M >= ctx->pol.s3_1x1_minrows));
 }
 
-static int run_conv(dt_ctx *ctx, const ConvLayer &L, const float *in, int in_ld, int B, int H, int W, float *out,
-                    int out_ld, int order, int epi, float slope, float *out2 = nullptr, int out2_ld = 0)
+// Which kernel form a conv layer's launch takes: choose_conv is the one place that decides it (and choose_wino, above, for the Winograd GEMMs); whoever needs to know
+// what a launch WILL take -- conv_1 for conv_2's input slot, the conv_3 + conv_4 fusion -- asks it instead of restating its tests.  Both are pure: no launch, no
+// workspace, no tag, no profile entry.
+enum { CF_S3_1X1, CF_DIRECT_H2, CF_FUSED4, CF_WINO, CF_SPLITK, CF_IGEMM };
+struct ConvChoice {
+    int form;                  // split 1x1 GEMM / direct fp16-form 3x3 / fused F(4x4) / Winograd / fp32 MFMA kernel with split-K / fp32 MFMA kernel
+    bool h2;                   // CF_S3_1X1: the fp16 form of the split GEMM (CF_WINO: wino.nt says; CF_DIRECT_H2 has no other)
+    int cfg, ksplit;           // CF_SPLITK, CF_IGEMM: tile configuration; CF_SPLITK: the split count
+    const WinoWeights *wts; WinoChoice wino;      // CF_WINO: L.wino or L.wino_alt, and what its launch takes
+    bool publishes;            // the launch's epilogue takes max |x| of what it leaves for the next layer into the layer's output slot
+};
+static ConvChoice choose_conv(const dt_ctx *ctx, const ConvLayer &L, const float *in, int in_ld, int B, int H, int W, const float *out, int order, int epi, bool has_out2)
 {
-    {   // what this layer overwrites (the pooled epilogues write a quarter of the pixels; the s2d epilogue a quarter with 4x the row)
-        const long long pix = (long long)B * H * W;
-        amax_forget(ctx, out, (epi == EPI_POOL || epi == EPI_S2D ? pix / 4 : pix) * out_ld);
-        if (out2) amax_forget(ctx, out2, pix / 4 * out2_ld);
-    }
+    ConvChoice c{};
+    const bool plain = epi == EPI_PLAIN && order == ORD_LINEAR, pool_even = epi == EPI_POOL && !((H | W) & 1);
+    const long long blocks = (long long)B * ((H + 15) / 16) * ((W + 15) / 16) * ((L.cout + 127) / 128);      // workgroups of the direct and the fused kernel
     // (the split 1x1 form reads its A rows with 16-byte DMA pieces: a caller tensor at a 4 / 8 / 12-byte offset takes the fp32 kernel instead of failing)
-    if (L.bias_s3 && ctx->s3_ones && epi == EPI_PLAIN && order == ORD_LINEAR && !out2 && in_ld % 4 == 0 && (reinterpret_cast<uintptr_t>(in) & 15) == 0 &&
+    if (L.bias_s3 && ctx->s3_ones && plain && !has_out2 && in_ld % 4 == 0 && (reinterpret_cast<uintptr_t>(in) & 15) == 0 &&
         (reinterpret_cast<uintptr_t>(out) & 3) == 0 && s3_1x1_eligible(ctx, L, (long long)B * H * W)) {
-        const long long M = (long long)B * H * W;
-        const bool h2 = L.wt_h2 && L.pscale_h2 && L.npad <= 2048 && h2_wanted(ctx);
-        GemmS3Args g;
-        memset(&g, 0, sizeof(g));
-        g.a_f32 = in; g.a_ld = in_ld; g.b = L.wt_s3.get(); g.c = out; g.c_ps = 0; g.P = 1; g.Mt = (int)M; g.Mp = (int)((M + 255) / 256 * 256); g.N = L.cout; g.Np = L.npad;
-        g.half = ctx->pol.s3_half;
-        g.K = L.cin; g.ldc = out_ld; g.ones = reinterpret_cast<const unsigned short *>(ctx->s3_ones.get()); g.bias_s3 = L.bias_s3.get(); g.act = 1; g.slope = slope;
-        if (h2) {      // the fp16 form: scaled operands (the activation's power of two from its max |x|), the bias added in the epilogue
-            g.nt = 2; g.b = L.wt_h2.get(); g.pscale = L.pscale_h2.get(); g.bias = L.bias.get(); g.ones = nullptr; g.bias_s3 = nullptr;
-            g.amax = ensure_amax(ctx, in, M, L.cin, in_ld, amax_in_slot(L));
-            if (!g.amax) return DT_ERR_DEVICE;
-        }
-        char tag[32];
-        snprintf(tag, sizeof(tag), "conv_%d", L.idx);
-        if (h2_wanted(ctx) && amax_out_slot(L)) g.amax_out = amax_slot(ctx, amax_out_slot(L));
-        if (ctx->prof && !ctx->capturing) ctx->prof_tab[h2 ? "s3_form:f16x2" : "s3_form:bf16x3"].launches += 1;
-        // bytes = A (fp32) + U (NT 16-bit terms) + out
-        ProfScope ps(ctx, "conv_gemm_s3", wino_gemm_s3_flops(g), 4.0 * M * L.cin + (h2 ? 4.0 : 6.0) * (double)L.cin * L.cout + 4.0 * (double)M * L.cout, tag);
-        prof_direct_form(ctx, 2.0 * M * (double)L.cin * L.cout, 4.0 * ((double)M * L.cin + (double)L.cin * L.cout + (double)M * L.cout), DF_S3);
-        const int rc = launch_wino_gemm_s3(ctx->stream, g, 0);
-        if (rc) return dt_fail(ctx, rc == 2 ? DT_ERR_ARG : DT_ERR_DEVICE, "%s: split-bf16 1x1 GEMM launch failed (rc=%d)", tag, rc);
-        if (g.amax_out) amax_note(ctx, out, M * out_ld, L.cout, amax_out_slot(L));
-        return DT_OK;
+        c.form = CF_S3_1X1;
+        c.h2 = L.wt_h2 && L.pscale_h2 && L.npad <= 2048 && h2_wanted(ctx);
     }
-    ConvArgs a;
-    memset(&a, 0, sizeof(a));
-    a.in = in; a.in_ld = in_ld; a.in_bs = (long long)H * W * in_ld;
-    a.wt = L.wt.get(); a.bias = L.bias.get();
-    a.out = out; a.out_ld = out_ld; a.out_bs = (long long)H * W * out_ld;
-    a.out2 = out2; a.out2_ld = out2_ld;
-    a.B = B; a.H = H; a.W = W; a.Cin = L.cin; a.N = L.cout; a.M = B * H * W; a.K = L.ks * L.ks * L.cin;
-    a.npad = L.npad;
-    a.slope = slope;
-    int cfg = pick_cfg(a.M, L.cout, L.ks);
-    const double flops = 2.0 * a.M * (double)a.K * L.cout;
-    const double bytes = 4.0 * ((double)a.M * L.cin + (double)a.K * L.cout +
-                                (double)a.M * L.cout / (epi == EPI_POOL ? 4.0 : 1.0));
-    char tag[32];
-    snprintf(tag, sizeof(tag), L.idx == 102 ? "tconv_2" : "conv_%d", L.idx);
     // conv_2 / 3 / 5's shapes: the DIRECT convolution in the two-term fp16 form (conv3_h2.hip) once there are enough tiles to fill the chip
-    if (L.w3_h2 && L.pscale_w3 && ctx->pol.c3h2 != 0 && h2_wanted(ctx) && in_ld % 4 == 0 && (reinterpret_cast<uintptr_t>(in) & 15) == 0 &&
-        ((epi == EPI_PLAIN && order == ORD_LINEAR) || (epi == EPI_POOL && !((H | W) & 1)))) {
-        const long long blocks = (long long)B * ((H + 15) / 16) * ((W + 15) / 16) * ((L.cout + 127) / 128);
-        if (ctx->pol.c3h2 == 2 || blocks >= C3H2_MIN_BLOCKS) {
-            Conv3H2Args c;
-            memset(&c, 0, sizeof(c));
-            c.in = in; c.in_bs = a.in_bs; c.in_ld = in_ld; c.B = B; c.H = H; c.W = W; c.Cin = L.cin; c.N = L.cout; c.Np = L.npad;
-            c.w = L.w3_h2.get(); c.pscale = L.pscale_w3.get(); c.bias = L.bias.get(); c.slope = slope;
-            if (epi == EPI_POOL) { c.out2 = out; c.out2_ld = out_ld; }
-            else { c.out = out; c.out_ld = out_ld; c.out_bs = a.out_bs; }
-            c.zeros = ws_get(ctx, "zeros256", 256, /*zero_on_grow=*/true);
-            if (!c.zeros) return DT_ERR_DEVICE;
-            c.amax = ensure_amax(ctx, in, (long long)B * H * W, L.cin, in_ld, amax_in_slot(L));
-            if (!c.amax) return DT_ERR_DEVICE;
-            if (amax_out_slot(L)) c.amax_out = amax_slot(ctx, amax_out_slot(L));
-            // executed fp16 MFMA FLOPs (three products per multiply, whole tiles); bytes: the input once per channel tile (+ halo 27 / 41 %) and the output
-            ProfScope ps(ctx, "conv_direct_h2", conv3_h2_flops(c),
-                         4.0 * ((double)B * H * W * L.cin * (L.cout % 128 ? 1.27 : 1.41) * ((L.cout + 127) / 128) + (double)a.M * L.cout / (epi == EPI_POOL ? 4.0 : 1.0)), tag);
-            prof_direct_form(ctx, flops, bytes, DF_C3H2);
-            const int rc = launch_conv3_h2(ctx->stream, c);
-            if (rc) return dt_fail(ctx, rc == 2 ? DT_ERR_ARG : DT_ERR_DEVICE, "%s: direct fp16-form 3x3 launch failed", tag);
-            if (c.amax_out) amax_note(ctx, out, (long long)a.M / (epi == EPI_POOL ? 4 : 1) * out_ld, L.cout, amax_out_slot(L));
-            return DT_OK;
-        }
-    }
+    else if (L.w3_h2 && L.pscale_w3 && ctx->pol.c3h2 != 0 && h2_wanted(ctx) && in_ld % 4 == 0 && (reinterpret_cast<uintptr_t>(in) & 15) == 0 && (plain || pool_even) &&
+             (ctx->pol.c3h2 == 2 || blocks >= C3H2_MIN_BLOCKS))
+        c.form = CF_DIRECT_H2;
     // conv_2 / 3 / 5 (6 / 8)'s shapes: the fused F(4x4,3x3) kernel (V and M' stay on the CU) once there are enough 16x16-pixel
     // blocks to fill the chip several times over; below that the unfused forms win (few, half-empty workgroups)
-    if (L.fused4s && ctx->pol.fused4 != 0 && in_ld % 4 == 0 && ((epi == EPI_PLAIN && order == ORD_LINEAR) || (epi == EPI_POOL && !((H | W) & 1)))) {
-        const long long blocks = (long long)B * ((H + 15) / 16) * ((W + 15) / 16) * ((L.cout + 127) / 128);
-        if (ctx->pol.fused4 == 2 || (((ctx->pol.fused4 == 1 && L.cin <= 64) || ctx->pol.fused4 == 3) && blocks >= 1024)) {
-            Wino4FusedArgs f;
-            memset(&f, 0, sizeof(f));
-            f.in = in; f.in_bs = a.in_bs; f.in_ld = in_ld; f.B = B; f.H = H; f.W = W; f.Cin = L.cin; f.N = L.cout;
-            f.u = L.fused4s.get(); f.bias = L.bias.get(); f.slope = slope;
-            if (epi == EPI_POOL) { f.out2 = out; f.out2_ld = out_ld; }
-            else { f.out = out; f.out_ld = out_ld; f.out_bs = a.out_bs; }
-            // executed MFMA FLOPs: 36 positions x (whole 4x4 tiles) x Cin x N x 2; bytes: input once per 128 output channels (+ halo 27 %) and the output
-            const double tiles = (double)B * ((H + 3) / 4) * ((W + 3) / 4);
-            ProfScope ps(ctx, "conv_fused", 2.0 * 36.0 * tiles * L.cin * L.cout,
-                         4.0 * ((double)B * H * W * L.cin * 1.27 * ((L.cout + 127) / 128) + (double)a.M * L.cout / (epi == EPI_POOL ? 4.0 : 1.0)), tag);
-            prof_direct_form(ctx, flops, bytes, DF_FUSED);
-            float *zeros = ws_get(ctx, "zeros256", 256, /*zero_on_grow=*/true);
-            if (!zeros) return DT_ERR_DEVICE;
-            if (h2_wanted(ctx) && amax_out_slot(L)) f.amax_out = amax_slot(ctx, amax_out_slot(L));
-            const int rc = launch_wino4s_fused(ctx->stream, f, zeros);
-            if (rc) return dt_fail(ctx, rc == 2 ? DT_ERR_ARG : DT_ERR_DEVICE, "%s: fused F(4x4) launch failed", tag);
-            if (f.amax_out) amax_note(ctx, out, (long long)a.M / (epi == EPI_POOL ? 4 : 1) * out_ld, L.cout, amax_out_slot(L));
-            return DT_OK;
-        }
-    }
-    if (wino_runs(ctx, L.wino, B, H, W, L.cout) && ((epi == EPI_PLAIN && order == ORD_LINEAR) || epi == EPI_POOL || epi == EPI_POOL_BOTH)) {
-        WinoIO io;
-        memset(&io, 0, sizeof(io));
-        io.in = in; io.in_ld = in_ld; io.in_bs = a.in_bs;
-        if (epi == EPI_POOL) { io.out2 = out; io.out2_ld = out_ld; }
-        else { io.out = out; io.out_ld = out_ld; io.out_bs = a.out_bs; io.out2 = out2; io.out2_ld = out2_ld; }
-        io.amax_out_slot = amax_out_slot(L);
+    else if (L.fused4s && ctx->pol.fused4 != 0 && in_ld % 4 == 0 && (plain || pool_even) &&
+             (ctx->pol.fused4 == 2 || (((ctx->pol.fused4 == 1 && L.cin <= 64) || ctx->pol.fused4 == 3) && blocks >= 1024)))
+        c.form = CF_FUSED4;
+    else if (wino_runs(ctx, L.wino, B, H, W, L.cout) && (plain || epi == EPI_POOL || epi == EPI_POOL_BOTH)) {
+        const bool pooled = epi == EPI_POOL || has_out2;
+        c.form = CF_WINO; c.wts = &L.wino;
+        c.wino = choose_wino(ctx, L.wino, L.cout, B, H, W, pooled, false);
         // F(6x6) or F(4x4) for this launch: with many tiles F(6x6)'s fewer multiplies win; with a few frames the choice
         // is about how the positions x row tiles x column tiles spread over the CUs (small_gemm_cost)
-        const WinoWeights *wts = &L.wino;
         if (L.wino_alt.u && !ctx->pol.pin) {
-            const bool pooled = io.out2 != nullptr;
-            const WinoGeom q6 = wino_geometry(ctx, 6, B, H, W, pooled), q4 = wino_geometry(ctx, 4, B, H, W, pooled);
-            const long long t6 = 64ll * ((q6.Mt + 127) / 128) * ((L.cout + 127) / 128);
-            // (the cost model prices the fp32 MFMA kernel's tiles: where the F(6x6) launch takes the split GEMM in the fp16 form -- run_wino's own test -- F(4x4) on the
+            const WinoChoice alt = choose_wino(ctx, L.wino_alt, L.cout, B, H, W, pooled, false);
+            const long long t6 = 64ll * ((c.wino.q.Mt + 127) / 128) * ((L.cout + 127) / 128);
+            // (the cost model prices the fp32 MFMA kernel's tiles: where the F(6x6) launch takes the split GEMM in the fp16 form -- choose_wino's answer -- F(4x4) on the
             //  fp32 kernel is no alternative: at 20 frames it cost the 13x13 layers 0.10-0.24 ms each against 0.05-0.11 on the split kernel)
-            const bool s3_h2_takes_it = ctx->pol.s3 != 0 && h2_wanted(ctx) && L.wino.h2 && L.cin % 32 == 0 && L.cout % 128 == 0 &&
-                                        L.npad % 128 == 0 && (ctx->pol.s3 == 2 || (L.cin >= S3_MINK && q6.Mt >= ctx->pol.s3_minrows_h2));
-            if (!s3_h2_takes_it && t6 <= 4096 && small_gemm_cost(q4.Mt, L.cout, 36, nullptr) < small_gemm_cost(q6.Mt, L.cout, 64, nullptr)) wts = &L.wino_alt;
-        }
-        return run_wino(ctx, *wts, L.bias.get(), L.cout, B, H, W, io, slope, tag, 0, amax_in_slot(L));
-    }
-    // Wave quantisation for small batches (few frames at 13x13 / 26x26): with 512 resident
-    // workgroup slots (256 CUs x 2) a layer of a few hundred output tiles leaves the chip
-    // partly idle or spills a nearly empty last round.  Split K over grid.y into a slab and
-    // combine deterministically; the split count minimises a simple round model
-    //   time(s) ~ rounds(tiles*s) / s + 0.003*s,  rounds(n) = full rounds + cost of the partial one
-    // (a half-empty round still costs ~0.6 of a full one: single workgroups per CU run faster).
-    prof_direct_form(ctx, flops, bytes);
-    int ksplit = 1;
-    if (epi == EPI_PLAIN && order == ORD_LINEAR && cfg != CFG_128x64) {
-        const int tiles = ((a.M + 127) / 128) * ((L.cout + 127) / 128);
-        const int nk = a.K / 32;
-        if (tiles < 2 * 512 && !ctx->pol.pin) {      // (DT_PIN: no split-K -- the split count would depend on the batch)
-            int smax = nk / 6;                           // keep >= 6 chunks (192 of K) per split
-            if (smax > 32) smax = 32;
-            double best = 1e30;
-            for (int sp = 1; sp <= (smax < 1 ? 1 : smax); ++sp) {
-                const int n = tiles * sp, full = n / 512, part = n % 512;
-                const double rounds = full + (part == 0 ? 0.0 : (part <= 256 ? 0.6 : 0.6 + 0.4 * (part - 256) / 256.0));
-                const double t = rounds / sp + 0.003 * sp;   // + slab write/read and combine launch per split
-                if (t < best - 1e-9) { best = t; ksplit = sp; }
+            if (c.wino.nt != 2 && t6 <= 4096 && small_gemm_cost(alt.q.Mt, L.cout, 36, nullptr) < small_gemm_cost(c.wino.q.Mt, L.cout, 64, nullptr)) {
+                c.wts = &L.wino_alt; c.wino = alt;
             }
         }
-        if (ksplit > 1) cfg = CFG_128x128;   // the split-K path is built for the 128x128 tile
+    } else {
+        // Wave quantisation for small batches (few frames at 13x13 / 26x26): with 512 resident
+        // workgroup slots (256 CUs x 2) a layer of a few hundred output tiles leaves the chip
+        // partly idle or spills a nearly empty last round.  Split K over grid.y into a slab and
+        // combine deterministically; the split count minimises a simple round model
+        //   time(s) ~ rounds(tiles*s) / s + 0.003*s,  rounds(n) = full rounds + cost of the partial one
+        // (a half-empty round still costs ~0.6 of a full one: single workgroups per CU run faster).
+        const int M = B * H * W;
+        c.form = CF_IGEMM; c.ksplit = 1;
+        c.cfg = pick_cfg(M, L.cout, L.ks);
+        if (plain && c.cfg != CFG_128x64) {
+            const int tiles = ((M + 127) / 128) * ((L.cout + 127) / 128), nk = L.ks * L.ks * L.cin / 32;
+            if (tiles < 2 * 512 && !ctx->pol.pin) {      // (DT_PIN: no split-K -- the split count would depend on the batch)
+                int smax = nk / 6;                           // keep >= 6 chunks (192 of K) per split
+                if (smax > 32) smax = 32;
+                double best = 1e30;
+                for (int sp = 1; sp <= (smax < 1 ? 1 : smax); ++sp) {
+                    const int n = tiles * sp, full = n / 512, part = n % 512;
+                    const double rounds = full + (part == 0 ? 0.0 : (part <= 256 ? 0.6 : 0.6 + 0.4 * (part - 256) / 256.0));
+                    const double t = rounds / sp + 0.003 * sp;   // + slab write/read and combine launch per split
+                    if (t < best - 1e-9) { best = t; c.ksplit = sp; }
+                }
+            }
+            if (c.ksplit > 1) { c.form = CF_SPLITK; c.cfg = CFG_128x128; }   // the split-K path is built for the 128x128 tile
+        }
     }
+    // publication: wanted, the layer has an output slot, and this form's epilogue can -- split-K's reduce cannot, the fp32 MFMA kernel for these epilogues
+    const bool can = c.form != CF_SPLITK && (c.form != CF_IGEMM || epi == EPI_PLAIN || epi == EPI_POOL || epi == EPI_POOL_BOTH || epi == EPI_S2D);
+    c.publishes = h2_wanted(ctx) && amax_out_slot(L) && can;
+    return c;
+}
+
+// one run_conv call as the function of its form sees it; flops / bytes: the direct form of the layer (3x3 and fp32-kernel forms)
+struct ConvCall {
+    const ConvLayer &L; const float *in; int in_ld, B, H, W; float *out; int out_ld, order, epi; float slope; float *out2; int out2_ld;
+    const char *tag; unsigned *amax_out; int M; double flops, bytes;
+};
+
+static int conv_s3_1x1(dt_ctx *ctx, const ConvCall &c, bool h2)
+{
+    const ConvLayer &L = c.L;
+    const long long M = (long long)c.B * c.H * c.W;
+    GemmS3Args g{};
+    g.a_f32 = c.in; g.a_ld = c.in_ld; g.b = L.wt_s3.get(); g.c = c.out; g.c_ps = 0; g.P = 1; g.Mt = (int)M; g.Mp = (int)((M + 255) / 256 * 256); g.N = L.cout; g.Np = L.npad;
+    g.half = ctx->pol.s3_half; g.K = L.cin; g.ldc = c.out_ld; g.ones = reinterpret_cast<const unsigned short *>(ctx->s3_ones.get()); g.bias_s3 = L.bias_s3.get(); g.act = 1; g.slope = c.slope;
+    if (h2) {      // the fp16 form: scaled operands (the activation's power of two from its max |x|), the bias added in the epilogue
+        g.nt = 2; g.b = L.wt_h2.get(); g.pscale = L.pscale_h2.get(); g.bias = L.bias.get(); g.ones = nullptr; g.bias_s3 = nullptr;
+        g.amax = ensure_amax(ctx, c.in, M, L.cin, c.in_ld, amax_in_slot(L));
+        if (!g.amax) return DT_ERR_DEVICE;
+    }
+    g.amax_out = c.amax_out;
+    prof_count(ctx, h2 ? "s3_form:f16x2" : "s3_form:bf16x3");
+    // bytes = A (fp32) + U (NT 16-bit terms) + out
+    ProfScope ps(ctx, "conv_gemm_s3", wino_gemm_s3_flops(g), 4.0 * M * L.cin + (h2 ? 4.0 : 6.0) * (double)L.cin * L.cout + 4.0 * (double)M * L.cout, c.tag);
+    prof_direct_form(ctx, 2.0 * M * (double)L.cin * L.cout, 4.0 * ((double)M * L.cin + (double)L.cin * L.cout + (double)M * L.cout), DF_S3);
+    const int rc = launch_wino_gemm_s3(ctx->stream, g, 0);
+    return rc ? dt_fail(ctx, launch_code(rc), "%s: split-bf16 1x1 GEMM launch failed (rc=%d)", c.tag, rc) : DT_OK;
+}
+// L4: the 1x1 layer applied behind this one in the same launch (conv3_h2.hip's FUSE instance; c.out takes ITS output), or null
+static int conv_direct_h2(dt_ctx *ctx, const ConvCall &c, const ConvLayer *L4 = nullptr)
+{
+    const ConvLayer &L = c.L;
+    Conv3H2Args a{};
+    a.in = c.in; a.in_bs = (long long)c.H * c.W * c.in_ld; a.in_ld = c.in_ld; a.B = c.B; a.H = c.H; a.W = c.W; a.Cin = L.cin; a.N = L.cout; a.Np = L.npad;
+    a.w = L.w3_h2.get(); a.pscale = L.pscale_w3.get(); a.bias = L.bias.get(); a.slope = c.slope;
+    if (L4) { a.w1 = L4->wt_h2.get(); a.pscale1 = L4->pscale_h2.get(); a.bias1 = L4->bias.get(); a.N1 = L4->cout; a.Np1 = L4->npad; a.slope1 = c.slope; }
+    if (c.epi == EPI_POOL) { a.out2 = c.out; a.out2_ld = c.out_ld; }
+    else { a.out = c.out; a.out_ld = c.out_ld; a.out_bs = (long long)c.H * c.W * c.out_ld; }
+    a.zeros = ws_get(ctx, "zeros256", 256, /*zero_on_grow=*/true);
+    if (!a.zeros) return DT_ERR_DEVICE;
+    a.amax = ensure_amax(ctx, c.in, (long long)c.B * c.H * c.W, L.cin, c.in_ld, amax_in_slot(L));
+    if (!a.amax) return DT_ERR_DEVICE;
+    a.amax_out = c.amax_out;
+    if (L4) prof_count(ctx, "conv_direct_h2:fused_1x1");
+    const double M = c.M;
+    // executed fp16 MFMA FLOPs (three products per multiply, whole tiles); bytes: the input once per channel tile (+ halo 27 / 41 %) and the output (fused: conv_4's)
+    ProfScope ps(ctx, "conv_direct_h2", conv3_h2_flops(a),
+                 L4 ? 4.0 * (M * L.cin * 1.41 + M * L4->cout)
+                    : 4.0 * ((double)c.B * c.H * c.W * L.cin * (L.cout % 128 ? 1.27 : 1.41) * ((L.cout + 127) / 128) + M * L.cout / (c.epi == EPI_POOL ? 4.0 : 1.0)), c.tag);
+    if (L4)      // direct form: both layers
+        prof_direct_form(ctx, 2.0 * M * (9.0 * L.cin * L.cout + (double)L4->cin * L4->cout),
+                         4.0 * (M * L.cin + 9.0 * L.cin * L.cout + 2.0 * M * L.cout + (double)L4->cin * L4->cout + M * L4->cout), DF_C3H2);
+    else prof_direct_form(ctx, c.flops, c.bytes, DF_C3H2);
+    const int rc = launch_conv3_h2(ctx->stream, a);
+    return rc ? dt_fail(ctx, launch_code(rc), L4 ? "%s: fused direct 3x3 + 1x1 launch failed" : "%s: direct fp16-form 3x3 launch failed", c.tag) : DT_OK;
+}
+static int conv_fused4(dt_ctx *ctx, const ConvCall &c)
+{
+    const ConvLayer &L = c.L;
+    Wino4FusedArgs f{};
+    f.in = c.in; f.in_bs = (long long)c.H * c.W * c.in_ld; f.in_ld = c.in_ld; f.B = c.B; f.H = c.H; f.W = c.W; f.Cin = L.cin; f.N = L.cout;
+    f.u = L.fused4s.get(); f.bias = L.bias.get(); f.slope = c.slope;
+    if (c.epi == EPI_POOL) { f.out2 = c.out; f.out2_ld = c.out_ld; }
+    else { f.out = c.out; f.out_ld = c.out_ld; f.out_bs = (long long)c.H * c.W * c.out_ld; }
+    // executed MFMA FLOPs: 36 positions x (whole 4x4 tiles) x Cin x N x 2; bytes: input once per 128 output channels (+ halo 27 %) and the output
+    const double tiles = (double)c.B * ((c.H + 3) / 4) * ((c.W + 3) / 4);
+    ProfScope ps(ctx, "conv_fused", 2.0 * 36.0 * tiles * L.cin * L.cout,
+                 4.0 * ((double)c.B * c.H * c.W * L.cin * 1.27 * ((L.cout + 127) / 128) + (double)c.M * L.cout / (c.epi == EPI_POOL ? 4.0 : 1.0)), c.tag);
+    prof_direct_form(ctx, c.flops, c.bytes, DF_FUSED);
+    float *zeros = ws_get(ctx, "zeros256", 256, /*zero_on_grow=*/true);
+    if (!zeros) return DT_ERR_DEVICE;
+    f.amax_out = c.amax_out;
+    const int rc = launch_wino4s_fused(ctx->stream, f, zeros);
+    return rc ? dt_fail(ctx, launch_code(rc), "%s: fused F(4x4) launch failed", c.tag) : DT_OK;
+}
+static int conv_wino(dt_ctx *ctx, const ConvCall &c, const WinoWeights &wts, const WinoChoice &wc)
+{
+    WinoIO io{};
+    io.in = c.in; io.in_ld = c.in_ld; io.in_bs = (long long)c.H * c.W * c.in_ld;
+    if (c.epi == EPI_POOL) { io.out2 = c.out; io.out2_ld = c.out_ld; }
+    else { io.out = c.out; io.out_ld = c.out_ld; io.out_bs = (long long)c.H * c.W * c.out_ld; io.out2 = c.out2; io.out2_ld = c.out2_ld; }
+    io.amax_out = c.amax_out;
+    return run_wino(ctx, wts, wc, c.L.bias.get(), c.L.cout, c.B, c.H, c.W, io, c.slope, c.tag, 0, amax_in_slot(c.L));
+}
+// the fp32 MFMA kernel (conv_igemm.hip), whole K per tile or split over ksplit slabs and reduced
+static int conv_igemm(dt_ctx *ctx, const ConvCall &c, int cfg, int ksplit)
+{
+    const ConvLayer &L = c.L;
+    ConvArgs a{};
+    a.in = c.in; a.in_ld = c.in_ld; a.in_bs = (long long)c.H * c.W * c.in_ld;
+    a.wt = L.wt.get(); a.bias = L.bias.get();
+    a.out = c.out; a.out_ld = c.out_ld; a.out_bs = (long long)c.H * c.W * c.out_ld;
+    a.out2 = c.out2; a.out2_ld = c.out2_ld; a.npad = L.npad; a.slope = c.slope;
+    a.B = c.B; a.H = c.H; a.W = c.W; a.Cin = L.cin; a.N = L.cout; a.M = c.M; a.K = L.ks * L.ks * L.cin;
+    prof_direct_form(ctx, c.flops, c.bytes);
     if (ksplit > 1) {
         float *slab = ws_get(ctx, "splitk", (size_t)ksplit * a.M * L.cout * sizeof(float));
         if (!slab) return DT_ERR_DEVICE;
         ConvArgs b = a;
         b.out = slab; b.out_ld = L.cout; b.ksplit = ksplit; b.bias = nullptr;
         {
-            ProfScope ps(ctx, "conv_igemm", flops, bytes + 4.0 * ksplit * a.M * (double)L.cout, tag);
-            const int rc = launch_igemm(ctx, b, L.ks, ORD_LINEAR, EPI_PARTIAL, CFG_128x128);
-            if (rc) return dt_fail(ctx, rc == 2 ? DT_ERR_ARG : DT_ERR_DEVICE, "conv_%d split-K launch failed (rc=%d)", L.idx, rc);
+            ProfScope ps(ctx, "conv_igemm", c.flops, c.bytes + 4.0 * ksplit * a.M * (double)L.cout, c.tag);
+            const int rc = launch_igemm(ctx, b, L.ks, ORD_LINEAR, EPI_PARTIAL, cfg);
+            if (rc) return dt_fail(ctx, launch_code(rc), "conv_%d split-K launch failed (rc=%d)", L.idx, rc);
         }
-        ProfScope ps2(ctx, "splitk_reduce", 0.0, 4.0 * (ksplit + 1.0) * a.M * (double)L.cout, tag);
-        if (launch_splitk_reduce(ctx->stream, slab, ksplit, a.M, L.cout, L.bias.get(), slope, out, out_ld))
+        ProfScope ps2(ctx, "splitk_reduce", 0.0, 4.0 * (ksplit + 1.0) * a.M * (double)L.cout, c.tag);
+        if (launch_splitk_reduce(ctx->stream, slab, ksplit, a.M, L.cout, L.bias.get(), c.slope, c.out, c.out_ld))
             return dt_fail(ctx, DT_ERR_DEVICE, "conv_%d split-K reduce launch failed", L.idx);
         return DT_OK;
     }
-    ProfScope ps(ctx, "conv_igemm", flops, bytes, tag);
-    const bool am_epi = epi == EPI_PLAIN || epi == EPI_POOL || epi == EPI_POOL_BOTH || epi == EPI_S2D;
-    if (am_epi && h2_wanted(ctx) && amax_out_slot(L)) a.amax_out = amax_slot(ctx, amax_out_slot(L));
-    const int rc = launch_igemm(ctx, a, L.ks, order, epi, cfg);
-    if (rc) return dt_fail(ctx, rc == 2 ? DT_ERR_ARG : DT_ERR_DEVICE, "conv_%d launch failed (rc=%d)", L.idx, rc);
-    if (a.amax_out) {      // the tensor the next layer reads: pooled where the epilogue pools, 4 N channels per quarter-resolution pixel after space_to_depth
-        if (epi == EPI_POOL_BOTH) amax_note(ctx, out2, (long long)a.M / 4 * out2_ld, L.cout, amax_out_slot(L));
-        else if (epi == EPI_POOL) amax_note(ctx, out, (long long)a.M / 4 * out_ld, L.cout, amax_out_slot(L));
-        else if (epi == EPI_S2D) amax_note(ctx, out, (long long)a.M / 4 * out_ld, 4 * L.cout, amax_out_slot(L));
-        else amax_note(ctx, out, (long long)a.M * out_ld, L.cout, amax_out_slot(L));
+    ProfScope ps(ctx, "conv_igemm", c.flops, c.bytes, c.tag);
+    a.amax_out = c.amax_out;
+    const int rc = launch_igemm(ctx, a, L.ks, c.order, c.epi, cfg);
+    return rc ? dt_fail(ctx, launch_code(rc), "conv_%d launch failed (rc=%d)", L.idx, rc) : DT_OK;
+}
+
+static int run_conv(dt_ctx *ctx, const ConvLayer &L, const float *in, int in_ld, int B, int H, int W, float *out, int out_ld, int order, int epi, float slope,
+                    float *out2 = nullptr, int out2_ld = 0)
+{
+    const Leaves lv = conv_leaves(epi, out, out_ld, out2, out2_ld, (long long)B * H * W, L.cout);
+    amax_forget(ctx, lv);
+    const ConvChoice ch = choose_conv(ctx, L, in, in_ld, B, H, W, out, order, epi, out2 != nullptr);
+    const int M = B * H * W, K = L.ks * L.ks * L.cin;
+    char tag[32];
+    snprintf(tag, sizeof(tag), L.idx == 102 ? "tconv_2" : "conv_%d", L.idx);
+    const ConvCall c{L, in, in_ld, B, H, W, out, out_ld, order, epi, slope, out2, out2_ld, tag, ch.publishes ? amax_slot(ctx, amax_out_slot(L)) : nullptr, M,
+                     2.0 * M * (double)K * L.cout, 4.0 * ((double)M * L.cin + (double)K * L.cout + (double)M * L.cout / (epi == EPI_POOL ? 4.0 : 1.0))};
+    int rc = DT_ERR_STATE;
+    switch (ch.form) {
+    case CF_S3_1X1: rc = conv_s3_1x1(ctx, c, ch.h2); break;
+    case CF_DIRECT_H2: rc = conv_direct_h2(ctx, c); break;
+    case CF_FUSED4: rc = conv_fused4(ctx, c); break;
+    case CF_WINO: rc = conv_wino(ctx, c, *ch.wts, ch.wino); break;
+    case CF_SPLITK: case CF_IGEMM: rc = conv_igemm(ctx, c, ch.cfg, ch.ksplit); break;
     }
-    return DT_OK;
+    if (rc == DT_OK && c.amax_out) amax_note(ctx, lv, amax_out_slot(L));      // the tensor the next layer reads now has its max |x| in the layer's slot
+    return rc;
 }
 
 // What dt_detector_extract wants out of the graph: the output of layer `idx` in one of the forms the reference's
@@ -1228,39 +1276,22 @@ static int extract_layer(dt_ctx *ctx, const ConvLayer &L, const float *in, int i
 }
 
 // conv_3 and the 1x1 conv_4 behind it as ONE launch of conv3_h2.hip (its FUSE instance: the 128-channel tensor between them never exists): where
-// conv_3 would take the direct fp16-form kernel anyway, conv_4 is a 128 -> <= 64 channel 1x1 layer with fp16-form weights, and DT_C3FUSE is on
-static bool conv34_fusable(const dt_ctx *ctx, const ConvLayer &L3, const ConvLayer &L4, const float *in, int in_ld, int B, int H, int W)
+// conv_3 would take the direct fp16-form kernel anyway (choose_conv), conv_4 is a 128 -> <= 64 channel 1x1 layer with fp16-form weights, and DT_C3FUSE is on
+static bool conv34_fusable(const dt_ctx *ctx, const ConvLayer &L3, const ConvLayer &L4, const float *in, int in_ld, int B, int H, int W, const float *out)
 {
-    const long long blocks = (long long)B * ((H + 15) / 16) * ((W + 15) / 16);
-    return ctx->pol.c3fuse != 0 && L3.ks == 3 && L3.w3_h2 && L3.pscale_w3 && L3.cout == 128 && L4.ks == 1 && L4.cin == 128 && L4.cout <= 64 && L4.wt_h2 && L4.pscale_h2 &&
-           ctx->pol.c3h2 != 0 && h2_wanted(ctx) && in_ld % 4 == 0 && (reinterpret_cast<uintptr_t>(in) & 15) == 0 && (ctx->pol.c3h2 == 2 || blocks >= C3H2_MIN_BLOCKS);
+    return ctx->pol.c3fuse != 0 && L3.ks == 3 && L3.cout == 128 && L4.ks == 1 && L4.cin == 128 && L4.cout <= 64 && L4.wt_h2 && L4.pscale_h2 &&
+           choose_conv(ctx, L3, in, in_ld, B, H, W, out, ORD_LINEAR, EPI_PLAIN, false).form == CF_DIRECT_H2;
 }
 static int run_conv34_fused(dt_ctx *ctx, const ConvLayer &L3, const ConvLayer &L4, const float *in, int in_ld, int B, int H, int W, float *out, int out_ld, float slope)
 {
-    const long long M = (long long)B * H * W;
-    amax_forget(ctx, out, M * out_ld);
-    Conv3H2Args c;
-    memset(&c, 0, sizeof(c));
-    c.in = in; c.in_bs = (long long)H * W * in_ld; c.in_ld = in_ld; c.B = B; c.H = H; c.W = W; c.Cin = L3.cin; c.N = L3.cout; c.Np = L3.npad;
-    c.w = L3.w3_h2.get(); c.pscale = L3.pscale_w3.get(); c.bias = L3.bias.get(); c.slope = slope;
-    c.w1 = L4.wt_h2.get(); c.pscale1 = L4.pscale_h2.get(); c.bias1 = L4.bias.get(); c.N1 = L4.cout; c.Np1 = L4.npad; c.slope1 = slope;
-    c.out = out; c.out_ld = out_ld; c.out_bs = (long long)H * W * out_ld;
-    c.zeros = ws_get(ctx, "zeros256", 256, /*zero_on_grow=*/true);
-    if (!c.zeros) return DT_ERR_DEVICE;
-    c.amax = ensure_amax(ctx, in, M, L3.cin, in_ld, AMAX_IN + L3.idx);
-    if (!c.amax) return DT_ERR_DEVICE;
-    if (amax_out_slot(L4)) c.amax_out = amax_slot(ctx, amax_out_slot(L4));
+    const Leaves lv = conv_leaves(EPI_PLAIN, out, out_ld, nullptr, 0, (long long)B * H * W, L4.cout);
+    amax_forget(ctx, lv);
     char tag[32];
     snprintf(tag, sizeof(tag), "conv_%d", L3.idx);
-    if (ctx->prof && !ctx->capturing) ctx->prof_tab["conv_direct_h2:fused_1x1"].launches += 1;
-    // bytes: conv_3's input once (+ 41 % halo), conv_4's output; direct form: both layers
-    ProfScope ps(ctx, "conv_direct_h2", conv3_h2_flops(c), 4.0 * ((double)M * L3.cin * 1.41 + (double)M * L4.cout), tag);
-    prof_direct_form(ctx, 2.0 * M * (9.0 * L3.cin * L3.cout + (double)L4.cin * L4.cout),
-                     4.0 * ((double)M * L3.cin + 9.0 * L3.cin * L3.cout + 2.0 * (double)M * L3.cout + (double)L4.cin * L4.cout + (double)M * L4.cout), DF_C3H2);
-    const int rc = launch_conv3_h2(ctx->stream, c);
-    if (rc) return dt_fail(ctx, rc == 2 ? DT_ERR_ARG : DT_ERR_DEVICE, "%s: fused direct 3x3 + 1x1 launch failed", tag);
-    if (c.amax_out) amax_note(ctx, out, M * out_ld, L4.cout, amax_out_slot(L4));
-    return DT_OK;
+    const ConvCall c{L3, in, in_ld, B, H, W, out, out_ld, ORD_LINEAR, EPI_PLAIN, slope, nullptr, 0, tag, amax_out_slot(L4) ? amax_slot(ctx, amax_out_slot(L4)) : nullptr, B * H * W, 0.0, 0.0};
+    const int rc = conv_direct_h2(ctx, c, &L4);
+    if (rc == DT_OK && c.amax_out) amax_note(ctx, lv, amax_out_slot(L4));
+    return rc;
 }
 
 // conv_2 .. conv_21 on the library-owned buffers (bufA holds conv_1's pooled output).  With `ex` the walk stops at
@@ -1276,7 +1307,7 @@ static int run_trunk(dt_ctx *ctx, int B, float *bufA, float *bufB, float *skip, 
         const int idx = TRUNK[li][0], pool = TRUNK[li][4];
         const ConvLayer &L = ctx->layers[idx];
         if (ex && ex->idx == idx && ex->kind <= EX_ACT) return extract_layer(ctx, L, cur, L.cin, B, h, w, *ex);
-        if (idx == 3 && !ex && TRUNK[li + 1][0] == 4 && conv34_fusable(ctx, L, ctx->layers[4], cur, L.cin, B, h, w)) {
+        if (idx == 3 && !ex && TRUNK[li + 1][0] == 4 && conv34_fusable(ctx, L, ctx->layers[4], cur, L.cin, B, h, w, nxt)) {
             // conv_3 + conv_4 in one launch: conv_4's output goes to `nxt`, one swap, conv_4's turn of the walk is skipped
             rc = run_conv34_fused(ctx, L, ctx->layers[4], cur, L.cin, B, h, w, nxt, ctx->layers[4].cout, LEAKY);
             if (rc) return rc;
@@ -1360,8 +1391,8 @@ static int detect_internal(dt_ctx *ctx, const void *frames, int dtype, int B, De
         amax_forget(ctx, bufA, (long long)per_frame * B);
         if (int rcz = amax_begin(ctx)) return rcz;
         // (its epilogue takes max |x| of what it writes: conv_2's direct fp16-form kernel scales its input by it)
-        // (conv_1 publishes only where conv_2 will read it: the direct fp16-form kernel)
-        const bool c2_direct = ctx->pol.c3h2 == 2 || (ctx->pol.c3h2 != 0 && (long long)B * ((H / 2 + 15) / 16) * ((W / 2 + 15) / 16) >= C3H2_MIN_BLOCKS);
+        // (conv_1 publishes only where conv_2 will read it: the direct fp16-form kernel -- run_trunk's launch of conv_2, asked for ahead of time)
+        const bool c2_direct = choose_conv(ctx, ctx->layers[2], bufA, ctx->layers[2].cin, B, H / 2, W / 2, bufB, ORD_QUAD, EPI_POOL, false).form == CF_DIRECT_H2;
         unsigned *am1 = c1s3 && h2_wanted(ctx) && c2_direct && conv1_direct_fills_amax(frames, dtype, W, ctx->conv1_w3.get(), ctx->conv1_w3u8.get()) ? amax_slot(ctx, 1) : nullptr;
         if (launch_conv1_direct(ctx->stream, frames, dtype, B, H, W, ctx->conv1_w.get(), ctx->conv1_b.get(), ctx->lut255.get(), LEAKY,
                                 bufA, c1s3 ? ctx->conv1_w3.get() : nullptr, c1s3 ? ctx->conv1_w3u8.get() : nullptr, am1))
@@ -1613,7 +1644,7 @@ extern "C" int dt_associate(dt_ctx *ctx, const float *d_boxes, const int *d_coun
     if (!ctx || !d_boxes || !d_counts || !d_ids || !d_nids) return dt_fail(ctx, DT_ERR_ARG, "null argument");
     ProfScope ps(ctx, "associate", 0.0, 4.0 * n_clips * (double)T * cap * 9.0);
     const int rc = launch_associate(ctx->stream, d_boxes, d_counts, n_clips, T, cap, assoc_threshold, d_ids, d_nids);
-    if (rc) return dt_fail(ctx, rc == 2 ? DT_ERR_ARG : DT_ERR_DEVICE, "associate launch failed");
+    if (rc) return dt_fail(ctx, launch_code(rc), "associate launch failed");
     return DT_OK;
 }
 
@@ -1714,15 +1745,15 @@ static int convlstm_sequence(dt_ctx *ctx, const float *z, int Cx, int n_clips, i
         io.in = z; io.in_ld = Cx; io.in_bs = (long long)GG * Cx;
         io.out = xproj; io.out_ld = N4; io.out_bs = (long long)GG * N4;
         io.bias16 = ctx->trk_bx16.get() + N4;         // corrections of the 16 border cases; row 0 of the table is the interior bias
-        if (ctx->prof && !ctx->capturing) ctx->prof_tab["convlstm_xproj:merged_conv23"].launches += 1;
-        const int rc = run_wino(ctx, ctx->trk_wxm_wino, ctx->trk_bx16.get(), N4, F, gh, gw, io, 1.0f, "convlstm_xproj", ctx->cb + 1024, AMAX_TRK);
+        prof_count(ctx, "convlstm_xproj:merged_conv23");
+        const int rc = run_wino(ctx, ctx->trk_wxm_wino, choose_wino(ctx, ctx->trk_wxm_wino, N4, F, gh, gw, io), ctx->trk_bx16.get(), N4, F, gh, gw, io, 1.0f, "convlstm_xproj", ctx->cb + 1024, AMAX_TRK);
         if (rc) return rc;
     } else if (wino_runs(ctx, wx_wino, F, gh, gw, N4)) {
         WinoIO io;
         memset(&io, 0, sizeof(io));
         io.in = z; io.in_ld = Cx; io.in_bs = (long long)GG * Cx;
         io.out = xproj; io.out_ld = N4; io.out_bs = (long long)GG * N4;
-        const int rc = run_wino(ctx, wx_wino, bx, N4, F, gh, gw, io, 1.0f, "convlstm_xproj", ctx->cb + 1024, AMAX_TRK);
+        const int rc = run_wino(ctx, wx_wino, choose_wino(ctx, wx_wino, N4, F, gh, gw, io), bx, N4, F, gh, gw, io, 1.0f, "convlstm_xproj", ctx->cb + 1024, AMAX_TRK);
         if (rc) return rc;
     } else {
         ConvArgs a;
@@ -1772,7 +1803,7 @@ static int convlstm_sequence(dt_ctx *ctx, const float *z, int Cx, int n_clips, i
             io.xproj = xproj + (long long)t * GG * N4; io.xp_ld = N4; io.xp_bs = xp_bs;
             io.cstate = cst; io.c_ld = U; io.c_bs = c_bs;
             // (h_{t-1} = o * tanh(c) lies in (-1, 1): the fp16 form's scale is static, nothing is measured)
-            const int rc = run_wino(ctx, wh_wino, nullptr, N4, n_clips, gh, gw, io, 1.0f, "convlstm_step", 0, AMAX_ONE);
+            const int rc = run_wino(ctx, wh_wino, choose_wino(ctx, wh_wino, N4, n_clips, gh, gw, io), nullptr, N4, n_clips, gh, gw, io, 1.0f, "convlstm_step", 0, AMAX_ONE);
             if (rc) return rc;
             continue;
         }
@@ -1807,15 +1838,14 @@ static int convlstm_sequence(dt_ctx *ctx, const float *z, int Cx, int n_clips, i
     return rc ? rc : graphed(ctx, "clstm_steps:" + shape, recurrence);
 }
 
-// the recurrent head on z [n_clips][T][G*G][Cx] (library- or caller-owned): ConvLSTM2D over T, then tconv_2
-static int track_recurrent_internal(dt_ctx *ctx, const float *z, int n_clips, int T, float *d_trk, int carry = CARRY_NONE)
+// the recurrent head on z [n_clips][T][G*G][Cx] (library- or caller-owned; null: on the caller's projection rows d_xp): ConvLSTM2D over T, then tconv_2
+static int track_recurrent_internal(dt_ctx *ctx, const float *z, int n_clips, int T, float *d_trk, int carry = CARRY_NONE, float *d_xp = nullptr)
 {
     const int gh = ctx->image_h / 32, gw = ctx->image_w / 32, GG = gh * gw;
     const int F = n_clips * T, U = ctx->trk_units, Cx = ctx->trk_cx, Cb = ctx->cb;
     float *hseq = ws_get(ctx, "trk_h", (size_t)F * GG * U * sizeof(float));
     if (!hseq) return DT_ERR_DEVICE;
-    int rc = convlstm_sequence(ctx, z, Cx, n_clips, T, gh, gw, U, ctx->trk_wx.get(), ctx->trk_bx.get(), ctx->trk_wh.get(), hseq, ctx->trk_wx_wino,
-                               ctx->trk_wh_wino, nullptr, carry);
+    int rc = convlstm_sequence(ctx, z, Cx, n_clips, T, gh, gw, U, ctx->trk_wx.get(), ctx->trk_bx.get(), ctx->trk_wh.get(), hseq, ctx->trk_wx_wino, ctx->trk_wh_wino, d_xp, carry);
     if (rc) return rc;
     float *trk = d_trk;
     if (!trk) {
@@ -1826,6 +1856,36 @@ static int track_recurrent_internal(dt_ctx *ctx, const float *z, int n_clips, in
     return run_conv(ctx, ctx->trk_out, hseq, U, F, gh, gw, trk, Cb, ORD_LINEAR, EPI_PLAIN, 1.0f);
 }
 
+// the detector's grid, columns [1024, 1024 + Cb) of the z rows, into d_det where the caller asks for it
+static int copy_det(dt_ctx *ctx, const float *z, long long rows, float *d_det)
+{
+    if (d_det && launch_copy_cols(ctx->stream, z + 1024, ctx->trk_cx, d_det, ctx->cb, rows, ctx->cb)) return dt_fail(ctx, DT_ERR_DEVICE, "detection copy launch failed");
+    return DT_OK;
+}
+
+// dt_track_forward, and with a slot list dt_track_stream_forward: the streams carry their ConvLSTM state from call to call in the context's slots
+static int track_forward_internal(dt_ctx *ctx, const void *d_frames, int frames_dtype, int n, int T, const int *h_slots, float *d_trk, float *d_det)
+{
+    StreamTable &S = ctx->streams;
+    const int gh = ctx->image_h / 32, gw = ctx->image_w / 32, GG = gh * gw;
+    const int F = n * T, Cx = ctx->trk_cx, Cb = ctx->cb;
+    int carry = h_slots ? CARRY_FRESH : CARRY_NONE;
+    for (int i = 0; h_slots && i < n; ++i)
+        if (S.warm[h_slots[i]]) carry = CARRY_WARM;
+    float *z = ws_get(ctx, "trk_z", (size_t)F * GG * Cx * sizeof(float), /*zero_on_grow=*/true);
+    if (!z) return DT_ERR_DEVICE;
+    int rc = detect_internal(ctx, d_frames, frames_dtype, F, Dest{z, Cx}, Dest{z + 1024, Cx}, /*skip23=*/!d_det && xproj_merged(ctx, F, gh, gw));
+    if (rc) return rc;
+    // the slot list reaches the state moves through the library-owned device list: filled here, in stream order and outside the graph
+    if (h_slots && launch_stream_slots(ctx->stream, h_slots, n, S.list.get(), nullptr)) return dt_fail(ctx, DT_ERR_DEVICE, "slot list launch failed");
+    rc = track_recurrent_internal(ctx, z, n, T, d_trk, carry);
+    if (rc) return rc;
+    for (int i = 0; h_slots && i < n; ++i) S.warm[h_slots[i]] = 1;
+    if (!d_det) return DT_OK;
+    ProfScope ps(ctx, "misc", 0.0, 8.0 * F * GG * (double)Cb);
+    return copy_det(ctx, z, (long long)F * GG, d_det);
+}
+
 extern "C" int dt_track_forward(dt_ctx *ctx, const void *d_frames, int frames_dtype, int n_clips, int T,
                                 float *d_trk, float *d_det)
 {
@@ -1833,23 +1893,9 @@ extern "C" int dt_track_forward(dt_ctx *ctx, const void *d_frames, int frames_dt
     if (!ctx || !d_frames) return dt_fail(ctx, DT_ERR_ARG, "null argument");
     if (!ctx->trk_loaded) return dt_fail(ctx, DT_ERR_STATE, "tracker weights not loaded");
     if (n_clips <= 0 || T <= 0) return dt_fail(ctx, DT_ERR_ARG, "n_clips and T must be positive");
-    const int gh = ctx->image_h / 32, gw = ctx->image_w / 32, GG = gh * gw;
-    const int F = n_clips * T, Cx = ctx->trk_cx, Cb = ctx->cb;
-    float *z = ws_get(ctx, "trk_z", (size_t)F * GG * Cx * sizeof(float), /*zero_on_grow=*/true);
-    if (!z) return DT_ERR_DEVICE;
-    int rc = detect_internal(ctx, d_frames, frames_dtype, F, Dest{z, Cx}, Dest{z + 1024, Cx}, /*skip23=*/!d_det && xproj_merged(ctx, F, gh, gw));
-    if (rc) return rc;
-    rc = track_recurrent_internal(ctx, z, n_clips, T, d_trk);
-    if (rc) return rc;
-    if (d_det) {
-        ProfScope ps(ctx, "misc", 0.0, 8.0 * F * GG * (double)Cb);
-        if (launch_copy_cols(ctx->stream, z + 1024, Cx, d_det, Cb, (long long)F * GG, Cb))
-            return dt_fail(ctx, DT_ERR_DEVICE, "detection copy launch failed");
-    }
-    return DT_OK;
+    return track_forward_internal(ctx, d_frames, frames_dtype, n_clips, T, nullptr, d_trk, d_det);
 }
 
-// dt_track_forward on streams that carry their ConvLSTM state from call to call in the context's slots
 extern "C" int dt_track_stream_forward(dt_ctx *ctx, const void *d_frames, int frames_dtype, int n, int T, const int *h_slots,
                                        float *d_trk, float *d_det)
 {
@@ -1859,27 +1905,8 @@ extern "C" int dt_track_stream_forward(dt_ctx *ctx, const void *d_frames, int fr
     if (n <= 0 || T <= 0) return dt_fail(ctx, DT_ERR_ARG, "n and T must be positive");
     int rc = streams_check_list(ctx, h_slots, n);
     if (rc) return rc;
-    StreamTable &S = ctx->streams;
-    const int gh = ctx->image_h / 32, gw = ctx->image_w / 32, GG = gh * gw;
-    const int F = n * T, Cx = ctx->trk_cx, Cb = ctx->cb;
-    if (S.row != GG * ctx->trk_units) return dt_fail(ctx, DT_ERR_STATE, "the stream table was opened for another model");
-    bool warm = false;
-    for (int i = 0; i < n; ++i) warm = warm || S.warm[h_slots[i]];
-    float *z = ws_get(ctx, "trk_z", (size_t)F * GG * Cx * sizeof(float), /*zero_on_grow=*/true);
-    if (!z) return DT_ERR_DEVICE;
-    rc = detect_internal(ctx, d_frames, frames_dtype, F, Dest{z, Cx}, Dest{z + 1024, Cx}, /*skip23=*/!d_det && xproj_merged(ctx, F, gh, gw));
-    if (rc) return rc;
-    // the slot list reaches the state moves through the library-owned device list: filled here, in stream order and outside the graph
-    if (launch_stream_slots(ctx->stream, h_slots, n, S.list.get(), nullptr)) return dt_fail(ctx, DT_ERR_DEVICE, "slot list launch failed");
-    rc = track_recurrent_internal(ctx, z, n, T, d_trk, warm ? CARRY_WARM : CARRY_FRESH);
-    if (rc) return rc;
-    for (int i = 0; i < n; ++i) S.warm[h_slots[i]] = 1;
-    if (d_det) {
-        ProfScope ps(ctx, "misc", 0.0, 8.0 * F * GG * (double)Cb);
-        if (launch_copy_cols(ctx->stream, z + 1024, Cx, d_det, Cb, (long long)F * GG, Cb))
-            return dt_fail(ctx, DT_ERR_DEVICE, "detection copy launch failed");
-    }
-    return DT_OK;
+    if (ctx->streams.row != (ctx->image_h / 32) * (ctx->image_w / 32) * ctx->trk_units) return dt_fail(ctx, DT_ERR_STATE, "the stream table was opened for another model");
+    return track_forward_internal(ctx, d_frames, frames_dtype, n, T, h_slots, d_trk, d_det);
 }
 
 extern "C" int dt_associate_stream(dt_ctx *ctx, const float *d_boxes, const int *d_counts, int n, int T, int cap,
@@ -1895,7 +1922,7 @@ extern "C" int dt_associate_stream(dt_ctx *ctx, const float *d_boxes, const int 
     ProfScope ps(ctx, "associate", 0.0, 4.0 * n * (double)(T + 2) * cap * 9.0, "stream");
     rc = launch_associate_stream(ctx->stream, d_boxes, d_counts, n, T, cap, assoc_threshold, d_ids, d_nids,
                                  AssocCarry{S.list.get(), S.boxes.get(), S.ids.get(), S.meta.get()});
-    if (rc) return dt_fail(ctx, rc == 2 ? DT_ERR_ARG : DT_ERR_DEVICE, "associate launch failed");
+    if (rc) return dt_fail(ctx, launch_code(rc), "associate launch failed");
     return DT_OK;
 }
 
@@ -1926,14 +1953,8 @@ extern "C" int dt_track_recurrent(dt_ctx *ctx, const float *d_z, int n_clips, in
     if (!ctx || !d_z) return dt_fail(ctx, DT_ERR_ARG, "null argument");
     if (!ctx->trk_loaded) return dt_fail(ctx, DT_ERR_STATE, "tracker weights not loaded");
     if (n_clips <= 0 || T <= 0) return dt_fail(ctx, DT_ERR_ARG, "n_clips and T must be positive");
-    int rc = track_recurrent_internal(ctx, d_z, n_clips, T, d_trk);
-    if (rc) return rc;
-    if (d_det) {
-        const int GG = (ctx->image_h / 32) * (ctx->image_w / 32);
-        if (launch_copy_cols(ctx->stream, d_z + 1024, ctx->trk_cx, d_det, ctx->cb, (long long)n_clips * T * GG, ctx->cb))
-            return dt_fail(ctx, DT_ERR_DEVICE, "detection copy launch failed");
-    }
-    return DT_OK;
+    const int rc = track_recurrent_internal(ctx, d_z, n_clips, T, d_trk);
+    return rc ? rc : copy_det(ctx, d_z, (long long)n_clips * T * (ctx->image_h / 32) * (ctx->image_w / 32), d_det);
 }
 
 // The same split one step later in the graph: the ConvLSTM2D INPUT projection W * x_t + b (MultiObjDetTracker.py:176; 55 % of
@@ -1950,18 +1971,14 @@ extern "C" int dt_track_detect_xproj(dt_ctx *ctx, const void *d_frames, int fram
     if (!ctx || !d_frames || !d_xp) return dt_fail(ctx, DT_ERR_ARG, "null argument");
     if (!ctx->trk_loaded) return dt_fail(ctx, DT_ERR_STATE, "tracker weights not loaded");
     if (n_frames <= 0) return dt_fail(ctx, DT_ERR_ARG, "n_frames must be positive");
-    const int gh = ctx->image_h / 32, gw = ctx->image_w / 32, GG = gh * gw;
-    const int Cx = ctx->trk_cx, Cb = ctx->cb;
+    const int gh = ctx->image_h / 32, gw = ctx->image_w / 32, GG = gh * gw, Cx = ctx->trk_cx;
     float *z = ws_get(ctx, "trk_z", (size_t)n_frames * GG * Cx * sizeof(float), /*zero_on_grow=*/true);
     if (!z) return DT_ERR_DEVICE;
     int rc = detect_internal(ctx, d_frames, frames_dtype, n_frames, Dest{z, Cx}, Dest{z + 1024, Cx}, /*skip23=*/!d_det && xproj_merged(ctx, n_frames, gh, gw));
     if (rc) return rc;
     rc = convlstm_sequence(ctx, z, Cx, n_frames, 1, gh, gw, ctx->trk_units, ctx->trk_wx.get(), ctx->trk_bx.get(), ctx->trk_wh.get(), nullptr,
                            ctx->trk_wx_wino, ctx->trk_wh_wino, d_xp);
-    if (rc) return rc;
-    if (d_det && launch_copy_cols(ctx->stream, z + 1024, Cx, d_det, Cb, (long long)n_frames * GG, Cb))
-        return dt_fail(ctx, DT_ERR_DEVICE, "detection copy launch failed");
-    return DT_OK;
+    return rc ? rc : copy_det(ctx, z, (long long)n_frames * GG, d_det);
 }
 
 extern "C" int dt_track_recurrent_xproj(dt_ctx *ctx, const float *d_xp, int n_clips, int T, float *d_trk)
@@ -1970,20 +1987,7 @@ extern "C" int dt_track_recurrent_xproj(dt_ctx *ctx, const float *d_xp, int n_cl
     if (!ctx || !d_xp) return dt_fail(ctx, DT_ERR_ARG, "null argument");
     if (!ctx->trk_loaded) return dt_fail(ctx, DT_ERR_STATE, "tracker weights not loaded");
     if (n_clips <= 0 || T <= 0) return dt_fail(ctx, DT_ERR_ARG, "n_clips and T must be positive");
-    const int gh = ctx->image_h / 32, gw = ctx->image_w / 32, GG = gh * gw;
-    const int F = n_clips * T, U = ctx->trk_units, Cb = ctx->cb;
-    float *hseq = ws_get(ctx, "trk_h", (size_t)F * GG * U * sizeof(float));
-    if (!hseq) return DT_ERR_DEVICE;
-    int rc = convlstm_sequence(ctx, nullptr, ctx->trk_cx, n_clips, T, gh, gw, U, ctx->trk_wx.get(), ctx->trk_bx.get(), ctx->trk_wh.get(), hseq,
-                               ctx->trk_wx_wino, ctx->trk_wh_wino, const_cast<float *>(d_xp));
-    if (rc) return rc;
-    float *trk = d_trk;
-    if (!trk) {
-        trk = ws_get(ctx, "trk_out", (size_t)F * GG * Cb * sizeof(float));
-        if (!trk) return DT_ERR_DEVICE;
-    }
-    // TimeDistributed(Conv2D(Cb,(1,1)))  'tconv_2'  (MultiObjDetTracker.py:182)
-    return run_conv(ctx, ctx->trk_out, hseq, U, F, gh, gw, trk, Cb, ORD_LINEAR, EPI_PLAIN, 1.0f);
+    return track_recurrent_internal(ctx, nullptr, n_clips, T, d_trk, CARRY_NONE, const_cast<float *>(d_xp));
 }
 
 // ---------------------------------------------------------------------------
@@ -2045,7 +2049,7 @@ extern "C" int dt_tiny_features(dt_ctx *ctx, const float *d_feat, const float *d
     ProfScope ps(ctx, "pool", 0.0, 4.0 * n_rows * ((double)fh * fw * fc + fdim));
     int rc = pool == 0 ? launch_global_maxpool(ctx->stream, d_feat, n_rows, fh * fw, fc, d_x, D)
                        : launch_maxpool4_flatten(ctx->stream, d_feat, n_rows, fh, fw, fc, d_x, D);
-    if (rc) return dt_fail(ctx, rc == 2 ? DT_ERR_ARG : DT_ERR_DEVICE, "pool launch failed");
+    if (rc) return dt_fail(ctx, launch_code(rc), "pool launch failed");
     if (launch_copy_cols(ctx->stream, d_det, ddim, d_x + fdim, D, n_rows, ddim))
         return dt_fail(ctx, DT_ERR_DEVICE, "det concat launch failed");
     return DT_OK;
@@ -2250,14 +2254,14 @@ extern "C" int dt_convlstm_step(dt_ctx *ctx, const float *d_x, int B, int H, int
         memset(&io, 0, sizeof(io));
         io.in = d_x; io.in_ld = Cx; io.in_bs = (long long)GG * Cx;
         io.out = xproj; io.out_ld = N4; io.out_bs = (long long)GG * N4;
-        if ((rc = run_wino(ctx, uwx, dbx.get(), N4, B, H, W, io, 1.0f, "convlstm_xproj", 0, AMAX_TEST))) return rc;
+        if ((rc = run_wino(ctx, uwx, choose_wino(ctx, uwx, N4, B, H, W, io), dbx.get(), N4, B, H, W, io, 1.0f, "convlstm_xproj", 0, AMAX_TEST))) return rc;
         HIP_TRY(ctx, hipMemcpyAsync(d_c_out, d_c, (size_t)B * GG * U * sizeof(float), hipMemcpyDeviceToDevice, ctx->stream));
         memset(&io, 0, sizeof(io));
         io.in = d_h; io.in_ld = U; io.in_bs = (long long)GG * U;
         io.out = d_h_out; io.out_ld = U; io.out_bs = (long long)GG * U;
         io.xproj = xproj; io.xp_ld = N4; io.xp_bs = (long long)GG * N4;
         io.cstate = d_c_out; io.c_ld = U; io.c_bs = (long long)GG * U;
-        return run_wino(ctx, uwh, nullptr, N4, B, H, W, io, 1.0f, "convlstm_step", 0, AMAX_TEST + 1);      // (a caller's h: measured)
+        return run_wino(ctx, uwh, choose_wino(ctx, uwh, N4, B, H, W, io), nullptr, N4, B, H, W, io, 1.0f, "convlstm_step", 0, AMAX_TEST + 1);      // (a caller's h: measured)
     }
     ConvArgs a;
     memset(&a, 0, sizeof(a));
@@ -2321,9 +2325,9 @@ extern "C" int dt_gemm_split(dt_ctx *ctx, const float *d_v, const float *d_u, in
     if (rows_form) { g.a = nullptr; g.a_f32 = d_v; g.a_ld = K; g.act = 1; g.slope = 1.0f; }      // (no bias, no activation)
     g.c_ps = (long long)Mt * N; g.P = P; g.Mt = Mt; g.Mp = (int)Mp; g.N = N; g.Np = (int)Np; g.K = K; g.ldc = N; g.half = half;
     ProfScope pscope(ctx, "conv_gemm_s3", wino_gemm_s3_flops(g), (double)P * (2.0 * nt * Mt * K + 2.0 * nt * (double)K * N + 4.0 * (double)Mt * N), "test_gemm");
-    if (ctx->prof && !ctx->capturing) ctx->prof_tab[wino_gemm_s3_half_chosen(g, 0) ? "s3_tile:128x2" : "s3_tile:256"].launches += 1;
+    if (pscope.on) prof_count(ctx, wino_gemm_s3_half_chosen(g, 0) ? "s3_tile:128x2" : "s3_tile:256");
     const int rc = launch_wino_gemm_s3(ctx->stream, g, 0);
-    if (rc) return dt_fail(ctx, rc == 2 ? DT_ERR_ARG : DT_ERR_DEVICE, "dt_gemm_split: launch failed (rc=%d)", rc);
+    if (rc) return dt_fail(ctx, launch_code(rc), "dt_gemm_split: launch failed (rc=%d)", rc);
     return DT_OK;
 }
 extern "C" int dt_gemm_split_bf16(dt_ctx *ctx, const float *d_v, const float *d_u, int P, int Mt, int K, int N, int half, float *d_m)
