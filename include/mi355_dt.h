@@ -49,7 +49,8 @@ DT_API void dt_destroy(dt_ctx *ctx);
 DT_API const char *dt_last_error(dt_ctx *ctx);
 DT_API int dt_set_stream(dt_ctx *ctx, void *hip_stream);
 /* ABI version of this header: major*100+minor (1.08: 1.07 + dt_amax_read, and later the four stream entries dt_stream_open, dt_stream_reset,
- * dt_track_stream_forward, dt_associate_stream -- additions only, the number stayed; 1.07: 1.06 + dt_gemm_split, dt_policy_set) */
+ * dt_track_stream_forward, dt_associate_stream, and the three track-memory entries dt_associate_mem, dt_stream_open_tracks, dt_associate_stream_mem
+ * -- additions only, the number stayed; 1.07: 1.06 + dt_gemm_split, dt_policy_set) */
 DT_API int dt_abi_version(void);
 
 /* ---- detector: KerasYOLO ---------------------------------------------- */
@@ -173,10 +174,21 @@ DT_API int dt_track_recurrent_xproj(dt_ctx *ctx, const float *d_xp, int n_clips,
 DT_API int dt_associate(dt_ctx *ctx, const float *d_boxes, const int *d_counts,
                  int n_clips, int T, int cap, float assoc_threshold,
                  int *d_ids, int *d_nids);
+/* Track memory (BUILD-DEFINED, DESIGN.md "Track identity"): a track that misses up to max_age frames keeps its id.  The kernel keeps a
+ * track table of at most tcap entries (box, label, id, age = frames since the track last had a box) per clip; a box takes the id of the
+ * unclaimed entry of its label with age <= max_age and the largest IoU >= assoc_threshold (ties: lowest table index), else a new id.
+ * After a frame the table is the frame's boxes in decode order followed by the unclaimed entries with age + 1 <= max_age in their old
+ * order, cut at tcap.  d_gaps [n_clips,T,cap] (may be NULL): the claimed entry's age -- 0 unbroken, k after k missed frames, -1 for a
+ * new id and in unused entries.  max_age = 0 is dt_associate bit for bit.  No motion model, no cross-label match, no optimal assignment.
+ * DT_ERR_ARG: max_age < 0, tcap < cap, or a table that does not fit the LDS (tcap <= 64 and T <= 64 run in registers and need none). */
+DT_API int dt_associate_mem(dt_ctx *ctx, const float *d_boxes, const int *d_counts,
+                 int n_clips, int T, int cap, float assoc_threshold, int max_age, int tcap,
+                 int *d_ids, int *d_nids, int *d_gaps);
 
 /* ---- streaming: ConvLSTM state and track ids carried across calls (addition; the reference's predict() sees one window) ---- *
  * A live stream delivers a frame, or a few, at a time.  The context holds a table of STREAM SLOTS in device memory; per slot the ConvLSTM
- * state h, c [G*G][U], the last frame's boxes [cap][8], their count and ids [cap], the next free track id, and counters of frames seen.
+ * state h, c [G*G][U], the track table (the last frame's boxes first, then lost tracks: boxes [tcap][8], ids and ages [tcap]; tcap = cap unless
+ * dt_stream_open_tracks says otherwise), the next free track id, and counters of frames seen.
  * Contract: a stream fed in chunks of any sizes gives what the stateless calls give on the concatenation of those chunks as one clip.
  * A FRESH slot (after dt_stream_open / dt_stream_reset, and after dt_tracker_load, dt_load_darknet_weights or dt_detector_config, which make
  * every slot fresh -- a load that changes the state's shape closes the table) is indistinguishable from a stateless call.
@@ -186,6 +198,9 @@ DT_API int dt_associate(dt_ctx *ctx, const float *d_boxes, const int *d_counts,
  * dt_stream_open: (re)allocates the table, every slot fresh; needs a loaded tracker.  cap = box capacity of the association state.
  * dt_stream_reset: the listed slots fresh again (zero state, ids from 0); h_slots == NULL: all of them.  Stream-ordered, no host wait. */
 DT_API int dt_stream_open(dt_ctx *ctx, int n_slots, int cap);
+/* dt_stream_open with a track table of tcap >= cap entries per slot (boxes [tcap][8], ids [tcap], ages [tcap]) for dt_associate_stream_mem;
+ * dt_stream_open(ctx, n, cap) is dt_stream_open_tracks(ctx, n, cap, cap).  DT_ERR_ARG: tcap < cap or tcap > 65535. */
+DT_API int dt_stream_open_tracks(dt_ctx *ctx, int n_slots, int cap, int tcap);
 DT_API int dt_stream_reset(dt_ctx *ctx, const int *h_slots, int n);
 /* dt_track_forward on d_frames [n, T, H, W, 3]: stream i starts from the state in slot h_slots[i] and leaves its state after frame T-1
  * there.  d_trk / d_det as dt_track_forward.  When any slot of the call is warm, t = 0 is a full recurrent step (the form steps t >= 1 take). */
@@ -196,6 +211,13 @@ DT_API int dt_track_stream_forward(dt_ctx *ctx, const void *d_frames, int frames
  * the table's (DT_ERR_ARG). */
 DT_API int dt_associate_stream(dt_ctx *ctx, const float *d_boxes, const int *d_counts, int n, int T, int cap,
                         float thr, const int *h_slots, int *d_ids, int *d_nids);
+/* dt_associate_mem for streams: the slot's track table is the table frame 0 is matched against, and the table after frame T-1 goes back
+ * to the slot.  Chunks of any sizes with one max_age give what dt_associate_mem gives on the concatenation with tcap = the table's.
+ * max_age belongs to the call: a call with a smaller one ignores older entries, and they leave the table at the end of its first frame.
+ * dt_associate_stream on any table is this entry with max_age = 0; the two may be mixed on one slot.  Errors as dt_associate_stream, and
+ * DT_ERR_ARG for max_age < 0; an error leaves the slots as they were. */
+DT_API int dt_associate_stream_mem(dt_ctx *ctx, const float *d_boxes, const int *d_counts, int n, int T, int cap,
+                        float thr, int max_age, const int *h_slots, int *d_ids, int *d_nids, int *d_gaps);
 
 /* ---- cross-stream detection exchange (multi-GPU; the reference has no counterpart) ---- *
  * north_star: "RCCL all-gather of detections over xGMI only for cross-stream association".  Each rank packs its

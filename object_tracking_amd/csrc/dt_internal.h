@@ -314,23 +314,34 @@ int launch_bbox_iou(hipStream_t st, const float *pairs, int n, float *iou);
 
 int launch_associate(hipStream_t st, const float *boxes, const int *counts, int n_clips, int T, int cap,
                      float thr, int *ids, int *nids);
-// Association state of the stream slots (dt_associate_stream): clip i of the call continues slot slots[i].  Per slot the last frame it saw --
-// boxes [cap][8] as the caller handed them, ids [cap] -- and meta = STREAM_META ints (stream_state.hip)
+// Association state of the stream slots (dt_associate_stream, dt_associate_stream_mem): clip i of the call continues slot slots[i].  Per slot its
+// TRACK TABLE of up to tcap entries -- boxes [tcap][8] (x, y, w, h, -, label, -, -), ids [tcap], ages [tcap] -- and meta = STREAM_META ints
+// (stream_state.hip).  The entries of age 0, the last frame the slot saw in decode order, lead the table; the aged entries follow them.
+// dt_associate_stream reads and leaves the age-0 entries only (the rule with max_age = 0) and never touches `ages`.
 struct AssocCarry {
     const int *slots;   // [n_clips] on the device; null = the stateless launch
-    float *boxes;       // [n_slots][cap][8]
-    int *ids;           // [n_slots][cap]
+    float *boxes;       // [n_slots][tcap][8]
+    int *ids;           // [n_slots][tcap]
+    int *ages;          // [n_slots][tcap]; read for the entries behind the age-0 ones only
     int *meta;          // [n_slots][STREAM_META]
+    int tcap;           // entries per slot
 };
+// track memory (decode.hip:associate_mem_kernel): 2 = argument error, nothing launched (tcap < cap, max_age < 0, a table beyond the LDS, carry.tcap != tcap)
+size_t assoc_mem_lds_bytes(int T, int cap, int tcap);      // dynamic LDS the launch needs; above 160 KB the launcher refuses
+int launch_associate_mem(hipStream_t st, const float *boxes, const int *counts, int n_clips, int T, int cap, float thr,
+                         int max_age, int tcap, int *ids, int *nids, int *gaps /*may be null*/, const AssocCarry &carry);
 int launch_associate_stream(hipStream_t st, const float *boxes, const int *counts, int n_clips, int T, int cap,
                             float thr, int *ids, int *nids, const AssocCarry &carry);
 
 // ---------------------------------------------------------------------------
 // stream slots: state that outlives a call (stream_state.hip)
 // ---------------------------------------------------------------------------
-// meta row of a slot: boxes in the stored last frame, next free track id, frames the recurrence has seen (0 = the slot's h / c rows
-// read as zeros whatever they hold), frames the association has seen.  A slot whose row is all zero is fresh.
+// meta row of a slot: entries in the stored track table, next free track id, frames the recurrence has seen (0 = the slot's h / c rows
+// read as zeros whatever they hold), frames the association has seen.  A slot whose row is all zero is fresh (an empty table).
+// SM_COUNT packs two counts, so that a reset stays one int4 store: bits 0..15 the age-0 entries (the last frame's boxes), bits 16..31 the
+// aged entries behind them.
 enum { SM_COUNT = 0, SM_NEXT_ID = 1, SM_FRAMES = 2, SM_ASSOC_FRAMES = 3, STREAM_META = 4 };
+enum { SM_COUNT_MASK = 0xffff, SM_AGED_SHIFT = 16 };
 // the call's slot list, from the caller's HOST array into the library-owned device list: the numbers travel as kernel arguments of a
 // launch OUTSIDE any captured graph, so neither a host synchronisation nor pinned staging is needed.  reset_meta != null: the listed slots' meta rows are zeroed too
 int launch_stream_slots(hipStream_t st, const int *h_slots, int n, int *d_list, int *reset_meta);
@@ -517,10 +528,12 @@ struct Policy {
 // The stream slots of a context (dt_stream_open): everything a stream carries from one call to the next, in device memory
 struct StreamTable {
     int n_slots = 0, cap = 0;
+    int tcap = 0;              // entries of a slot's track table (dt_stream_open: cap)
     int row = 0;               // floats per h / c row: G*G*U of the tracker the table was opened under
     DevMem<float> h, c;        // ConvLSTM state [n_slots][G*G][U]
-    DevMem<float> boxes;       // the last frame's boxes [n_slots][cap][8]
-    DevMem<int> ids;           // ... and their ids [n_slots][cap]
+    DevMem<float> boxes;       // the track table's boxes [n_slots][tcap][8]: the last frame's first, aged entries behind them
+    DevMem<int> ids;           // ... their ids [n_slots][tcap]
+    DevMem<int> ages;          // ... and ages [n_slots][tcap]
     DevMem<int> meta;          // [n_slots][STREAM_META]
     DevMem<int> list;          // [n_slots]: the slot list of the running call, filled before its launches (never a kernel argument of a captured launch)
     std::vector<char> warm;    // host mirror of meta[SM_FRAMES] != 0: decides between the gates-only launch and a full step at t = 0

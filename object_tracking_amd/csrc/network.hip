@@ -420,11 +420,12 @@ static int streams_check_list(dt_ctx *ctx, const int *h_slots, int n)
     return DT_OK;
 }
 
-extern "C" int dt_stream_open(dt_ctx *ctx, int n_slots, int cap)
+extern "C" int dt_stream_open_tracks(dt_ctx *ctx, int n_slots, int cap, int tcap)
 {
     if (!ctx) return DT_ERR_ARG;
     if (!ctx->trk_loaded) return dt_fail(ctx, DT_ERR_STATE, "tracker weights not loaded");
     if (n_slots <= 0 || n_slots > 65535 || cap <= 0) return dt_fail(ctx, DT_ERR_ARG, "n_slots must be in [1, 65535] and cap positive");
+    if (tcap < cap || tcap > SM_COUNT_MASK) return dt_fail(ctx, DT_ERR_ARG, "tcap must be in [cap, %d]", (int)SM_COUNT_MASK);
     const long long row = (long long)(ctx->image_h / 32) * (ctx->image_w / 32) * ctx->trk_units;
     if (row <= 0 || row >= (1ll << 31)) return dt_fail(ctx, DT_ERR_ARG, "bad state row size");
     graphs_clear(ctx);      // captured state moves hold the old table's pointers
@@ -432,15 +433,21 @@ extern "C" int dt_stream_open(dt_ctx *ctx, int n_slots, int cap)
     StreamTable S;
     HIP_TRY(ctx, S.h.alloc((size_t)n_slots * row));
     HIP_TRY(ctx, S.c.alloc((size_t)n_slots * row));
-    HIP_TRY(ctx, S.boxes.alloc((size_t)n_slots * cap * DT_BOX_FLOATS));
-    HIP_TRY(ctx, S.ids.alloc((size_t)n_slots * cap));
+    HIP_TRY(ctx, S.boxes.alloc((size_t)n_slots * tcap * DT_BOX_FLOATS));
+    HIP_TRY(ctx, S.ids.alloc((size_t)n_slots * tcap));
+    HIP_TRY(ctx, S.ages.alloc((size_t)n_slots * tcap));
     HIP_TRY(ctx, S.meta.alloc((size_t)n_slots * STREAM_META));
     HIP_TRY(ctx, S.list.alloc((size_t)n_slots));
     HIP_TRY(ctx, hipMemsetAsync(S.meta.get(), 0, (size_t)n_slots * STREAM_META * sizeof(int), ctx->stream));
-    S.n_slots = n_slots; S.cap = cap; S.row = (int)row;
+    S.n_slots = n_slots; S.cap = cap; S.tcap = tcap; S.row = (int)row;
     S.warm.assign((size_t)n_slots, 0);
     ctx->streams = std::move(S);
     return DT_OK;
+}
+
+extern "C" int dt_stream_open(dt_ctx *ctx, int n_slots, int cap)
+{
+    return dt_stream_open_tracks(ctx, n_slots, cap, cap);
 }
 
 extern "C" int dt_stream_reset(dt_ctx *ctx, const int *h_slots, int n)
@@ -1648,6 +1655,18 @@ extern "C" int dt_associate(dt_ctx *ctx, const float *d_boxes, const int *d_coun
     return DT_OK;
 }
 
+extern "C" int dt_associate_mem(dt_ctx *ctx, const float *d_boxes, const int *d_counts, int n_clips, int T, int cap,
+                                float assoc_threshold, int max_age, int tcap, int *d_ids, int *d_nids, int *d_gaps)
+{
+    if (!ctx || !d_boxes || !d_counts || !d_ids || !d_nids) return dt_fail(ctx, DT_ERR_ARG, "null argument");
+    if (max_age < 0 || tcap < cap) return dt_fail(ctx, DT_ERR_ARG, "max_age must not be negative and tcap not below cap");
+    ProfScope ps(ctx, "associate", 0.0, 4.0 * n_clips * (double)T * cap * 10.0, "memory");
+    const int rc = launch_associate_mem(ctx->stream, d_boxes, d_counts, n_clips, T, cap, assoc_threshold, max_age, tcap, d_ids, d_nids,
+                                        d_gaps, AssocCarry{nullptr, nullptr, nullptr, nullptr, nullptr, 0});
+    if (rc) return dt_fail(ctx, launch_code(rc), "associate launch failed");
+    return DT_OK;
+}
+
 // ---------------------------------------------------------------------------
 // tracker head (ConvLSTM2D + 1x1)
 // ---------------------------------------------------------------------------
@@ -1921,7 +1940,27 @@ extern "C" int dt_associate_stream(dt_ctx *ctx, const float *d_boxes, const int 
     if (launch_stream_slots(ctx->stream, h_slots, n, S.list.get(), nullptr)) return dt_fail(ctx, DT_ERR_DEVICE, "slot list launch failed");
     ProfScope ps(ctx, "associate", 0.0, 4.0 * n * (double)(T + 2) * cap * 9.0, "stream");
     rc = launch_associate_stream(ctx->stream, d_boxes, d_counts, n, T, cap, assoc_threshold, d_ids, d_nids,
-                                 AssocCarry{S.list.get(), S.boxes.get(), S.ids.get(), S.meta.get()});
+                                 AssocCarry{S.list.get(), S.boxes.get(), S.ids.get(), S.ages.get(), S.meta.get(), S.tcap});
+    if (rc) return dt_fail(ctx, launch_code(rc), "associate launch failed");
+    return DT_OK;
+}
+
+extern "C" int dt_associate_stream_mem(dt_ctx *ctx, const float *d_boxes, const int *d_counts, int n, int T, int cap,
+                                       float assoc_threshold, int max_age, const int *h_slots, int *d_ids, int *d_nids, int *d_gaps)
+{
+    if (!ctx || !d_boxes || !d_counts || !d_ids || !d_nids) return dt_fail(ctx, DT_ERR_ARG, "null argument");
+    if (n <= 0 || T <= 0) return dt_fail(ctx, DT_ERR_ARG, "n and T must be positive");
+    if (max_age < 0) return dt_fail(ctx, DT_ERR_ARG, "max_age must not be negative");
+    int rc = streams_check_list(ctx, h_slots, n);
+    if (rc) return rc;
+    StreamTable &S = ctx->streams;
+    if (cap != S.cap) return dt_fail(ctx, DT_ERR_ARG, "cap %d differs from the stream table's %d", cap, S.cap);
+    // refused before the slot list is written, so that an error launches nothing
+    if (assoc_mem_lds_bytes(T, cap, S.tcap) > 160 * 1024) return dt_fail(ctx, DT_ERR_ARG, "a track table of %d entries does not fit the LDS", S.tcap);
+    if (launch_stream_slots(ctx->stream, h_slots, n, S.list.get(), nullptr)) return dt_fail(ctx, DT_ERR_DEVICE, "slot list launch failed");
+    ProfScope ps(ctx, "associate", 0.0, 4.0 * n * (double)(T + 2) * cap * 10.0, "stream_memory");
+    rc = launch_associate_mem(ctx->stream, d_boxes, d_counts, n, T, cap, assoc_threshold, max_age, S.tcap, d_ids, d_nids, d_gaps,
+                              AssocCarry{S.list.get(), S.boxes.get(), S.ids.get(), S.ages.get(), S.meta.get(), S.tcap});
     if (rc) return dt_fail(ctx, launch_code(rc), "associate launch failed");
     return DT_OK;
 }

@@ -31,6 +31,7 @@ SYMBOLS = [
     "dt_track_xproj_width", "dt_track_detect_xproj", "dt_track_recurrent_xproj",
     "dt_gemm_split_bf16", "dt_gemm_split", "dt_policy_set", "dt_amax_read",
     "dt_stream_open", "dt_stream_reset", "dt_track_stream_forward", "dt_associate_stream",
+    "dt_associate_mem", "dt_stream_open_tracks", "dt_associate_stream_mem",
 ]
 
 _lib = None
@@ -74,6 +75,9 @@ def load_library():
     L.dt_stream_reset.argtypes = [vp, ctypes.POINTER(ci), ci]
     L.dt_track_stream_forward.argtypes = [vp, vp, ci, ci, ci, ctypes.POINTER(ci), vp, vp]
     L.dt_associate_stream.argtypes = [vp, vp, vp, ci, ci, ci, cf, ctypes.POINTER(ci), vp, vp]
+    L.dt_associate_mem.argtypes = [vp, vp, vp, ci, ci, ci, cf, ci, ci, vp, vp, vp]
+    L.dt_stream_open_tracks.argtypes = [vp, ci, ci, ci]
+    L.dt_associate_stream_mem.argtypes = [vp, vp, vp, ci, ci, ci, cf, ci, ctypes.POINTER(ci), vp, vp, vp]
     L.dt_track_row_width.argtypes = [vp]
     L.dt_track_detect.argtypes = [vp, vp, ci, ci, vp]
     L.dt_track_recurrent.argtypes = [vp, vp, ci, ci, vp, vp]
@@ -291,14 +295,22 @@ class Context(object):
         self._check(self.lib.dt_bbox_iou(self.h, _dptr(pairs), n, _dptr(out)), "dt_bbox_iou")
         return out
 
-    def associate(self, boxes, counts, assoc_threshold):
-        """boxes [n_clips,T,cap,8], counts [n_clips,T] int32 -> ids [n_clips,T,cap], nids [n_clips]."""
+    def associate(self, boxes, counts, assoc_threshold, max_age=0, track_cap=None, want_gaps=False):
+        """boxes [n_clips,T,cap,8], counts [n_clips,T] int32 -> ids [n_clips,T,cap], nids [n_clips].
+        max_age > 0, a track_cap or want_gaps: the track-memory rule (dt_associate_mem) -- a track that misses up to max_age frames keeps
+        its id, the table of tracks holds track_cap (None: cap) entries; with want_gaps the result is (ids, nids, gaps [n_clips,T,cap])."""
         t = self.torch
         assert boxes.is_cuda and boxes.is_contiguous() and counts.is_contiguous() and counts.dtype == t.int32
         n_clips, T, cap, _ = boxes.shape
         ids = t.empty((n_clips, T, cap), dtype=t.int32, device=self.device)
         nids = t.empty((n_clips,), dtype=t.int32, device=self.device)
         self._sync_stream()
+        if max_age != 0 or track_cap is not None or want_gaps:
+            gaps = t.empty((n_clips, T, cap), dtype=t.int32, device=self.device) if want_gaps else None
+            self._check(self.lib.dt_associate_mem(self.h, _dptr(boxes), _dptr(counts), n_clips, T, cap, float(assoc_threshold), int(max_age),
+                                                  cap if track_cap is None else int(track_cap), _dptr(ids), _dptr(nids), _dptr(gaps)),
+                        "dt_associate_mem")
+            return (ids, nids, gaps) if want_gaps else (ids, nids)
         self._check(self.lib.dt_associate(self.h, _dptr(boxes), _dptr(counts), n_clips, T, cap,
                                           float(assoc_threshold), _dptr(ids), _dptr(nids)), "dt_associate")
         return ids, nids
@@ -361,10 +373,14 @@ class Context(object):
         slots = [int(v) for v in slots]
         return len(slots), (ctypes.c_int * max(1, len(slots)))(*slots)
 
-    def stream_open(self, n_slots, cap):
-        """(re)allocate the stream slots, every one fresh; cap = box capacity of the association state"""
+    def stream_open(self, n_slots, cap, track_cap=None):
+        """(re)allocate the stream slots, every one fresh; cap = box capacity of the association state, track_cap (None: cap) = entries
+        of a slot's track table (associate_stream with max_age > 0)"""
         self._sync_stream()
-        self._check(self.lib.dt_stream_open(self.h, int(n_slots), int(cap)), "dt_stream_open")
+        if track_cap is None:
+            self._check(self.lib.dt_stream_open(self.h, int(n_slots), int(cap)), "dt_stream_open")
+        else:
+            self._check(self.lib.dt_stream_open_tracks(self.h, int(n_slots), int(cap), int(track_cap)), "dt_stream_open_tracks")
 
     def stream_reset(self, slots=None):
         """the listed slots (None: all) fresh again: zero ConvLSTM state, track ids from 0"""
@@ -392,9 +408,11 @@ class Context(object):
                                                      _dptr(trk), _dptr(det)), "dt_track_stream_forward")
         return (trk, det) if want_det else trk
 
-    def associate_stream(self, boxes, counts, assoc_threshold, slots):
+    def associate_stream(self, boxes, counts, assoc_threshold, slots, max_age=0, want_gaps=False):
         """associate on boxes [n,T,cap,8], counts [n,T]: frame 0 of stream i is matched against the last frame slot slots[i] saw,
-        ids continue across calls, nids [n] = ids opened by the stream since its reset."""
+        ids continue across calls, nids [n] = ids opened by the stream since its reset.
+        max_age > 0 or want_gaps: the track-memory rule (dt_associate_stream_mem) against the slot's track table; with want_gaps the
+        result is (ids, nids, gaps [n,T,cap])."""
         t = self.torch
         assert boxes.is_cuda and boxes.is_contiguous() and counts.is_contiguous() and counts.dtype == t.int32
         n, T, cap, _ = boxes.shape
@@ -404,6 +422,11 @@ class Context(object):
         ids = t.empty((n, T, cap), dtype=t.int32, device=self.device)
         nids = t.empty((n,), dtype=t.int32, device=self.device)
         self._sync_stream()
+        if max_age != 0 or want_gaps:
+            gaps = t.empty((n, T, cap), dtype=t.int32, device=self.device) if want_gaps else None
+            self._check(self.lib.dt_associate_stream_mem(self.h, _dptr(boxes), _dptr(counts), n, T, cap, float(assoc_threshold),
+                                                         int(max_age), arr, _dptr(ids), _dptr(nids), _dptr(gaps)), "dt_associate_stream_mem")
+            return (ids, nids, gaps) if want_gaps else (ids, nids)
         self._check(self.lib.dt_associate_stream(self.h, _dptr(boxes), _dptr(counts), n, T, cap, float(assoc_threshold),
                                                  arr, _dptr(ids), _dptr(nids)), "dt_associate_stream")
         return ids, nids

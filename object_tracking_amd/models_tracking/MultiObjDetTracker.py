@@ -125,6 +125,11 @@ class MultiObjDetTracker(object):
     # build-defined (no reference counterpart): IoU a frame-t box needs with a
     # frame-(t-1) box of the same label to inherit its track id
     ASSOC_THRESHOLD = 0.3
+    # build-defined track memory: frames a track may go without a box and still keep its id (0: a box can
+    # inherit an id from the previous frame only), and the entries of the table of tracks (None: the box capacity `cap`;
+    # a table of at most 64 entries, which needs cap <= 64 too, runs in registers)
+    MAX_AGE = 0
+    TRACK_CAP = None
 
     train_image_folder = 'data/MOT17/MOT17Det/train/'
     train_annot_folder = 'data/MOT17Ann/train/'
@@ -193,16 +198,20 @@ class MultiObjDetTracker(object):
           counts [n_clips,T]        boxes per frame
           ids    [n_clips,T,cap]    track ids (-1 in unused slots), per clip from 0
           nids   [n_clips]          ids opened per clip
+          gaps   [n_clips,T,cap]    only with MAX_AGE > 0: frames the box's track had missed (0 unbroken, -1 new id / unused)
         One dt_track_forward (YOLOv2 x T, ConvLSTM recurrence, 1x1), one dt_decode
         over all frames, one dt_associate."""
         return self.decode_and_associate(self.model.forward(frames, want_det=False), cap=cap)
 
     # ---- streaming (addition): ConvLSTM state and track ids carried across calls ----
-    def open_streams(self, n_slots, cap=None):
-        """Allocate n_slots stream slots on the device (every one fresh).  cap: box capacity per frame, as in track_clips."""
+    def open_streams(self, n_slots, cap=None, track_cap=None):
+        """Allocate n_slots stream slots on the device (every one fresh).  cap: box capacity per frame, as in track_clips;
+        track_cap: entries of a slot's track table (None: TRACK_CAP, and with that None too: cap)."""
         if cap is None:
             cap = self.GRID_H * self.GRID_W * self.BOX
-        self.model.ctx.stream_open(n_slots, cap)
+        if track_cap is None:
+            track_cap = self.TRACK_CAP
+        self.model.ctx.stream_open(n_slots, cap, track_cap=track_cap)
         self._stream_cap = cap
 
     def reset_streams(self, slots=None):
@@ -223,6 +232,9 @@ class MultiObjDetTracker(object):
         r = ctx.decode(flat, self.OBJ_THRESHOLD, self.NMS_THRESHOLD, self.ANCHORS, len(self.LABELS), cap=cap)
         boxes = r["boxes"].reshape(n, T, cap, mi355_dt.DT_BOX_FLOATS)
         counts = r["counts"].reshape(n, T)
+        if self.MAX_AGE > 0:
+            ids, nids, gaps = ctx.associate_stream(boxes, counts, self.ASSOC_THRESHOLD, slots, max_age=self.MAX_AGE, want_gaps=True)
+            return dict(boxes=boxes, counts=counts, ids=ids, nids=nids, gaps=gaps, netout=trk)
         ids, nids = ctx.associate_stream(boxes, counts, self.ASSOC_THRESHOLD, slots)
         return dict(boxes=boxes, counts=counts, ids=ids, nids=nids, netout=trk)
 
@@ -237,6 +249,10 @@ class MultiObjDetTracker(object):
         r = ctx.decode(flat, self.OBJ_THRESHOLD, self.NMS_THRESHOLD, self.ANCHORS, len(self.LABELS), cap=cap)
         boxes = r["boxes"].reshape(n_clips, T, cap, mi355_dt.DT_BOX_FLOATS)
         counts = r["counts"].reshape(n_clips, T)
+        if self.MAX_AGE > 0:
+            ids, nids, gaps = ctx.associate(boxes, counts, self.ASSOC_THRESHOLD, max_age=self.MAX_AGE, track_cap=self.TRACK_CAP,
+                                            want_gaps=True)
+            return dict(boxes=boxes, counts=counts, ids=ids, nids=nids, gaps=gaps, netout=trk)
         ids, nids = ctx.associate(boxes, counts, self.ASSOC_THRESHOLD)
         return dict(boxes=boxes, counts=counts, ids=ids, nids=nids, netout=trk)
 
@@ -256,6 +272,7 @@ class MultiObjDetTracker(object):
         boxes = res["boxes"][clip].cpu().numpy()
         counts = res["counts"][clip].cpu().numpy()
         ids = res["ids"][clip].cpu().numpy()
+        gaps = res["gaps"][clip].cpu().numpy() if res.get("gaps") is not None else None
         out = []
         for t in range(boxes.shape[0]):
             n = min(int(counts[t]), boxes.shape[1])
@@ -266,6 +283,8 @@ class MultiObjDetTracker(object):
                 bb.label = int(lab)
                 bb.score = sc
                 bb.track_id = int(ids[t, i])
+                # frames the track had gone without a box (0: unbroken, -1: a new id); None when the result carries no gaps (MAX_AGE = 0)
+                bb.track_gap = int(gaps[t, i]) if gaps is not None else None
                 lst.append(bb)
             out.append(lst)
         return out
