@@ -403,6 +403,7 @@ struct PendingEvent {
 struct DevBuf {
     void *p = nullptr;
     size_t bytes = 0;
+    long long layout = 0;      // ws_get_padded: the row layout whose pad columns are known to be zero (0: none yet)
 };
 
 // Owner of one device allocation: hipFree in the destructor and in reset(); move-only.  It does NOT synchronise: whoever releases memory that
@@ -598,6 +599,8 @@ struct dt_ctx {
 
 int dt_fail(dt_ctx *ctx, int code, const char *fmt, ...);
 float *ws_get(dt_ctx *ctx, const char *name, size_t bytes, bool zero_on_grow = false);
+// rows of `width` floats of which only the first `used` are ever written: the pad columns [used, width) read zero
+float *ws_get_padded(dt_ctx *ctx, const char *name, size_t bytes, int width, int used);
 
 #define HIP_TRY(ctx, expr)                                                                       \
     do {                                                                                         \

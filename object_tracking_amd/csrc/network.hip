@@ -127,9 +127,36 @@ float *ws_get(dt_ctx *ctx, const char *name, size_t bytes, bool zero_on_grow)
             return nullptr;
         }
         b.bytes = bytes;
+        b.layout = 0;
         if (zero_on_grow) (void)hipMemsetAsync(b.p, 0, bytes, ctx->stream);
     }
     return static_cast<float *>(b.p);
+}
+
+// A workspace whose rows carry pad columns that no kernel writes and the GEMM behind it reads (trk_z, tiny_x): zero when it is allocated, and zeroed once
+// more when a call arrives with another row layout than the one before it -- after dt_tracker_load / dt_tiny_load for another class count or D the new
+// rows' pads lie on bytes that held activations (0 * NaN is NaN, and the fp16 form's max |x| is taken over the padded width).  Calls that keep the
+// layout -- the steady state -- add no launch: the pads sit at the same offsets whatever the number of rows.
+float *ws_get_padded(dt_ctx *ctx, const char *name, size_t bytes, int width, int used)
+{
+    float *p = ws_get(ctx, name, bytes, /*zero_on_grow=*/true);
+    if (!p) return nullptr;
+    DevBuf &b = ctx->ws[name];
+    const long long layout = ((long long)width << 32) | (unsigned)used;
+    if (b.layout != layout) {
+        if (b.layout != 0 && width > used) {      // (0: allocated and zeroed just now; rows without pad columns have nothing to keep zero)
+            if (ctx->capturing) {   // a memset recorded into a graph would run at every replay (graphed() runs every shape once uncaptured first: not reached today)
+                dt_fail(ctx, DT_ERR_STATE, "workspace %s would be zeroed during graph capture", name);
+                return nullptr;
+            }
+            if (hipMemsetAsync(b.p, 0, b.bytes, ctx->stream) != hipSuccess) {
+                dt_fail(ctx, DT_ERR_DEVICE, "hipMemsetAsync failed for workspace %s", name);
+                return nullptr;
+            }
+        }
+        b.layout = layout;
+    }
+    return p;
 }
 
 ProfScope::ProfScope(dt_ctx *c, const char *name, double flops, double bytes, const char *tag)
@@ -1891,7 +1918,7 @@ static int track_forward_internal(dt_ctx *ctx, const void *d_frames, int frames_
     int carry = h_slots ? CARRY_FRESH : CARRY_NONE;
     for (int i = 0; h_slots && i < n; ++i)
         if (S.warm[h_slots[i]]) carry = CARRY_WARM;
-    float *z = ws_get(ctx, "trk_z", (size_t)F * GG * Cx * sizeof(float), /*zero_on_grow=*/true);
+    float *z = ws_get_padded(ctx, "trk_z", (size_t)F * GG * Cx * sizeof(float), Cx, 1024 + Cb);
     if (!z) return DT_ERR_DEVICE;
     int rc = detect_internal(ctx, d_frames, frames_dtype, F, Dest{z, Cx}, Dest{z + 1024, Cx}, /*skip23=*/!d_det && xproj_merged(ctx, F, gh, gw));
     if (rc) return rc;
@@ -2011,7 +2038,7 @@ extern "C" int dt_track_detect_xproj(dt_ctx *ctx, const void *d_frames, int fram
     if (!ctx->trk_loaded) return dt_fail(ctx, DT_ERR_STATE, "tracker weights not loaded");
     if (n_frames <= 0) return dt_fail(ctx, DT_ERR_ARG, "n_frames must be positive");
     const int gh = ctx->image_h / 32, gw = ctx->image_w / 32, GG = gh * gw, Cx = ctx->trk_cx;
-    float *z = ws_get(ctx, "trk_z", (size_t)n_frames * GG * Cx * sizeof(float), /*zero_on_grow=*/true);
+    float *z = ws_get_padded(ctx, "trk_z", (size_t)n_frames * GG * Cx * sizeof(float), Cx, 1024 + ctx->cb);
     if (!z) return DT_ERR_DEVICE;
     int rc = detect_internal(ctx, d_frames, frames_dtype, n_frames, Dest{z, Cx}, Dest{z + 1024, Cx}, /*skip23=*/!d_det && xproj_merged(ctx, n_frames, gh, gw));
     if (rc) return rc;
@@ -2101,7 +2128,7 @@ extern "C" int dt_tiny_sequence(dt_ctx *ctx, const float *d_x, int n_seq, int T,
     if (n_seq <= 0 || T <= 0) return dt_fail(ctx, DT_ERR_ARG, "n_seq and T must be positive");
     const int U = ctx->tiny_U, D = ctx->tiny_D, Dp = ctx->tiny_Dpad, N4 = 4 * U;
     const int R = n_seq * T;
-    float *x = ws_get(ctx, "tiny_x", (size_t)R * Dp * sizeof(float), /*zero_on_grow=*/true);
+    float *x = ws_get_padded(ctx, "tiny_x", (size_t)R * Dp * sizeof(float), Dp, D);
     float *xproj = ws_get(ctx, "tiny_xproj", (size_t)R * N4 * sizeof(float));
     float *hseq = ws_get(ctx, "tiny_h", (size_t)R * U * sizeof(float));
     float *cst = ws_get(ctx, "tiny_c", (size_t)n_seq * U * sizeof(float));
