@@ -105,6 +105,8 @@ struct WinoArgs {
     // P = (ts+2)^2 Winograd positions
     int B, H, W, th, tw, Mt, ts;
     int g;   // frames per side of the virtual mosaic the tiles live on (1: one frame; winograd.hip:vpixel)
+    int ph, pw;   // g > 1: the mosaic's frame pitch, rows / columns from one frame's origin to the next (>= H + 1 / W + 1: at least one separator of zeros;
+                  // EVEN where out2 is set, so that no 2x2 pooling window straddles a tile or a frame -- network.hip:wino_geometry)
     // input transform: in (NHWC, pixel stride in_ld, image stride in_bs), C channels -> v [P][Mt][C]
     const float *in;
     long long in_bs;
@@ -475,7 +477,7 @@ struct Policy {
     int wino_tile = 0;       // DT_WINO_TILE: 2/4/6 for every layer; 0 = default (6, recurrent convolution 4)
     int wino_mint = 0;       // DT_WINO_MINT: Winograd tiles from which a launch takes the transforms; 0 = the per-tile-size default (wino_runs)
     double wino_ws_gb = 96.0;   // DT_WINO_WS_GB: V + M' workspace above this -> direct form
-    int mosaic = -1;         // DT_WINO_MOSAIC: 1 never, 2/3/4 force, -1 = fewest tiles
+    int mosaic = -1;         // DT_WINO_MOSAIC: 1 never, 2 .. 6 force, -1 = fewest tiles
     int fused4 = 1;          // DT_WINO_FUSED4: the fused F(4x4) kernel (wino4s_fused.hip): 0 never / 1 conv_2 / 3 / 5 (Cin <= 64) from 1024
                              //                 blocks / 3 also conv_6 / 8 (Cin 128) / 2 any eligible layer at any size.  Read at weight load (0) and per launch
     int trk_merge = 1;       // DT_TRK_MERGE: the ConvLSTM2D input projection reads conv_feat only -- conv_23 (1x1, linear: x_bbox = W23 feat + b23) is folded into the

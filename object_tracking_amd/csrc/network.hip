@@ -904,22 +904,29 @@ struct WinoIO {
 };
 
 // Tile geometry of a Winograd launch.  Mosaic factor g: g x g frames with zero separators share one virtual image
-// (winograd.hip:vpixel) when that needs fewer tiles per frame (13x13 F(4x4): 12.25 instead of 16); pooled outputs need
-// frame-aligned tiles.
-struct WinoGeom { int g, th, tw, Mt; };
+// (winograd.hip:vpixel) when that needs fewer tiles per frame (13x13 F(4x4): 12.25 instead of 16).  The frame pitch ph / pw
+// belongs to the launch: H + 1 / W + 1 (one separator), and the next EVEN number where the launch pools, so that frame and
+// tile origins are even and no 2x2 pooling window straddles a tile or a frame (winograd.hip:pooled_pixel).  g runs to 6:
+//   13x13 F(6x6): g = 3, 42 = 7 tiles, 5.44 per frame (9);   26x26: g = 2, 54 = 9 tiles, 20.25 (25);   13x13 F(4x4): g = 2, 28 = 7 tiles, 12.25 (16);
+//   26x26 pooled (conv_13): pitch 28, g = 3, 84 = 14 tiles, 21.78 (25);   52x52 (conv_6): pitch 53, g = 6, 318 = 53 tiles, 78.03 (81);
+//   52x52 pooled (conv_8): pitch 54 = 9 tiles for every g: stays at 81.
+// The rule prices whole groups: a ragged last group costs a whole mosaic's tiles (B >= g * g keeps it to a factor below 2).
+struct WinoGeom { int g, ph, pw, th, tw, Mt; };
 static WinoGeom wino_geometry(const dt_ctx *ctx, int ts, int B, int H, int W, bool pooled)
 {
     WinoGeom q;
     q.g = 1;
-    const int g_env = ctx->pol.mosaic;   // 1: never (tests, A/B), 2 / 3 / 4: force
+    q.ph = pooled ? (H + 2) & ~1 : H + 1;
+    q.pw = pooled ? (W + 2) & ~1 : W + 1;
+    const int g_env = ctx->pol.mosaic;   // 1: never (tests, A/B), 2 .. 6: force
     double best = (double)((H + ts - 1) / ts) * ((W + ts - 1) / ts);
-    for (int g = 2; g <= 4 && !pooled && g_env != 1; ++g) {
-        const double t = (double)((g * (H + 1) + ts - 1) / ts) * ((g * (W + 1) + ts - 1) / ts) / (g * g);
+    for (int g = 2; g <= 6 && g_env != 1; ++g) {
+        const double t = (double)((g * q.ph + ts - 1) / ts) * ((g * q.pw + ts - 1) / ts) / (g * g);
         if ((t < best * 0.97 && B >= g * g) || g_env == g) { best = t; q.g = g; }
     }
     if (q.g == 1) { q.th = (H + ts - 1) / ts; q.tw = (W + ts - 1) / ts; q.Mt = B * q.th * q.tw; }
     else {
-        q.th = (q.g * (H + 1) + ts - 1) / ts; q.tw = (q.g * (W + 1) + ts - 1) / ts;
+        q.th = (q.g * q.ph + ts - 1) / ts; q.tw = (q.g * q.pw + ts - 1) / ts;
         q.Mt = ((B + q.g * q.g - 1) / (q.g * q.g)) * q.th * q.tw;
     }
     return q;
@@ -966,7 +973,7 @@ static int run_wino(dt_ctx *ctx, const WinoWeights &wts, const WinoChoice &wc, c
                             : conv_leaves(EPI_POOL, io.out2, io.out2_ld, nullptr, 0, (long long)B * H * W, N));
     WinoArgs w{};
     w.B = B; w.H = H; w.W = W; w.ts = ts;
-    w.g = wc.q.g; w.th = wc.q.th; w.tw = wc.q.tw; w.Mt = wc.q.Mt;
+    w.g = wc.q.g; w.ph = wc.q.ph; w.pw = wc.q.pw; w.th = wc.q.th; w.tw = wc.q.tw; w.Mt = wc.q.Mt;
     prof_count(ctx, "wino_mosaic:g%d_ts%d", w.g, ts);   // which mosaic / tile size a launch took
     const int P = (ts + 2) * (ts + 2);
     const size_t mt = (size_t)w.Mt;

@@ -115,9 +115,12 @@ template <int TS, typename T> __device__ __forceinline__ void at_1d(T *m)
 }
 
 // Tiles live on a VIRTUAL image: one frame (g = 1), or a g x g mosaic of frames laid out with a pitch of
-// H+1 / W+1, i.e. with one row / column of zeros between neighbours.  The zero separator is exactly the
+// ph / pw (WinoArgs) = H+1 / W+1, i.e. with one row / column of zeros between neighbours.  The zero separator is exactly the
 // 'same' padding both neighbours need, so tiles may straddle frames: a 13x13 grid costs (2*14/4)^2 / 4 =
 // 12.25 F(4x4,3x3) tiles per frame instead of the 16 that cover 16x16 (-23 % GEMM rows and transform traffic).
+// A launch with a pooled output takes the next EVEN pitch (two separator rows where H is even: one more row of zeros does
+// 'same' padding no harm): frame origins and tile origins (multiples of the even tile size) are then even virtual coordinates,
+// so a 2x2 pooling window lies inside one tile and either inside one frame or inside the separators (pooled_pixel).
 struct TileId {
     int grp, ty, tx;   // frame group (g*g frames), tile row / column on its virtual image
 };
@@ -139,9 +142,49 @@ __device__ __forceinline__ bool vpixel(const WinoArgs &p, int grp, int vh, int v
         b = grp; h = vh; w = vw;
         return vh < p.H && vw < p.W;
     }
-    const int fy = vh / (p.H + 1), fx = vw / (p.W + 1);
-    h = vh - fy * (p.H + 1);
-    w = vw - fx * (p.W + 1);
+    const int fy = vh / p.ph, fx = vw / p.pw;
+    h = vh - fy * p.ph;
+    w = vw - fx * p.pw;
+    b = (grp * p.g + fy) * p.g + fx;
+    return fy < p.g && fx < p.g && h < p.H && w < p.W && b < p.B;
+}
+// the 2x2 pooling window whose top-left corner is virtual (vh, vw), both even -> frame b and pooled pixel (h2, w2) of its H/2 x W/2 output;
+// false = the window lies in the separators / past the image (or hangs over the last row / column of an odd frame: MaxPooling2D drops it)
+__device__ __forceinline__ bool pooled_pixel(const WinoArgs &p, int grp, int vh, int vw, int &b, int &h2, int &w2)
+{
+    int h = 0, w = 0;
+    const bool ok = vpixel(p, grp, vh, vw, b, h, w);
+    h2 = h >> 1; w2 = w >> 1;
+    return ok && h2 < (p.H >> 1) && w2 < (p.W >> 1);
+}
+// The thread-per-item output kernel walks its tile instead: where the tile starts -- frame row / column of its group and the pixel inside that
+// frame, ONE division per axis and tile -- and from there in steps of one pixel (two for the pooling windows) with a carry into the next frame.
+// The same mapping as vpixel / pooled_pixel (g == 1: one frame, no carry); the divisions per pixel cost the kernel a third of its wavefronts.
+struct TileOrg {
+    int fy, h, fx, w;   // frame row / column in the group, pixel in the frame of the tile's first output
+    int ph, pw;         // the pitch the walk carries at
+};
+template <int TS> __device__ __forceinline__ TileOrg tile_org(const WinoArgs &p, const TileId &t)
+{
+    TileOrg o;
+    if (p.g == 1) {
+        o.fy = 0; o.h = TS * t.ty; o.fx = 0; o.w = TS * t.tx;
+        o.ph = o.pw = 0x7fffffff;
+    } else {
+        o.fy = TS * t.ty / p.ph; o.h = TS * t.ty - o.fy * p.ph;
+        o.fx = TS * t.tx / p.pw; o.w = TS * t.tx - o.fx * p.pw;
+        o.ph = p.ph; o.pw = p.pw;
+    }
+    return o;
+}
+// d = 1, or 2 from an even x at an even pitch: one carry at the most
+__device__ __forceinline__ void mosaic_step(int &f, int &x, int pitch, int d)
+{
+    x += d;
+    if (x >= pitch) { x -= pitch; ++f; }
+}
+__device__ __forceinline__ bool mosaic_pixel(const WinoArgs &p, int grp, int fy, int h, int fx, int w, int &b)
+{
     b = (grp * p.g + fy) * p.g + fx;
     return fy < p.g && fx < p.g && h < p.H && w < p.W && b < p.B;
 }
@@ -302,6 +345,7 @@ template <int TS, int V> __global__ __launch_bounds__(WINO_THREADS) void wino_ou
         const int tile = (int)(it / nq);
         const int c = (int)(it - (long long)tile * nq) * V;
         const TileId t = tile_id(p, tile);
+        const TileOrg o = tile_org<TS>(p, t);
         T m[NI][NI];
         wino_at_m_a<TS, V>(p.m + (long long)tile * p.m_ld + c, plane, m);
         const T bv = p.bias ? vload<V>(p.bias + c) : vzero<V>();
@@ -315,12 +359,14 @@ template <int TS, int V> __global__ __launch_bounds__(WINO_THREADS) void wino_ou
                 m[i][j] = v;
             }
         if (p.out) {
+            int fy = o.fy, h = o.h;
 #pragma unroll
-            for (int i = 0; i < TS; ++i)
+            for (int i = 0; i < TS; ++i) {
+                int fx = o.fx, w = o.w;
 #pragma unroll
                 for (int j = 0; j < TS; ++j) {
-                    int b, h, w;
-                    if (vpixel(p, t.grp, TS * t.ty + i, TS * t.tx + j, b, h, w)) {
+                    int b;
+                    if (mosaic_pixel(p, t.grp, fy, h, fx, w, b)) {
                         T v = m[i][j];
                         if (p.bias16) {    // (slope 1: launcher) border pixels add their case's correction to the interior bias already in v
                             const int k = wino_border_case(p, h, w);
@@ -332,16 +378,23 @@ template <int TS, int V> __global__ __launch_bounds__(WINO_THREADS) void wino_ou
                         }
                         vstore_nt<V>(p.out + (long long)b * p.out_bs + (long long)(h * p.W + w) * p.out_ld + c, v);
                     }
+                    mosaic_step(fx, w, o.pw, 1);
                 }
+                mosaic_step(fy, h, o.ph, 1);
+            }
         }
-        if (p.out2) {   // MaxPooling2D(2,2): H and W are even whenever the reference pools; g == 1 (launcher)
+        if (p.out2) {   // MaxPooling2D(2,2): H and W are even whenever the reference pools; the pitch of a mosaic is even (launcher), so a window
+                        // lies in one tile and in one frame, or in the separators
             const int H2 = p.H >> 1, W2 = p.W >> 1;
+            int fy = o.fy, h = o.h;
 #pragma unroll
-            for (int i = 0; i < TS / 2; ++i)
+            for (int i = 0; i < TS / 2; ++i) {
+                int fx = o.fx, w = o.w;
 #pragma unroll
                 for (int j = 0; j < TS / 2; ++j) {
-                    const int h2 = (TS / 2) * t.ty + i, w2 = (TS / 2) * t.tx + j;
-                    if (h2 < H2 && w2 < W2) {
+                    int b;
+                    const int h2 = h >> 1, w2 = w >> 1;
+                    if (mosaic_pixel(p, t.grp, fy, h, fx, w, b) && h2 < H2 && w2 < W2) {
                         T mx;
 #pragma unroll
                         for (int e = 0; e < V; ++e)
@@ -351,9 +404,12 @@ template <int TS, int V> __global__ __launch_bounds__(WINO_THREADS) void wino_ou
 #pragma unroll
                             for (int e = 0; e < V; ++e) am = fmaxf(am, fabsf(lane_of<V>(mx, e)));
                         }
-                        vstore<V>(p.out2 + ((long long)(t.grp * H2 + h2) * W2 + w2) * p.out2_ld + c, mx);
+                        vstore<V>(p.out2 + (((long long)b * H2 + h2) * W2 + w2) * p.out2_ld + c, mx);
                     }
+                    mosaic_step(fx, w, o.pw, 2);
                 }
+                mosaic_step(fy, h, o.ph, 2);
+            }
         }
     }
     if (p.amax_out) dt_amax_publish(p.amax_out, am);
@@ -672,7 +728,7 @@ __global__ __launch_bounds__(WINO_THREADS) void wino_output_coop6_kernel(WinoArg
                 }
             }
         }
-        if (p.out2) {   // MaxPooling2D(2,2) (g == 1: launcher): output rows 2k, 2k+1 sit in neighbouring lanes
+        if (p.out2) {   // MaxPooling2D(2,2) (even mosaic pitch: launcher): output rows 2k, 2k+1 sit in neighbouring lanes
             const int H2 = p.H >> 1, W2 = p.W >> 1;
 #pragma unroll
             for (int k = 0; k < 3; ++k) {
@@ -682,13 +738,13 @@ __global__ __launch_bounds__(WINO_THREADS) void wino_output_coop6_kernel(WinoArg
                     const float a = fmaxf(lane_of<4>(row[2 * k], e), lane_of<4>(row[2 * k + 1], e));
                     set_lane<4>(mx, e, fmaxf(a, __shfl_xor(a, 1)));
                 }
-                const int h2 = 3 * t.ty + (sub >> 1), w2 = 3 * t.tx + k;
-                if (live && sub < 6 && !(sub & 1) && h2 < H2 && w2 < W2) {
+                int b, h2, w2;
+                if (live && sub < 6 && !(sub & 1) && pooled_pixel(p, t.grp, 6 * t.ty + sub, 6 * t.tx + 2 * k, b, h2, w2)) {
                     if (am_pool) {
 #pragma unroll
                         for (int e = 0; e < 4; ++e) am = fmaxf(am, fabsf(lane_of<4>(mx, e)));
                     }
-                    vstore<4>(p.out2 + ((long long)(t.grp * H2 + h2) * W2 + w2) * p.out2_ld + c, mx);
+                    vstore<4>(p.out2 + (((long long)b * H2 + h2) * W2 + w2) * p.out2_ld + c, mx);
                 }
             }
         }
@@ -805,9 +861,17 @@ int launch_wino_h2_pack(hipStream_t st, const float *u, int P, int npad, int K, 
 // a launch this small is latency-bound on the one-thread-per-item kernels: take the cooperative form
 static inline bool wino_coop_wanted(long long items_pairs) { return items_pairs < (long long)WINO_COOP_MAX_ITEMS; }
 
+// a mosaic needs at least one separator row / column between frames, and an even pitch where the launch pools (pooled_pixel)
+static inline bool wino_pitch_ok(const WinoArgs &a)
+{
+    if (a.g < 1) return false;
+    if (a.g == 1) return true;
+    return a.ph > a.H && a.pw > a.W && !(a.out2 && ((a.ph | a.pw) & 1));
+}
+
 int launch_wino_input(hipStream_t st, const WinoArgs &a)
 {
-    if (a.C % 4 || a.in_ld % 4 || a.Mt <= 0 || (a.ts != 2 && a.ts != 4 && a.ts != 6) || a.g < 1) return 2;
+    if (a.C % 4 || a.in_ld % 4 || a.Mt <= 0 || (a.ts != 2 && a.ts != 4 && a.ts != 6) || !wino_pitch_ok(a)) return 2;
     if (a.v_s3 && a.nt == 2) {      // the fp16 form: the cooperative 8-channel producer only
         if ((a.ts != 6 && a.ts != 4) || a.C % 32 || a.Mp < a.Mt || !a.amax) return 2;
         const long long wgs = ((long long)((a.Mt + 3) & ~3) * (a.C / 8) + WINO_S3IN_THREADS / 8 - 1) / (WINO_S3IN_THREADS / 8);
@@ -851,7 +915,7 @@ bool wino_output_fills_amax(const WinoArgs &a, int gates)
 }
 int launch_wino_output(hipStream_t st, const WinoArgs &a, int gates)
 {
-    if (a.m_ld % 4 || a.Mt <= 0 || (a.ts != 2 && a.ts != 4 && a.ts != 6) || a.g < 1 || (a.out2 && a.g != 1)) return 2;
+    if (a.m_ld % 4 || a.Mt <= 0 || (a.ts != 2 && a.ts != 4 && a.ts != 6) || !wino_pitch_ok(a)) return 2;
     if (gates) {
         if (a.N % 128 || a.out_ld % 4 || a.c_ld % 4 || a.xp_ld % 4) return 2;
         if (a.ts == 6)
