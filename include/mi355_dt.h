@@ -50,6 +50,7 @@ DT_API const char *dt_last_error(dt_ctx *ctx);
 DT_API int dt_set_stream(dt_ctx *ctx, void *hip_stream);
 /* ABI version of this header: major*100+minor (1.08: 1.07 + dt_amax_read, and later the four stream entries dt_stream_open, dt_stream_reset,
  * dt_track_stream_forward, dt_associate_stream, and the three track-memory entries dt_associate_mem, dt_stream_open_tracks, dt_associate_stream_mem
+ * and the four tiny-tracker stream entries dt_tiny_stream_open, dt_tiny_stream_reset, dt_tiny_stream_sequence, dt_tiny_stream_forward
  * -- additions only, the number stayed; 1.07: 1.06 + dt_gemm_split, dt_policy_set) */
 DT_API int dt_abi_version(void);
 
@@ -260,6 +261,26 @@ DT_API int dt_tiny_forward(dt_ctx *ctx, const float *d_feat, const float *d_det,
 DT_API int dt_tiny_features(dt_ctx *ctx, const float *d_feat, const float *d_det, int n_rows,
                      int fh, int fw, int fc, int pool, float *d_x);
 DT_API int dt_tiny_sequence(dt_ctx *ctx, const float *d_x, int n_seq, int T, float *d_out);
+
+/* ---- streaming single-object trackers: the LSTM state h, c [U] carried across calls (addition; the contract of the stream block above) ---- *
+ * A table of TINY STREAM SLOTS, apart from dt_stream_open's (a context may hold both; neither touches the other): per slot h (two copies,
+ * used alternately), c and a counter of frames seen.  A tiny stream fed in chunks of any sizes gives what dt_tiny_sequence / dt_tiny_forward
+ * give on the concatenation of those chunks as one sequence, bit for bit; a FRESH slot (after dt_tiny_stream_open / dt_tiny_stream_reset, and
+ * after dt_tiny_load, which makes every slot fresh before it replaces a weight) is indistinguishable from a stateless call.
+ * h_slots: a HOST array of n DISTINCT numbers in [0, n_slots), consumed before the call returns; sequence i of the call lives in slot
+ * h_slots[i].  The streams of a call need not be in step; fresh and warm slots may be mixed in one call.
+ * DT_ERR_STATE: before dt_tiny_load or before dt_tiny_stream_open (a load for other units would close the table; units is 512 today, so
+ * no load does).  DT_ERR_ARG: a duplicate or out-of-range
+ * slot, n <= 0, T <= 0, n_slots <= 0.  An error leaves every slot as it was.
+ *   dt_tiny_stream_open:     (re)allocates the table, every slot fresh; needs loaded weights
+ *   dt_tiny_stream_reset:    the listed slots fresh again; h_slots == NULL: all of them.  Stream-ordered, no host wait
+ *   dt_tiny_stream_sequence: dt_tiny_sequence on d_x [n, T, D], sequence i continuing from -- and leaving its state in -- slot h_slots[i]
+ *   dt_tiny_stream_forward:  dt_tiny_features followed by dt_tiny_stream_sequence (arguments as dt_tiny_forward) */
+DT_API int dt_tiny_stream_open(dt_ctx *ctx, int n_slots);
+DT_API int dt_tiny_stream_reset(dt_ctx *ctx, const int *h_slots, int n);          /* h_slots == NULL: all */
+DT_API int dt_tiny_stream_sequence(dt_ctx *ctx, const float *d_x, int n, int T, const int *h_slots, float *d_out);
+DT_API int dt_tiny_stream_forward(dt_ctx *ctx, const float *d_feat, const float *d_det, int n, int T,
+                                  int fh, int fw, int fc, int pool, const int *h_slots, float *d_out);
 
 /* generate_heatmap_feat (utility/utils.py:53-58) applied as the data generator does
  * (preprocessing.py:455): d_box4 [n,4] centre-format (cx,cy,w,h) -> d_heat [n, hs*hs] of 0/1.

@@ -386,6 +386,25 @@ int launch_lstm_step(hipStream_t st, const float *xproj /*[B][4U] gate-interleav
                      float *h_out, long long ho_bs, int B, int U);
 int launch_lstm_step0(hipStream_t st, const float *xproj, long long xp_bs, float *cstate, float *h_out,
                       long long ho_bs, int B, int U);
+// The tiny trackers' stream slots (dt_tiny_stream_open; TinyStreamTable below): meta row of a slot = frames the slot has seen (0 = fresh:
+// its h / c rows read as zeros whatever they hold), which of the two h copies is current, two spare words.  One row is one int4, like
+// STREAM_META, so launch_stream_slots resets these rows too.
+enum { TSM_FRAMES = 0, TSM_CUR = 1, TSM_META = 4 };
+static_assert(TSM_META == STREAM_META, "launch_stream_slots zeroes one int4 per slot in either table");
+struct LstmSlots {
+    const int *list;     // [B] device: slot of track b of the call
+    const int *meta;     // [n_slots][TSM_META]
+    float *h;            // [2][n_slots][U]
+    float *c;            // [n_slots][U]
+    long long copy;      // floats from one h copy to the other: n_slots * U
+    int first, last;     // the launch is the first / last step of its call (T = 1: both)
+};
+// launch_lstm_step with the state rows addressed per track through the slot list: c in the table row at every step, h_prev from the table
+// on the first step (h_prev may be null there), h_t into the table's other copy on the last one
+int launch_lstm_step_stream(hipStream_t st, const float *xproj, long long xp_bs, const float *h_prev, long long h_bs,
+                            const float *Ur_packed, float *h_out, long long ho_bs, int B, int U, const LstmSlots &s);
+// behind the last step: the listed slots' current copy flips and their frame counters advance by T
+int launch_lstm_stream_advance(hipStream_t st, const int *list, int *meta, int B, int T);
 int launch_dense_sigmoid(hipStream_t st, const float *h, long long h_bs, const float *Wd /*[U][O]*/,
                          const float *bd, int B, int U, int O, float *out, long long out_bs);
 
@@ -542,6 +561,17 @@ struct StreamTable {
     std::vector<char> warm;    // host mirror of meta[SM_FRAMES] != 0: decides between the gates-only launch and a full step at t = 0
 };
 
+// The stream slots of the tiny trackers (dt_tiny_stream_open): the per-object LSTM's state, carried from one call to the next.  Apart from
+// `streams`: a context may hold both tables, and no entry of one touches the other.
+struct TinyStreamTable {
+    int n_slots = 0;
+    int U = 0;                 // units of the model the table was opened under
+    DevMem<float> h;           // [2][n_slots][U]: two copies, used alternately -- a call reads meta[TSM_CUR] and writes the other (recurrent.hip)
+    DevMem<float> c;           // [n_slots][U]
+    DevMem<int> meta;          // [n_slots][TSM_META]
+    DevMem<int> list;          // [n_slots]: the slot list of the running call (never a kernel argument of a captured launch)
+};
+
 struct dt_ctx {
     std::string err;
     Policy pol;
@@ -581,6 +611,7 @@ struct dt_ctx {
     int tiny_D = 0, tiny_Dpad = 0, tiny_U = 0, tiny_O = 0, tiny_Opad = 0;
     DevMem<float> tiny_wx, tiny_bx, tiny_ur, tiny_wd, tiny_bd;
     StreamTable streams;
+    TinyStreamTable tiny_streams;
     // workspaces (grown on demand)
     std::map<std::string, DevBuf> ws;
     int last_batch = 0;

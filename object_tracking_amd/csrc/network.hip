@@ -48,6 +48,21 @@ static void graphs_clear(dt_ctx *ctx)
     ctx->graph_tags.clear();
 }
 
+// the graphs whose key ends in `suffix` only (a table of their launches' pointers is about to be replaced).  The CALLER has synchronised
+// ctx->stream: replays run there
+static void graphs_drop(dt_ctx *ctx, const char *suffix)
+{
+    const std::string suf(suffix);
+    const auto ends = [&](const std::string &k) { return k.size() >= suf.size() && k.compare(k.size() - suf.size(), suf.size(), suf) == 0; };
+    for (auto it = ctx->graphs.begin(); it != ctx->graphs.end();) {
+        if (!ends(it->first)) { ++it; continue; }
+        (void)hipGraphExecDestroy(it->second);
+        it = ctx->graphs.erase(it);
+    }
+    for (auto it = ctx->graph_seen.begin(); it != ctx->graph_seen.end();) it = ends(it->first) ? ctx->graph_seen.erase(it) : std::next(it);
+    for (auto it = ctx->graph_tags.begin(); it != ctx->graph_tags.end();) it = ends(it->first) ? ctx->graph_tags.erase(it) : std::next(it);
+}
+
 // Runs `body` (a sequence of launches on ctx->stream that touches library-owned buffers only), as a replayed
 // hipGraph when graphs are on: first sighting of `key` runs plainly (allocates workspaces, one-time kernel
 // attribute calls), the second captures on the internal stream and instantiates, later ones replay.
@@ -2066,6 +2081,82 @@ extern "C" int dt_track_recurrent_xproj(dt_ctx *ctx, const float *d_xp, int n_cl
 // ---------------------------------------------------------------------------
 // TinyTracker
 // ---------------------------------------------------------------------------
+// ---- the tiny trackers' stream slots (TinyStreamTable, dt_internal.h): the per-object LSTM's h / c carried across calls ----
+// Every slot fresh again, in stream order (a zero meta row: the slot's rows read as zeros, recurrent.hip).  U: the units of the model the
+// slots are to serve.  A table opened under another U is closed -- a guard for the day the step is compiled for another U: today dt_tiny_load
+// refuses units != 512 before it touches anything, so no caller can get there.  dt_tiny_load calls this after its one synchronisation and
+// BEFORE its first upload: a load that fails half way leaves no warm state over mixed weights.
+static int tiny_streams_fresh(dt_ctx *ctx, int U)
+{
+    TinyStreamTable &S = ctx->tiny_streams;
+    if (!S.n_slots) return DT_OK;
+    if (S.U != U) {      // only a load gets here: it has synchronised the stream
+        graphs_drop(ctx, ":stream");
+        S = TinyStreamTable();
+        return DT_OK;
+    }
+    HIP_TRY(ctx, hipMemsetAsync(S.meta.get(), 0, (size_t)S.n_slots * TSM_META * sizeof(int), ctx->stream));
+    return DT_OK;
+}
+
+// what every tiny stream call checks before it launches anything: an error leaves every slot as it was
+static int tiny_stream_check(dt_ctx *ctx, int n, int T, const int *h_slots)
+{
+    const TinyStreamTable &S = ctx->tiny_streams;
+    if (!ctx->tiny_loaded) return dt_fail(ctx, DT_ERR_STATE, "TinyTracker weights not loaded");
+    if (!S.n_slots) return dt_fail(ctx, DT_ERR_STATE, "dt_tiny_stream_open must be called first");
+    if (n <= 0 || T <= 0) return dt_fail(ctx, DT_ERR_ARG, "n and T must be positive");
+    if (!h_slots || n > S.n_slots) return dt_fail(ctx, DT_ERR_ARG, "a stream call names between 1 and n_slots = %d slots", S.n_slots);
+    std::vector<char> seen((size_t)S.n_slots, 0);
+    for (int i = 0; i < n; ++i) {
+        if (h_slots[i] < 0 || h_slots[i] >= S.n_slots) return dt_fail(ctx, DT_ERR_ARG, "slot %d is outside [0, %d)", h_slots[i], S.n_slots);
+        if (seen[h_slots[i]]) return dt_fail(ctx, DT_ERR_ARG, "slot %d is named twice in one call", h_slots[i]);
+        seen[h_slots[i]] = 1;
+    }
+    return DT_OK;
+}
+
+// the slot list into the table's device list, 64 numbers per launch, outside any graph; reset_meta: the listed rows are zeroed too
+static int tiny_stream_list(dt_ctx *ctx, const int *h_slots, int n, int *reset_meta)
+{
+    TinyStreamTable &S = ctx->tiny_streams;
+    for (int base = 0; base < n; base += 64) {
+        ProfScope ps(ctx, "stream_state", 0.0, 4.0 * std::min(64, n - base), reset_meta ? "tiny_reset" : "tiny_slots");
+        if (launch_stream_slots(ctx->stream, h_slots + base, std::min(64, n - base), S.list.get() + base, reset_meta))
+            return dt_fail(ctx, DT_ERR_DEVICE, "slot list launch failed");
+    }
+    return DT_OK;
+}
+
+extern "C" int dt_tiny_stream_open(dt_ctx *ctx, int n_slots)
+{
+    if (!ctx) return DT_ERR_ARG;
+    if (!ctx->tiny_loaded) return dt_fail(ctx, DT_ERR_STATE, "TinyTracker weights not loaded");
+    if (n_slots <= 0 || n_slots > (1 << 20)) return dt_fail(ctx, DT_ERR_ARG, "n_slots must be in [1, %d]", 1 << 20);
+    const int U = ctx->tiny_U;
+    (void)hipStreamSynchronize(ctx->stream);      // queued steps, and replays of the graphs dropped next, may still use the old table
+    graphs_drop(ctx, ":stream");      // captured steps hold the old table's pointers
+    TinyStreamTable S;
+    HIP_TRY(ctx, S.h.alloc((size_t)2 * n_slots * U));
+    HIP_TRY(ctx, S.c.alloc((size_t)n_slots * U));
+    HIP_TRY(ctx, S.meta.alloc((size_t)n_slots * TSM_META));
+    HIP_TRY(ctx, S.list.alloc((size_t)n_slots));
+    HIP_TRY(ctx, hipMemsetAsync(S.meta.get(), 0, (size_t)n_slots * TSM_META * sizeof(int), ctx->stream));
+    S.n_slots = n_slots; S.U = U;
+    ctx->tiny_streams = std::move(S);
+    return DT_OK;
+}
+
+extern "C" int dt_tiny_stream_reset(dt_ctx *ctx, const int *h_slots, int n)
+{
+    if (!ctx) return DT_ERR_ARG;
+    if (!ctx->tiny_streams.n_slots) return dt_fail(ctx, DT_ERR_STATE, "dt_tiny_stream_open must be called first");
+    if (!h_slots) return tiny_streams_fresh(ctx, ctx->tiny_streams.U);
+    if (n == 0) return DT_OK;
+    const int rc = tiny_stream_check(ctx, n, 1, h_slots);
+    return rc ? rc : tiny_stream_list(ctx, h_slots, n, ctx->tiny_streams.meta.get());
+}
+
 extern "C" int dt_tiny_load(dt_ctx *ctx, int D, int units, int out_dim, const float *h_kernel,
                             const float *h_recurrent, const float *h_bias, const float *h_dense_kernel,
                             const float *h_dense_bias)
@@ -2098,6 +2189,7 @@ extern "C" int dt_tiny_load(dt_ctx *ctx, int D, int units, int out_dim, const fl
     }
     (void)hipStreamSynchronize(ctx->stream);      // queued work may still read the weights these replace
     int rc;
+    if ((rc = tiny_streams_fresh(ctx, U))) return rc;      // state computed under other weights means nothing
     if ((rc = upload(ctx, ctx->tiny_wx, wx))) return rc;
     if ((rc = upload(ctx, ctx->tiny_bx, bx))) return rc;
     if ((rc = upload(ctx, ctx->tiny_ur, ur))) return rc;
@@ -2128,22 +2220,25 @@ extern "C" int dt_tiny_features(dt_ctx *ctx, const float *d_feat, const float *d
     return DT_OK;
 }
 
-extern "C" int dt_tiny_sequence(dt_ctx *ctx, const float *d_x, int n_seq, int T, float *d_out)
+// dt_tiny_sequence, and with a slot list (checked by the caller: tiny_stream_check) dt_tiny_stream_sequence: sequence i starts from the state
+// in slot h_slots[i] of ctx->tiny_streams and leaves its state after frame T - 1 there.  The stream form launches: the slot list (64 numbers per
+// launch), x staging, [the projection, T slot-addressed steps, the slots' bookkeeping] as one graphed sequence, the head.
+static int tiny_sequence_internal(dt_ctx *ctx, const float *d_x, int n_seq, int T, const int *h_slots, float *d_out)
 {
-    if (!ctx || !d_x || !d_out) return dt_fail(ctx, DT_ERR_ARG, "null argument");
-    if (!ctx->tiny_loaded) return dt_fail(ctx, DT_ERR_STATE, "TinyTracker weights not loaded");
-    if (n_seq <= 0 || T <= 0) return dt_fail(ctx, DT_ERR_ARG, "n_seq and T must be positive");
     const int U = ctx->tiny_U, D = ctx->tiny_D, Dp = ctx->tiny_Dpad, N4 = 4 * U;
     const int R = n_seq * T;
     float *x = ws_get_padded(ctx, "tiny_x", (size_t)R * Dp * sizeof(float), Dp, D);
     float *xproj = ws_get(ctx, "tiny_xproj", (size_t)R * N4 * sizeof(float));
     float *hseq = ws_get(ctx, "tiny_h", (size_t)R * U * sizeof(float));
-    float *cst = ws_get(ctx, "tiny_c", (size_t)n_seq * U * sizeof(float));
-    if (!x || !xproj || !hseq || !cst) return DT_ERR_DEVICE;
+    float *cst = h_slots ? nullptr : ws_get(ctx, "tiny_c", (size_t)n_seq * U * sizeof(float));
+    if (!x || !xproj || !hseq || (!h_slots && !cst)) return DT_ERR_DEVICE;
+    TinyStreamTable &S = ctx->tiny_streams;
+    // the slot list reaches the steps through the library-owned device list: filled here, in stream order and outside the graph
+    if (h_slots) { const int rc = tiny_stream_list(ctx, h_slots, n_seq, nullptr); if (rc) return rc; }
     if (launch_copy_cols(ctx->stream, d_x, D, x, Dp, R, D))   // K padded to a multiple of 32 (pad columns stay 0)
         return dt_fail(ctx, DT_ERR_DEVICE, "x staging launch failed");
     // staged x, xproj, h and c are library-owned: the projection and the T launch-bound steps replay as a graph
-    int grc = graphed(ctx, "lstm:" + std::to_string(n_seq) + "x" + std::to_string(T), [&]() -> int {
+    int grc = graphed(ctx, "lstm:" + std::to_string(n_seq) + "x" + std::to_string(T) + (h_slots ? ":stream" : ""), [&]() -> int {
     {   // x.W + b for every (sequence, t) at once on the matrix cores
         ConvArgs a;
         memset(&a, 0, sizeof(a));
@@ -2161,12 +2256,20 @@ extern "C" int dt_tiny_sequence(dt_ctx *ctx, const float *d_x, int n_seq, int T,
     for (int t = 0; t < T; ++t) {
         ProfScope ps(ctx, "lstm_step", 2.0 * n_seq * (double)U * N4, 4.0 * ((double)U * N4 + n_seq * (6.0 * U + N4)));
         int rc;
-        if (t == 0)
+        if (h_slots)      // every step in the slot-addressed form: c is the slots' rows, h enters from and leaves to the table
+            rc = launch_lstm_step_stream(ctx->stream, xproj + (long long)t * N4, xp_bs, t ? hseq + (long long)(t - 1) * U : nullptr, h_bs,
+                                         ctx->tiny_ur.get(), hseq + (long long)t * U, h_bs, n_seq, U,
+                                         LstmSlots{S.list.get(), S.meta.get(), S.h.get(), S.c.get(), (long long)S.n_slots * U, t == 0, t == T - 1});
+        else if (t == 0)
             rc = launch_lstm_step0(ctx->stream, xproj, xp_bs, cst, hseq, h_bs, n_seq, U);
         else
             rc = launch_lstm_step(ctx->stream, xproj + (long long)t * N4, xp_bs, hseq + (long long)(t - 1) * U, h_bs,
                                   cst, ctx->tiny_ur.get(), hseq + (long long)t * U, h_bs, n_seq, U);
         if (rc) return dt_fail(ctx, DT_ERR_DEVICE, "LSTM step launch failed");
+    }
+    if (h_slots) {      // the copy the last step wrote becomes current, the frame counters advance (T is part of the graph's key)
+        ProfScope ps(ctx, "stream_state", 0.0, 24.0 * n_seq, "tiny_advance");
+        if (launch_lstm_stream_advance(ctx->stream, S.list.get(), S.meta.get(), n_seq, T)) return dt_fail(ctx, DT_ERR_DEVICE, "stream bookkeeping launch failed");
     }
     return DT_OK;
     });
@@ -2189,6 +2292,33 @@ extern "C" int dt_tiny_sequence(dt_ctx *ctx, const float *d_x, int n_seq, int T,
             return dt_fail(ctx, DT_ERR_DEVICE, "Dense head launch failed");
     }
     return DT_OK;
+}
+
+extern "C" int dt_tiny_sequence(dt_ctx *ctx, const float *d_x, int n_seq, int T, float *d_out)
+{
+    if (!ctx || !d_x || !d_out) return dt_fail(ctx, DT_ERR_ARG, "null argument");
+    if (!ctx->tiny_loaded) return dt_fail(ctx, DT_ERR_STATE, "TinyTracker weights not loaded");
+    if (n_seq <= 0 || T <= 0) return dt_fail(ctx, DT_ERR_ARG, "n_seq and T must be positive");
+    return tiny_sequence_internal(ctx, d_x, n_seq, T, nullptr, d_out);
+}
+
+extern "C" int dt_tiny_stream_sequence(dt_ctx *ctx, const float *d_x, int n, int T, const int *h_slots, float *d_out)
+{
+    if (!ctx || !d_x || !d_out) return dt_fail(ctx, DT_ERR_ARG, "null argument");
+    const int rc = tiny_stream_check(ctx, n, T, h_slots);
+    return rc ? rc : tiny_sequence_internal(ctx, d_x, n, T, h_slots, d_out);
+}
+
+extern "C" int dt_tiny_stream_forward(dt_ctx *ctx, const float *d_feat, const float *d_det, int n, int T, int fh, int fw, int fc, int pool,
+                                      const int *h_slots, float *d_out)
+{
+    if (!ctx || !d_feat || !d_det || !d_out) return dt_fail(ctx, DT_ERR_ARG, "null argument");
+    int rc = tiny_stream_check(ctx, n, T, h_slots);      // before the features: an error launches nothing
+    if (rc) return rc;
+    float *rows = ws_get(ctx, "tiny_rows", (size_t)n * T * ctx->tiny_D * sizeof(float));
+    if (!rows) return DT_ERR_DEVICE;
+    rc = dt_tiny_features(ctx, d_feat, d_det, n * T, fh, fw, fc, pool, rows);
+    return rc ? rc : tiny_sequence_internal(ctx, rows, n, T, h_slots, d_out);
 }
 
 extern "C" int dt_tiny_forward(dt_ctx *ctx, const float *d_feat, const float *d_det, int n_seq, int T, int fh, int fw,

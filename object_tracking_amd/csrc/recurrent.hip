@@ -164,9 +164,19 @@ __device__ __forceinline__ float wave_sum(float v)
     return v;
 }
 
-__global__ __launch_bounds__(128) void lstm_step_kernel(const float *xproj, long long xp_bs, const float *h_prev,
-                                                        long long h_bs, float *cstate, const float *ur, float *h_out,
-                                                        long long ho_bs, int B, int U)
+// The step in its two forms (the kernel is the template, so that the stateless instance compiles to what it was before the stream form
+// existed).  STREAM = false, SL = NoSlots: the stateless step (dt_tiny_sequence) -- h_prev and cstate are the call's own
+// rows, track b at b * h_bs / b * U.  STREAM = true, SL = LstmSlots (cstate unused): the streams' step (dt_tiny_stream_sequence) -- track b of the call lives in slot
+// s.list[b] of the context's table (LstmSlots, dt_internal.h): c is the slot's row c[slot], updated in place at every step; on the FIRST
+// step of a call h_prev is the slot's current copy h[cur][slot] (zeros, and c = 0, when the slot is fresh: selected, never multiplied --
+// the rows of a fresh slot may hold anything); on the LAST step h_t goes to the OTHER copy h[cur ^ 1][slot] as well as to h_out, so that
+// no workgroup of the launch writes a word another one still reads as h_prev (T = 1: one launch is both).  `cur` and the frame counter
+// are not written here (lstm_stream_advance_kernel, after the last step).  The arithmetic is the same statement for statement: a stream
+// fed in chunks equals the stateless call on the concatenation bit for bit.
+struct NoSlots {};
+template <bool STREAM, class SL>
+__global__ __launch_bounds__(128) void lstm_step_kernel(const float *xproj, long long xp_bs, const float *h_prev, long long h_bs,
+                                                          float *cstate, const float *ur, float *h_out, long long ho_bs, int B, int U, SL s)
 {
     const int lane = threadIdx.x & 63;
     const int j = blockIdx.x * 2 + (threadIdx.x >> 6);
@@ -186,6 +196,14 @@ __global__ __launch_bounds__(128) void lstm_step_kernel(const float *xproj, long
     for (int b0 = 0; b0 < B; b0 += 64) {
         float keep[4] = {0.f, 0.f, 0.f, 0.f};
         const int bn = min(64, B - b0);
+        // STREAM: lane l reads the slot of track b0 + l and its meta row ONCE per block of 64 tracks (bit 0: the current h copy, bit 1: fresh); the
+        // groups below take a track's words from its lane, so the h rows of a group are one round trip as in the stateless form
+        [[maybe_unused]] int my_slot = 0, my_fl = 0;
+        if constexpr (STREAM) {
+            my_slot = s.list[b0 + min(lane, bn - 1)];      // (clamped: every lane holds a slot of the call)
+            const int4 m = *reinterpret_cast<const int4 *>(s.meta + my_slot * TSM_META);
+            my_fl = (m.y & 1) | (m.x == 0 ? 2 : 0);
+        }
         // tracks in groups of 8: the sixteen 16-byte loads of a group are issued back to back
         // (one L2 round trip per group instead of one per track), then reduced
         for (int g0 = 0; g0 < bn; g0 += 8) {
@@ -193,6 +211,18 @@ __global__ __launch_bounds__(128) void lstm_step_kernel(const float *xproj, long
 #pragma unroll
             for (int u = 0; u < 8; ++u) {
                 const int bb = min(g0 + u, bn - 1);     // clamp: tail slots re-read the last row
+                if constexpr (STREAM) {
+                    if (s.first) {                      // (the clamp keeps bb a track of the call, so the slot is one of its slots)
+                        const int slot = __shfl(my_slot, bb), fl = __shfl(my_fl, bb);
+                        const float *hp = s.h + (fl & 1) * s.copy + (long long)slot * U + lane * 8;
+                        const f32x4 a0 = *reinterpret_cast<const f32x4 *>(hp);
+                        const f32x4 a1 = *reinterpret_cast<const f32x4 *>(hp + 4);
+                        const f32x4 z = {0.0f, 0.0f, 0.0f, 0.0f};
+                        x0[u] = (fl & 2) ? z : a0;
+                        x1[u] = (fl & 2) ? z : a1;
+                        continue;
+                    }
+                }
                 const float *hp = h_prev + (long long)(b0 + bb) * h_bs + lane * 8;
                 x0[u] = *reinterpret_cast<const f32x4 *>(hp);
                 x1[u] = *reinterpret_cast<const f32x4 *>(hp + 4);
@@ -252,10 +282,20 @@ __global__ __launch_bounds__(128) void lstm_step_kernel(const float *xproj, long
             const float zf = keep[1] + xp[U + j];
             const float zc = keep[2] + xp[2 * U + j];
             const float zo = keep[3] + xp[3 * U + j];
-            float *cp = cstate + (long long)b * U + j;
-            const float cn = hard_sigmoid_r(zf) * (*cp) + hard_sigmoid_r(zi) * tanhf(zc);
-            *cp = cn;
-            h_out[(long long)b * ho_bs + j] = hard_sigmoid_r(zo) * tanhf(cn);
+            if constexpr (STREAM) {
+                float *cp = s.c + (long long)my_slot * U + j;
+                const float cold = (s.first && (my_fl & 2)) ? 0.0f : *cp;
+                const float cn = hard_sigmoid_r(zf) * cold + hard_sigmoid_r(zi) * tanhf(zc);
+                *cp = cn;
+                const float hn = hard_sigmoid_r(zo) * tanhf(cn);
+                h_out[(long long)b * ho_bs + j] = hn;
+                if (s.last) s.h[((my_fl & 1) ^ 1) * s.copy + (long long)my_slot * U + j] = hn;
+            } else {
+                float *cp = cstate + (long long)b * U + j;
+                const float cn = hard_sigmoid_r(zf) * (*cp) + hard_sigmoid_r(zi) * tanhf(zc);
+                *cp = cn;
+                h_out[(long long)b * ho_bs + j] = hard_sigmoid_r(zo) * tanhf(cn);
+            }
         }
     }
 }
@@ -265,8 +305,39 @@ int launch_lstm_step(hipStream_t st, const float *xproj, long long xp_bs, const 
 {
     if (U != 512) return 2;   // lane k-slice of 8 is compiled in (LSTM_UNITS = 512, config.json:19)
     if (B <= 0) return 0;
-    hipLaunchKernelGGL(lstm_step_kernel, dim3((unsigned)((U + 1) / 2)), dim3(128), 0, st, xproj, xp_bs, h_prev, h_bs,
-                       cstate, Ur_packed, h_out, ho_bs, B, U);
+    hipLaunchKernelGGL((lstm_step_kernel<false, NoSlots>), dim3((unsigned)((U + 1) / 2)), dim3(128), 0, st, xproj, xp_bs, h_prev, h_bs,
+                       cstate, Ur_packed, h_out, ho_bs, B, U, NoSlots{});
+    return hipGetLastError() == hipSuccess ? 0 : 1;
+}
+
+int launch_lstm_step_stream(hipStream_t st, const float *xproj, long long xp_bs, const float *h_prev, long long h_bs,
+                            const float *Ur_packed, float *h_out, long long ho_bs, int B, int U, const LstmSlots &s)
+{
+    if (U != 512) return 2;
+    if (B <= 0) return 0;
+    if (!s.list || !s.meta || !s.h || !s.c || s.copy <= 0 || (!s.first && !h_prev)) return 2;
+    hipLaunchKernelGGL((lstm_step_kernel<true, LstmSlots>), dim3((unsigned)((U + 1) / 2)), dim3(128), 0, st, xproj, xp_bs, h_prev, h_bs, (float *)nullptr,
+                       Ur_packed, h_out, ho_bs, B, U, s);
+    return hipGetLastError() == hipSuccess ? 0 : 1;
+}
+
+// After the last step of a stream call: the copy the step wrote becomes the slots' current one and their frame counters advance by T.
+// A launch of its own, stream-ordered behind the steps: every workgroup of a step reads `cur` and the counter, so no step may write them.
+__global__ __launch_bounds__(256) void lstm_stream_advance_kernel(const int *list, int *meta, int B, int T)
+{
+    const int b = blockIdx.x * 256 + threadIdx.x;
+    if (b >= B) return;
+    int *m = meta + list[b] * TSM_META;      // the slots of a call are distinct: one thread per row
+    const int f = m[TSM_FRAMES];
+    m[TSM_FRAMES] = f > (1 << 30) ? f : f + T;      // saturates: only "zero or not" is ever read
+    m[TSM_CUR] ^= 1;
+}
+
+int launch_lstm_stream_advance(hipStream_t st, const int *list, int *meta, int B, int T)
+{
+    if (B <= 0) return 0;
+    if (T <= 0 || T > (1 << 30)) return 2;
+    hipLaunchKernelGGL(lstm_stream_advance_kernel, dim3((unsigned)((B + 255) / 256)), dim3(256), 0, st, list, meta, B, T);
     return hipGetLastError() == hipSuccess ? 0 : 1;
 }
 

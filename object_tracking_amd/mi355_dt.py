@@ -32,6 +32,7 @@ SYMBOLS = [
     "dt_gemm_split_bf16", "dt_gemm_split", "dt_policy_set", "dt_amax_read",
     "dt_stream_open", "dt_stream_reset", "dt_track_stream_forward", "dt_associate_stream",
     "dt_associate_mem", "dt_stream_open_tracks", "dt_associate_stream_mem",
+    "dt_tiny_stream_open", "dt_tiny_stream_reset", "dt_tiny_stream_sequence", "dt_tiny_stream_forward",
 ]
 
 _lib = None
@@ -95,6 +96,10 @@ def load_library():
     L.dt_tiny_forward.argtypes = [vp, vp, vp, ci, ci, ci, ci, ci, ci, vp]
     L.dt_tiny_features.argtypes = [vp, vp, vp, ci, ci, ci, ci, ci, vp]
     L.dt_tiny_sequence.argtypes = [vp, vp, ci, ci, vp]
+    L.dt_tiny_stream_open.argtypes = [vp, ci]
+    L.dt_tiny_stream_reset.argtypes = [vp, ctypes.POINTER(ci), ci]
+    L.dt_tiny_stream_sequence.argtypes = [vp, vp, ci, ci, ctypes.POINTER(ci), vp]
+    L.dt_tiny_stream_forward.argtypes = [vp, vp, vp, ci, ci, ci, ci, ci, ci, ctypes.POINTER(ci), vp]
     L.dt_top_box.argtypes = [vp, vp, vp, ci, ci, vp]
     L.dt_conv2d.argtypes = [vp, vp, ci, ci, ci, ci, vp, ci, ci, vp, cf, ci, vp, vp]
     L.dt_convlstm_step.argtypes = [vp, vp, ci, ci, ci, ci, vp, vp, ci, vp, vp, vp, vp, vp]
@@ -563,6 +568,48 @@ class Context(object):
         out = self._f32(n_seq, T, self.tiny_out)
         self._sync_stream()
         self._check(self.lib.dt_tiny_sequence(self.h, _dptr(x), n_seq, T, _dptr(out)), "dt_tiny_sequence")
+        return out
+
+    # ---- tiny tracker streams: the LSTM state carried across calls -------
+    def tiny_stream_open(self, n_slots):
+        """(re)allocate the tiny trackers' stream slots (h, c [units] per slot), every one fresh; apart from stream_open's table"""
+        self._sync_stream()
+        self._check(self.lib.dt_tiny_stream_open(self.h, int(n_slots)), "dt_tiny_stream_open")
+
+    def tiny_stream_reset(self, slots=None):
+        """the listed slots (None: all) fresh again: the next call on them starts from h = c = 0"""
+        self._sync_stream()
+        if slots is None:
+            self._check(self.lib.dt_tiny_stream_reset(self.h, None, 0), "dt_tiny_stream_reset")
+        else:
+            n, arr = self._slot_array(slots)
+            self._check(self.lib.dt_tiny_stream_reset(self.h, arr, n), "dt_tiny_stream_reset")
+
+    def tiny_stream_sequence(self, x, slots):
+        """tiny_sequence on x [n,T,D] whose sequence i continues from -- and leaves its LSTM state in -- slot slots[i]."""
+        assert x.is_cuda and x.is_contiguous()
+        n, T, _ = x.shape
+        ns, arr = self._slot_array(slots)
+        if ns != n:
+            raise NativeError("dt_tiny_stream_sequence failed (1): %d slots for %d streams" % (ns, n))
+        out = self._f32(n, T, self.tiny_out)
+        self._sync_stream()
+        self._check(self.lib.dt_tiny_stream_sequence(self.h, _dptr(x), n, T, arr, _dptr(out)), "dt_tiny_stream_sequence")
+        return out
+
+    def tiny_stream_forward(self, feat, det, slots, pool="Global"):
+        """tiny_forward on feat [n,T,fh,fw,fc], det [n,T,4 or hs*hs] whose sequence i continues in slot slots[i]."""
+        t = self.torch
+        assert feat.is_cuda and feat.is_contiguous() and feat.dtype == t.float32
+        assert det.is_cuda and det.is_contiguous() and det.dtype == t.float32
+        n, T, fh, fw, fc = feat.shape
+        ns, arr = self._slot_array(slots)
+        if ns != n:
+            raise NativeError("dt_tiny_stream_forward failed (1): %d slots for %d streams" % (ns, n))
+        out = self._f32(n, T, self.tiny_out)
+        self._sync_stream()
+        self._check(self.lib.dt_tiny_stream_forward(self.h, _dptr(feat), _dptr(det), n, T, fh, fw, fc,
+                                                    0 if pool == "Global" else 1, arr, _dptr(out)), "dt_tiny_stream_forward")
         return out
 
     def top_box(self, boxes, counts):

@@ -61,3 +61,14 @@ class TinyHeatmapTracker(TinyTracker):
         heat = ctx.tiny_sequence(rows.reshape(n_seq, T, -1).contiguous())
         rects = ctx.rect_from_heatmap(heat.reshape(n_seq * T, -1), self.HEATMAP_SIZE, thresh)
         return heat, rects.reshape(n_seq, T, 4)
+
+    def track_stream(self, frames, slots, detector, thresh=0.75):
+        """frames [n,T,H,W,3], stream i continuing in slot slots[i] -> (heatmaps, rects) as track_sequences gives them on the
+        concatenation of everything the streams were fed since their reset."""
+        n, T = frames.shape[:2]
+        flat = frames.reshape((n * T,) + tuple(frames.shape[2:]))
+        rows, _ = self.frame_rows(flat, detector)
+        ctx = self.model_tracker.ctx
+        heat = ctx.tiny_stream_sequence(rows.reshape(n, T, -1).contiguous(), slots)
+        rects = ctx.rect_from_heatmap(heat.reshape(n * T, -1), self.HEATMAP_SIZE, thresh)
+        return heat, rects.reshape(n, T, 4)

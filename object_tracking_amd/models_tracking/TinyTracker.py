@@ -102,3 +102,24 @@ class TinyTracker(BaseTracker):
         flat = frames.reshape((n_seq * T,) + tuple(frames.shape[2:]))
         rows, _ = self.frame_rows(flat, detector)
         return self.model_tracker.ctx.tiny_sequence(rows.reshape(n_seq, T, -1).contiguous())
+
+    # ------------------------------------------------------------------
+    # Streaming (addition): the LSTM state h, c of every tracked object lives in a slot of the context's tiny stream table
+    # (mi355_dt.Context.tiny_stream_open) and is carried from one call to the next.  A stream fed in chunks of any sizes gives what
+    # track_sequences gives on the concatenation of the chunks; models_tracking.streams.StreamTable maps stream keys to slots.
+    def open_streams(self, n_slots, cap=None):
+        """(Re)allocate n_slots stream slots, every one fresh.  `cap` is accepted and ignored: StreamTable passes it, and a
+        single-object tracker keeps no box table."""
+        self.model_tracker.ctx.tiny_stream_open(int(n_slots))
+
+    def reset_streams(self, slots=None):
+        """The listed slots (None: all) fresh again: their next frame starts from h = c = 0."""
+        self.model_tracker.ctx.tiny_stream_reset(slots)
+
+    def track_stream(self, frames, slots, detector):
+        """frames [n,T,H,W,3], stream i continuing in slot slots[i] -> boxes [n,T,4] (device tensor): what track_sequences
+        gives for these frames on the concatenation of everything the streams were fed since their reset."""
+        n, T = frames.shape[:2]
+        flat = frames.reshape((n * T,) + tuple(frames.shape[2:]))
+        rows, _ = self.frame_rows(flat, detector)
+        return self.model_tracker.ctx.tiny_stream_sequence(rows.reshape(n, T, -1).contiguous(), slots)

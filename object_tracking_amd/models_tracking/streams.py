@@ -11,7 +11,9 @@ to the next key that opens).
     table.release("gate-3")
 
 `tracker` is anything with open_streams(n_slots, cap) and reset_streams(slots)
--- a MultiObjDetTracker -- or None for bookkeeping alone.
+-- a MultiObjDetTracker, a TinyTracker or a TinyHeatmapTracker (their slots hold
+the per-object LSTM state; `cap` means nothing to them and is ignored) -- or
+None for bookkeeping alone.
 """
 
 
