@@ -89,7 +89,9 @@ DT_API int dt_detector_tap(dt_ctx *ctx, const char *name, int batch, float *d_ou
  * (BatchNormalization output), leaky_re_lu_1..21 (alias act_N) and conv_feat (after LeakyReLU),
  * max_pooling2d_1..5, lambda_1 (space_to_depth), concatenate_1, reshape_1 / lambda_2 (= conv_23 values).
  * The fused production path never materialises most of these: the call re-runs the graph up to the layer and
- * executes that layer un-fused (a one-image debugging call, not a hot path).
+ * executes that layer un-fused (a one-image debugging call, not a hot path).  The layers before it run in the
+ * kernel forms dt_detect_forward takes at this batch; leaky_re_lu_4 is written by the fused conv_3 + conv_4
+ * launch itself wherever the forward takes that launch.
  *   shape4 [4] receives (batch, h, w, channels) of the layer (may be NULL); with d_out == NULL only the shape
  *   is returned; d_out holds out_floats floats and receives the dense NHWC tensor. */
 DT_API int dt_detector_extract(dt_ctx *ctx, const void *d_frames, int frames_dtype, int batch,

@@ -1363,13 +1363,19 @@ static int run_trunk(dt_ctx *ctx, int B, float *bufA, float *bufB, float *skip, 
         const int idx = TRUNK[li][0], pool = TRUNK[li][4];
         const ConvLayer &L = ctx->layers[idx];
         if (ex && ex->idx == idx && ex->kind <= EX_ACT) return extract_layer(ctx, L, cur, L.cin, B, h, w, *ex);
-        if (idx == 3 && !ex && TRUNK[li + 1][0] == 4 && conv34_fusable(ctx, L, ctx->layers[4], cur, L.cin, B, h, w, nxt)) {
-            // conv_3 + conv_4 in one launch: conv_4's output goes to `nxt`, one swap, conv_4's turn of the walk is skipped
-            rc = run_conv34_fused(ctx, L, ctx->layers[4], cur, L.cin, B, h, w, nxt, ctx->layers[4].cout, LEAKY);
-            if (rc) return rc;
-            float *t = cur; cur = nxt; nxt = t;
-            ++li;                      // conv_4 is done
-            continue;
+        if (idx == 3 && TRUNK[li + 1][0] == 4) {
+            // conv_3 + conv_4 in one launch.  An extraction of conv_4 / norm_4 asks for conv_4 before its LeakyReLU, which the fused launch never forms: two
+            // launches (conv_3's own forms returned above); leaky_re_lu_4 is the launch's output, written straight into the caller's tensor (dense, ld 64)
+            const bool ex4 = ex && ex->idx == 4;
+            float *out34 = ex4 ? ex->out : nxt;
+            if (!(ex4 && ex->kind < EX_ACT) && conv34_fusable(ctx, L, ctx->layers[4], cur, L.cin, B, h, w, out34)) {
+                rc = run_conv34_fused(ctx, L, ctx->layers[4], cur, L.cin, B, h, w, out34, ctx->layers[4].cout, LEAKY);
+                if (ex4) { ex->done = rc == DT_OK; return rc; }
+                if (rc) return rc;
+                float *t = cur; cur = nxt; nxt = t;      // conv_4's output is in `nxt`: one swap, conv_4's turn of the walk is skipped
+                ++li;
+                continue;
+            }
         }
         if (idx == 13) {   // skip tapped before the pool (KerasYOLO.py:347)
             rc = run_conv(ctx, L, cur, L.cin, B, h, w, skip, 512, ORD_QUAD, EPI_POOL_BOTH, LEAKY, nxt, 512);

@@ -1216,9 +1216,10 @@ def test_policy_set_pin_holds_in_conv2d(ctx):
     assert f.get("s3_form:f16x2", 0) > 0, f      # (the same call un-pinned takes the fp16 form: the witness can fire)
 
 
-def test_extract_selects_kernels_as_detect_forward(ctx):
+def test_extract_selects_kernels_as_detect_forward(ctx, monkeypatch):
     """dt_detector_extract picks kernel forms by its batch exactly as dt_detect_forward does: at 8 frames (below DT_H2_MINFRAMES) neither
-    runs the fp16 form, so the per-layer taps see the kernels of the forward."""
+    runs the fp16 form, so the per-layer taps see the kernels of the forward.  Where the forward runs conv_3 + conv_4 as one launch
+    (16 frames of 64x96 with the direct kernel forced), so does the extraction of a later layer -- and with DT_C3FUSE=0 neither does."""
     det, _, _ = _detector(ctx, 416, 416, 12)
     c = det.model.ctx
     d = dev(np.concatenate([synth.synth_clip(4, 416, 416, 2, seed=s) for s in (25, 26)]), c)
@@ -1227,6 +1228,21 @@ def test_extract_selects_kernels_as_detect_forward(ctx):
     assert set(ext) == set(fwd) and "s3_form:f16x2" not in ext and "conv_direct_h2" not in ext, (fwd, ext)
     d16 = torch.cat([d, d])
     assert "s3_form:f16x2" in _forms(c, lambda: c.detector_extract(d16, "leaky_re_lu_20"))      # 16 frames: the fp16 form
+    # a batch and policy at which the forward fuses conv_4 into conv_3's launch
+    monkeypatch.setenv("DT_C3H2", "2")
+    det, _, _ = _detector(ctx, 64, 96, 12)
+    c = det.model.ctx
+    d = dev(synth.synth_clip(16, 64, 96, 2, seed=27), c)
+    fwd = _forms(c, lambda: c.detect_forward(d))
+    assert fwd.get("conv_direct_h2:fused_1x1") == 1 and fwd.get("conv_direct_h2") == 3, fwd      # conv_2, conv_3 (+ conv_4), conv_5
+    ext = _forms(c, lambda: c.detector_extract(d, "leaky_re_lu_20"))
+    assert set(ext) == set(fwd) and ext["conv_direct_h2:fused_1x1"] == 1 and ext["conv_direct_h2"] == 3, (fwd, ext)
+    assert not [n for n in c.profile_names() if n.endswith(":conv_4")]
+    monkeypatch.setenv("DT_C3FUSE", "0")
+    c.reload_policy()
+    fwd0 = _forms(c, lambda: c.detect_forward(d))
+    ext0 = _forms(c, lambda: c.detector_extract(d, "leaky_re_lu_20"))
+    assert set(ext0) == set(fwd0) and "conv_direct_h2:fused_1x1" not in ext0 and ext0["conv_direct_h2"] == 3, (fwd0, ext0)
 
 
 # ---- hipGraph replay of the launch-bound inner sequences (dt_graph_enable) ------------------
@@ -1427,7 +1443,8 @@ def test_conv_fused_f4x4_vs_oracle(ctx, monkeypatch, B, H, W, Cin, Cout, pool, f
     (1, 26, 22, 32, 64, 0),
     (2, 24, 40, 64, 64, 1),       # 64 -> 64: two chunks on the 16x16-tile instance
     (2, 16, 32, 32, 128, 0),      # 32 -> 128: one chunk on the 8x16-tile instance
-    (70, 13, 13, 64, 128, 0),     # frames smaller than a tile, more items than workgroups (the persistent loop turns over)
+    (70, 13, 13, 64, 128, 0),     # frames smaller than a tile (70 x 2 tile rows = 140 items: fewer than the launch's workgroups, the
+                                  # persistent loop does NOT turn over here -- tests/test_gpu_conv3_h2_layer.py turns it over)
 ])
 def test_conv3_direct_h2_vs_oracle(ctx, monkeypatch, B, H, W, Cin, Cout, pool):
     monkeypatch.setenv("DT_C3H2", "2")
