@@ -51,6 +51,7 @@ DT_API int dt_set_stream(dt_ctx *ctx, void *hip_stream);
 /* ABI version of this header: major*100+minor (1.08: 1.07 + dt_amax_read, and later the four stream entries dt_stream_open, dt_stream_reset,
  * dt_track_stream_forward, dt_associate_stream, and the three track-memory entries dt_associate_mem, dt_stream_open_tracks, dt_associate_stream_mem
  * and the four tiny-tracker stream entries dt_tiny_stream_open, dt_tiny_stream_reset, dt_tiny_stream_sequence, dt_tiny_stream_forward
+ * and the two track-motion entries dt_associate_motion, dt_associate_stream_motion
  * -- additions only, the number stayed; 1.07: 1.06 + dt_gemm_split, dt_policy_set) */
 DT_API int dt_abi_version(void);
 
@@ -187,6 +188,19 @@ DT_API int dt_associate(dt_ctx *ctx, const float *d_boxes, const int *d_counts,
 DT_API int dt_associate_mem(dt_ctx *ctx, const float *d_boxes, const int *d_counts,
                  int n_clips, int T, int cap, float assoc_threshold, int max_age, int tcap,
                  int *d_ids, int *d_nids, int *d_gaps);
+/* Track motion (BUILD-DEFINED, DESIGN.md "Track identity"): dt_associate_mem with every table entry matched where a constant velocity
+ * predicts it.  An entry carries a velocity (vx, vy) of its box's x, y per frame.  With k = (float)(age + 1) its predicted box is
+ * (x + k*vx, y + k*vy, w, h) and the IoU of the match is taken against that box; everything else of the match is dt_associate_mem's.
+ * When a box claims an entry: o = (x_box - x_entry) / k on the entry's STORED x (y likewise), v_box = v + gain * (o - v); a box that
+ * opens a new id starts at rest.  Survivors keep box and velocity.  All float32, every operation rounded on its own, no FMA.
+ * gain in [0, 1]; gain = 0 is dt_associate_mem bit for bit.  max_age = 0 still uses the velocity: an age-0 entry is matched one step
+ * ahead, and in dense scenes that can open a few more ids than dt_associate does.  w / h are not predicted; boxes must be finite.
+ * No Kalman filter, no cross-label match, no optimal assignment, no minimum hit count, no read-out of predicted boxes.
+ * DT_ERR_ARG: as dt_associate_mem (the LDS tables hold 9 words per entry here, so the largest tcap is smaller), and gain outside
+ * [0, 1] or NaN. */
+DT_API int dt_associate_motion(dt_ctx *ctx, const float *d_boxes, const int *d_counts,
+                 int n_clips, int T, int cap, float assoc_threshold, int max_age, int tcap, float gain,
+                 int *d_ids, int *d_nids, int *d_gaps);
 
 /* ---- streaming: ConvLSTM state and track ids carried across calls (addition; the reference's predict() sees one window) ---- *
  * A live stream delivers a frame, or a few, at a time.  The context holds a table of STREAM SLOTS in device memory; per slot the ConvLSTM
@@ -221,6 +235,15 @@ DT_API int dt_associate_stream(dt_ctx *ctx, const float *d_boxes, const int *d_c
  * DT_ERR_ARG for max_age < 0; an error leaves the slots as they were. */
 DT_API int dt_associate_stream_mem(dt_ctx *ctx, const float *d_boxes, const int *d_counts, int n, int T, int cap,
                         float thr, int max_age, const int *h_slots, int *d_ids, int *d_nids, int *d_gaps);
+/* dt_associate_motion for streams: the slot's track table, with a velocity per entry (a further [tcap][2] floats per slot), is the table
+ * frame 0 is matched against, and table and velocities after frame T-1 go back to the slot.  Chunks of any sizes with one max_age and
+ * one gain give what dt_associate_motion gives on the concatenation with tcap = the table's, bit for bit.  The three stream association
+ * entries may be mixed on one slot: a call of dt_associate_stream or dt_associate_stream_mem makes the slot's tracks forget their
+ * velocities (the next motion call finds every track at rest); ids, boxes and ages carry over as between those two.  A fresh or reset
+ * slot has an empty table.  Errors as dt_associate_stream_mem, and DT_ERR_ARG for gain outside [0, 1] or NaN or a table whose 9-word
+ * entries do not fit the LDS; an error leaves the slots as they were. */
+DT_API int dt_associate_stream_motion(dt_ctx *ctx, const float *d_boxes, const int *d_counts, int n, int T, int cap,
+                        float thr, int max_age, float gain, const int *h_slots, int *d_ids, int *d_nids, int *d_gaps);
 
 /* ---- cross-stream detection exchange (multi-GPU; the reference has no counterpart) ---- *
  * north_star: "RCCL all-gather of detections over xGMI only for cross-stream association".  Each rank packs its

@@ -1115,6 +1115,313 @@ int launch_associate_mem(hipStream_t st, const float *boxes, const int *counts, 
 }
 
 // ---------------------------------------------------------------------------
+// Track identity with TRACK MOTION (DESIGN.md "Track identity", motion gain): the track-memory rule above with every table
+// entry matched where a constant velocity predicts it.  An entry carries, beside box, label, id and age, the velocity
+// (vx, vy) of its box's x, y per frame.  With k = float(age + 1) the entry's PREDICTED box is (x + k*vx, y + k*vy, w, h)
+// (one multiply, one add, each rounded: this file forms no FMA), and the match is associate_mem_kernel's with the IoU taken
+// against the predicted box.  When box i claims entry j: o = (x_i - x_j) / k on the STORED x_j (the correctly rounded
+// quotient), v_i = v_j + gain * (o - v_j); a box that opens a new id starts at rest.  The rebuild carries the velocities
+// along.  gain = 0 leaves every velocity 0 and is associate_mem_kernel bit for bit.
+// A sibling of associate_mem_kernel, same two forms, chosen by the launcher from tcap and T alone.
+// STREAM: the slot's velocities live in carry.vel and are the table's only while carry.vstamp[slot] equals the slot's
+// association frame counter, which every association entry advances and this kernel alone copies into the stamp -- so a
+// table that dt_associate_stream / dt_associate_stream_mem has touched since reads as at rest.
+// ---------------------------------------------------------------------------
+template <bool STREAM>
+__global__ __launch_bounds__(64) void associate_motion_kernel(const float *boxes, const int *counts, int T, int cap, float thr,
+                                                              int max_age, int tcap, float gain, int *ids, int *nids, int *gaps,
+                                                              AssocCarry carry)
+{
+    extern __shared__ __attribute__((aligned(16))) float smem[];
+    const int clip = blockIdx.x, lane = threadIdx.x;
+    const float *bx = boxes + (long long)clip * T * cap * DT_BOX_FLOATS;
+    const int *cnt = counts + (long long)clip * T;
+    int *id = ids + (long long)clip * T * cap;
+    int *gp = gaps ? gaps + (long long)clip * T * cap : nullptr;
+    int next_id = 0;
+    int nt = 0, n0 = 0;       // entries in the table; of them, leading entries of age 0 (the last frame's boxes)
+    float *sb = nullptr, *sv = nullptr;
+    int *si = nullptr, *sa = nullptr, *sm = nullptr, *ss = nullptr;
+    bool vvalid = false;      // the slot's stored velocities belong to the table it holds
+    if constexpr (STREAM) {
+        const int slot = carry.slots[clip];
+        sb = carry.boxes + (long long)slot * tcap * DT_BOX_FLOATS;
+        si = carry.ids + (long long)slot * tcap;
+        sa = carry.ages + (long long)slot * tcap;
+        sv = carry.vel + (long long)slot * tcap * 2;
+        sm = carry.meta + slot * STREAM_META;
+        ss = carry.vstamp + slot;
+        const int w = sm[SM_COUNT];
+        n0 = min(w & SM_COUNT_MASK, cap);
+        nt = min(n0 + (int)((unsigned)w >> SM_AGED_SHIFT), tcap);
+        next_id = sm[SM_NEXT_ID];
+        const int f = sm[SM_ASSOC_FRAMES];
+        vvalid = f > 0 && f <= (1 << 30) && *ss == f;
+    }
+    auto store_meta = [&]() {
+        if (lane == 0) {
+            sm[SM_COUNT] = n0 | ((nt - n0) << SM_AGED_SHIFT);
+            sm[SM_NEXT_ID] = next_id;
+            const int f = sm[SM_ASSOC_FRAMES];
+            const int f1 = f > (1 << 30) ? f : f + T;
+            sm[SM_ASSOC_FRAMES] = f1;
+            *ss = f1;                                   // (a saturated counter never validates: the test above)
+        }
+    };
+    // ---- register form (tcap <= 64, hence every frame <= 64 boxes; T <= 64) ----
+    // associate_mem_kernel's, with vx, vy in two more registers per lane.  The table does not change within a frame but for the
+    // claims, so lane j predicts its entry once per frame, in front of the chain over the boxes.  On a claim the winner's stored
+    // x, y, age, vx, vy reach every lane by v_readlane at the wave-uniform bj and lane i selects its new velocity; the rebuild
+    // pushes nine values through ds_permute.
+    if (tcap <= 64 && T <= 64) {
+        const int cnt_l = lane < T ? min(cnt[lane], cap) : 0;
+        auto request = [&](int t, float4 &q, float &ql) {
+            const int n = __builtin_amdgcn_readlane(cnt_l, t);
+            const float *src = bx + ((long long)t * cap + (lane < n ? lane : 0)) * DT_BOX_FLOATS;
+            q = *reinterpret_cast<const float4 *>(src);
+            ql = src[5];
+        };
+        float4 nq; float nl;
+        request(0, nq, nl);
+        float tbx = 0.0f, tby = 0.0f, tbw = 0.0f, tbh = 0.0f, tbl = 0.0f, tvx = 0.0f, tvy = 0.0f;
+        int tid = -1, tage = 0, outv = -1, outg = -1;
+        if constexpr (STREAM) {
+            if (lane < nt) {
+                const float *q = sb + lane * DT_BOX_FLOATS;
+                const float4 v = *reinterpret_cast<const float4 *>(q);
+                tbx = v.x; tby = v.y; tbw = v.z; tbh = v.w; tbl = q[5];
+                tid = si[lane];
+                tage = lane < n0 ? 0 : sa[lane];
+                if (vvalid) {
+                    const float2 w = *reinterpret_cast<const float2 *>(sv + lane * 2);
+                    tvx = w.x; tvy = w.y;
+                }
+            }
+        }
+        const unsigned long long below = (1ull << lane) - 1ull;
+        for (int t = 0; t < T; ++t) {
+            const int n = __builtin_amdgcn_readlane(cnt_l, t);
+            const float cx = nq.x, cy = nq.y, cw = nq.z, ch = nq.w, cl = nl;        // waits for frame t's boxes
+            if (t + 1 < T) request(t + 1, nq, nl);
+            if (t > 0 && lane < cap) {
+                id[(t - 1) * cap + lane] = outv;
+                if (gp) gp[(t - 1) * cap + lane] = outg;
+            }
+            // the entry's predicted place in this frame
+            const float tk = (float)(tage + 1);
+            const float qx = tbx + tk * tvx, qy = tby + tk * tvy;
+            int cid = -1, cgap = -1;
+            float cvx = 0.0f, cvy = 0.0f;
+            for (int i = 0; i < n; ++i) {
+                const float ax = readlane_f(cx, i), ay = readlane_f(cy, i), aw = readlane_f(cw, i), ah = readlane_f(ch, i);
+                const float al = readlane_f(cl, i);
+                const float iou = bbox_iou_ref(ax, ay, aw, ah, qx, qy, tbw, tbh);
+                const unsigned key = (lane < nt && tid >= 0 && tage <= max_age && tbl == al && iou >= thr) ? __float_as_uint(iou) + 1u : 0u;
+                const unsigned m = wave_umax_dpp(key);
+                int my_id, my_gap = -1;
+                float nvx = 0.0f, nvy = 0.0f;           // a new track starts at rest
+                if (m != 0u) {
+                    const int bj = __ffsll((long long)__ballot(key == m)) - 1;
+                    my_id = __builtin_amdgcn_readlane(tid, bj);
+                    my_gap = __builtin_amdgcn_readlane(tage, bj);
+                    const float ex = readlane_f(tbx, bj), ey = readlane_f(tby, bj);
+                    const float evx = readlane_f(tvx, bj), evy = readlane_f(tvy, bj);
+                    const float k = (float)(my_gap + 1);
+                    const float ox = (ax - ex) / k, oy = (ay - ey) / k;
+                    nvx = evx + gain * (ox - evx);
+                    nvy = evy + gain * (oy - evy);
+                    tid = lane == bj ? -1 : tid;        // claimed
+                } else {
+                    my_id = next_id++;
+                }
+                cid = lane == i ? my_id : cid;
+                cgap = lane == i ? my_gap : cgap;
+                cvx = lane == i ? nvx : cvx;
+                cvy = lane == i ? nvy : cvy;
+            }
+            outv = cid; outg = cgap;                    // lanes >= n keep -1
+            // rebuild: frame t's boxes in lanes 0 .. n-1, the kept survivors behind them (associate_mem_kernel's permutation)
+            const bool surv = lane < nt && tid >= 0 && tage < max_age;
+            const unsigned long long sm_ = __ballot(surv);
+            const bool keep = surv && n + __popcll(sm_ & below) < tcap;
+            const unsigned long long km = __ballot(keep);
+            const int kept = __popcll(km);
+            const int dst = keep ? n + __popcll(km & below) : n + kept + __popcll(~km & below);
+            const int da = (dst & 63) << 2;
+            const float px = __int_as_float(__builtin_amdgcn_ds_permute(da, __float_as_int(tbx)));
+            const float py = __int_as_float(__builtin_amdgcn_ds_permute(da, __float_as_int(tby)));
+            const float pw = __int_as_float(__builtin_amdgcn_ds_permute(da, __float_as_int(tbw)));
+            const float ph = __int_as_float(__builtin_amdgcn_ds_permute(da, __float_as_int(tbh)));
+            const float pl = __int_as_float(__builtin_amdgcn_ds_permute(da, __float_as_int(tbl)));
+            const float pvx = __int_as_float(__builtin_amdgcn_ds_permute(da, __float_as_int(tvx)));
+            const float pvy = __int_as_float(__builtin_amdgcn_ds_permute(da, __float_as_int(tvy)));
+            const int pi = __builtin_amdgcn_ds_permute(da, tid);
+            const int pa = __builtin_amdgcn_ds_permute(da, tage);
+            const bool cur = lane < n;
+            tbx = cur ? cx : px; tby = cur ? cy : py; tbw = cur ? cw : pw; tbh = cur ? ch : ph; tbl = cur ? cl : pl;
+            tvx = cur ? cvx : pvx; tvy = cur ? cvy : pvy;
+            tid = cur ? cid : pi;
+            tage = cur ? 0 : pa + 1;
+            nt = n + kept; n0 = n;      // lanes >= nt: don't-care, every use above is guarded by `lane < nt`
+        }
+        if (lane < cap) {
+            id[(T - 1) * cap + lane] = outv;
+            if (gp) gp[(T - 1) * cap + lane] = outg;
+        }
+        if (lane == 0) nids[clip] = next_id;
+        if constexpr (STREAM) {
+            if (lane < nt) {
+                float4 *q = reinterpret_cast<float4 *>(sb + lane * DT_BOX_FLOATS);
+                q[0] = make_float4(tbx, tby, tbw, tbh);
+                q[1] = make_float4(0.0f, tbl, 0.0f, 0.0f);
+                si[lane] = tid;
+                sa[lane] = tage;
+                *reinterpret_cast<float2 *>(sv + lane * 2) = make_float2(tvx, tvy);
+            }
+            store_meta();
+        }
+        return;
+    }
+    // ---- general form (any tcap): associate_mem_kernel's two LDS tables, of nine words per entry ----
+    const int TS = 9 * tcap;                             // one table: [5][tcap] box fields | [tcap] ids | [tcap] ages | [2][tcap] vx, vy
+    float *A = smem, *B = smem + TS;
+    volatile int *cgap = reinterpret_cast<volatile int *>(smem + 2 * TS);      // [cap] gaps of the current frame
+    if constexpr (STREAM) {
+        volatile int *aid = reinterpret_cast<volatile int *>(A + 5 * tcap), *aage = aid + tcap;
+        for (int j = lane; j < nt; j += 64) {
+            const float *q = sb + j * 8;
+            A[j] = q[0]; A[tcap + j] = q[1]; A[2 * tcap + j] = q[2]; A[3 * tcap + j] = q[3]; A[4 * tcap + j] = q[5];
+            aid[j] = si[j];
+            aage[j] = j < n0 ? 0 : sa[j];
+            A[7 * tcap + j] = vvalid ? sv[2 * j] : 0.0f;
+            A[8 * tcap + j] = vvalid ? sv[2 * j + 1] : 0.0f;
+        }      // (the fence after frame 0's boxes below orders these too)
+    }
+    for (int t = 0; t < T; ++t) {
+        const int n = min(cnt[t], cap);
+        const float *cur = bx + (long long)t * cap * DT_BOX_FLOATS;
+        volatile int *aid = reinterpret_cast<volatile int *>(A + 5 * tcap), *aage = aid + tcap;
+        volatile int *bid = reinterpret_cast<volatile int *>(B + 5 * tcap), *bage = bid + tcap;
+        for (int j = lane; j < n; j += 64) {
+            const float *q = cur + j * 8;
+            B[j] = q[0]; B[tcap + j] = q[1]; B[2 * tcap + j] = q[2]; B[3 * tcap + j] = q[3]; B[4 * tcap + j] = q[5];
+            bage[j] = 0;
+        }
+        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
+        __builtin_amdgcn_wave_barrier();
+        for (int i = 0; i < n; ++i) {
+            const float ax = B[i], ay = B[tcap + i], aw = B[2 * tcap + i], ah = B[3 * tcap + i], al = B[4 * tcap + i];
+            unsigned bestk = 0u;
+            int bj = 0;
+            for (int j0 = 0; j0 < nt; j0 += 64) {          // 64 candidates per pass, as associate_kernel
+                const int j = j0 + lane;
+                unsigned key = 0u;
+                if (j < nt && aid[j] >= 0 && aage[j] <= max_age && A[4 * tcap + j] == al) {
+                    const float k = (float)(aage[j] + 1);
+                    const float qx = A[j] + k * A[7 * tcap + j], qy = A[tcap + j] + k * A[8 * tcap + j];
+                    const float iou = bbox_iou_ref(ax, ay, aw, ah, qx, qy, A[2 * tcap + j], A[3 * tcap + j]);
+                    if (iou >= thr) key = __float_as_uint(iou) + 1u;
+                }
+                const unsigned m = wave_umax_dpp(key);
+                if (m > bestk) {
+                    bestk = m;
+                    bj = j0 + __ffsll((long long)__ballot(key == m)) - 1;
+                }
+            }
+            int my_id, my_gap = -1;
+            float nvx = 0.0f, nvy = 0.0f;               // a new track starts at rest
+            if (bestk != 0u) {
+                my_id = aid[bj];
+                my_gap = aage[bj];
+                const float evx = A[7 * tcap + bj], evy = A[8 * tcap + bj];
+                const float k = (float)(my_gap + 1);
+                const float ox = (ax - A[bj]) / k, oy = (ay - A[tcap + bj]) / k;
+                nvx = evx + gain * (ox - evx);
+                nvy = evy + gain * (oy - evy);
+                __builtin_amdgcn_wave_barrier();
+                if (lane == 0) aid[bj] = -1;            // claimed
+            } else {
+                my_id = next_id++;
+            }
+            if (lane == 0) { bid[i] = my_id; cgap[i] = my_gap; B[7 * tcap + i] = nvx; B[8 * tcap + i] = nvy; }
+            __builtin_amdgcn_wave_barrier();
+        }
+        for (int j = lane; j < cap; j += 64) {
+            id[t * cap + j] = j < n ? bid[j] : -1;
+            if (gp) gp[t * cap + j] = j < n ? cgap[j] : -1;
+        }
+        // survivors, 64 entries per pass, compacted behind the frame's boxes by a wave scan
+        int run = n;
+        for (int j0 = 0; j0 < nt; j0 += 64) {
+            const int j = j0 + lane;
+            const bool surv = j < nt && aid[j] >= 0 && aage[j] < max_age;
+            const unsigned long long bal = __ballot(surv);
+            const int d = run + __popcll(bal & ((1ull << lane) - 1ull));
+            if (surv && d < tcap) {
+                B[d] = A[j]; B[tcap + d] = A[tcap + j]; B[2 * tcap + d] = A[2 * tcap + j]; B[3 * tcap + d] = A[3 * tcap + j];
+                B[4 * tcap + d] = A[4 * tcap + j];
+                bid[d] = aid[j];
+                bage[d] = aage[j] + 1;
+                B[7 * tcap + d] = A[7 * tcap + j]; B[8 * tcap + d] = A[8 * tcap + j];
+            }
+            run += __popcll(bal);
+        }
+        nt = min(run, tcap); n0 = n;
+        float *sw = A; A = B; B = sw;
+        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
+        __builtin_amdgcn_wave_barrier();
+    }
+    if (lane == 0) nids[clip] = next_id;
+    if constexpr (STREAM) {
+        volatile int *aid = reinterpret_cast<volatile int *>(A + 5 * tcap), *aage = aid + tcap;
+        for (int j = lane; j < nt; j += 64) {
+            float4 *q = reinterpret_cast<float4 *>(sb + j * DT_BOX_FLOATS);
+            q[0] = make_float4(A[j], A[tcap + j], A[2 * tcap + j], A[3 * tcap + j]);
+            q[1] = make_float4(0.0f, A[4 * tcap + j], 0.0f, 0.0f);
+            si[j] = aid[j];
+            sa[j] = aage[j];
+            *reinterpret_cast<float2 *>(sv + j * 2) = make_float2(A[7 * tcap + j], A[8 * tcap + j]);
+        }
+        store_meta();
+    }
+}
+
+// dynamic LDS of associate_motion_kernel: none in the register form (tcap <= 64, T <= 64); general form: two tables of 9 words per entry
+// and the frame's gaps.  More than 160 KB: launch_associate_motion refuses the arguments.
+size_t assoc_motion_lds_bytes(int T, int cap, int tcap)
+{
+    return (tcap <= 64 && T <= 64) ? 0 : ((size_t)18 * tcap + cap) * sizeof(float);
+}
+
+// 0: launched; 1: device error; 2: argument error (nothing launched).  carry.slots == null: the stateless launch.
+int launch_associate_motion(hipStream_t st, const float *boxes, const int *counts, int n_clips, int T, int cap, float thr,
+                            int max_age, int tcap, float gain, int *ids, int *nids, int *gaps, const AssocCarry &carry)
+{
+    if (n_clips <= 0) return 0;
+    if (T <= 0 || cap <= 0 || tcap < cap || tcap > SM_COUNT_MASK || max_age < 0) return 2;
+    if (!(gain >= 0.0f && gain <= 1.0f)) return 2;      // (NaN fails both comparisons)
+    const bool stream = carry.slots != nullptr;
+    if (stream && (carry.tcap != tcap || !carry.vel || !carry.vstamp)) return 2;
+    const size_t lds = assoc_motion_lds_bytes(T, cap, tcap);
+    if (lds > 160 * 1024) return 2;
+    static PerDeviceOnce attr;
+    if (attr.ensure(nullptr, [](int) {
+            return hipFuncSetAttribute(reinterpret_cast<const void *>(associate_motion_kernel<false>), hipFuncAttributeMaxDynamicSharedMemorySize,
+                                       160 * 1024) != hipSuccess ||
+                   hipFuncSetAttribute(reinterpret_cast<const void *>(associate_motion_kernel<true>), hipFuncAttributeMaxDynamicSharedMemorySize,
+                                       160 * 1024) != hipSuccess;
+        }))
+        return 1;
+    if (stream)
+        hipLaunchKernelGGL(associate_motion_kernel<true>, dim3((unsigned)n_clips), dim3(64), lds, st, boxes, counts, T, cap, thr, max_age,
+                           tcap, gain, ids, nids, gaps, carry);
+    else
+        hipLaunchKernelGGL(associate_motion_kernel<false>, dim3((unsigned)n_clips), dim3(64), lds, st, boxes, counts, T, cap, thr, max_age,
+                           tcap, gain, ids, nids, gaps, AssocCarry{nullptr, nullptr, nullptr, nullptr, nullptr, 0});
+    return hipGetLastError() == hipSuccess ? 0 : 1;
+}
+
+// ---------------------------------------------------------------------------
 // highest-score box per frame (ties -> lowest index), one wavefront per frame
 // ---------------------------------------------------------------------------
 __global__ __launch_bounds__(64) void top_box_kernel(const float *boxes, const int *counts, int cap, float *out4)

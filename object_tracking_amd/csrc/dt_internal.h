@@ -327,6 +327,9 @@ struct AssocCarry {
     int *ages;          // [n_slots][tcap]; read for the entries behind the age-0 ones only
     int *meta;          // [n_slots][STREAM_META]
     int tcap;           // entries per slot
+    float *vel = nullptr;    // [n_slots][tcap][2] track velocities (vx, vy), dt_associate_stream_motion only; null in every other launch
+    int *vstamp = nullptr;   // [n_slots] meta[SM_ASSOC_FRAMES] as the last motion call left it: the slot's velocities belong to its table only
+                             // while the two agree (0 and a saturated counter: they never do, and every velocity reads as 0)
 };
 // track memory (decode.hip:associate_mem_kernel): 2 = argument error, nothing launched (tcap < cap, max_age < 0, a table beyond the LDS, carry.tcap != tcap)
 size_t assoc_mem_lds_bytes(int T, int cap, int tcap);      // dynamic LDS the launch needs; above 160 KB the launcher refuses
@@ -334,6 +337,11 @@ int launch_associate_mem(hipStream_t st, const float *boxes, const int *counts, 
                          int max_age, int tcap, int *ids, int *nids, int *gaps /*may be null*/, const AssocCarry &carry);
 int launch_associate_stream(hipStream_t st, const float *boxes, const int *counts, int n_clips, int T, int cap,
                             float thr, int *ids, int *nids, const AssocCarry &carry);
+// track motion (decode.hip:associate_motion_kernel): the track-memory rule with every entry matched at its constant-velocity prediction.
+// 2 = argument error, nothing launched (those of launch_associate_mem, a gain outside [0, 1] or NaN, a stream launch without vel / vstamp)
+size_t assoc_motion_lds_bytes(int T, int cap, int tcap);   // dynamic LDS the launch needs; above 160 KB the launcher refuses
+int launch_associate_motion(hipStream_t st, const float *boxes, const int *counts, int n_clips, int T, int cap, float thr,
+                            int max_age, int tcap, float gain, int *ids, int *nids, int *gaps /*may be null*/, const AssocCarry &carry);
 
 // ---------------------------------------------------------------------------
 // stream slots: state that outlives a call (stream_state.hip)
@@ -347,6 +355,8 @@ enum { SM_COUNT_MASK = 0xffff, SM_AGED_SHIFT = 16 };
 // the call's slot list, from the caller's HOST array into the library-owned device list: the numbers travel as kernel arguments of a
 // launch OUTSIDE any captured graph, so neither a host synchronisation nor pinned staging is needed.  reset_meta != null: the listed slots' meta rows are zeroed too
 int launch_stream_slots(hipStream_t st, const int *h_slots, int n, int *d_list, int *reset_meta);
+// vstamp[d_list[i]] = 0 for i < n: the listed slots' velocities are invalid (dt_stream_reset, after launch_stream_slots has filled d_list)
+int launch_stream_clear_stamps(hipStream_t st, const int *d_list, int n, int *vstamp);
 struct StateMove {
     const int *slots;      // [n] device
     float *tab_h, *tab_c;  // [n_slots][row]
@@ -556,6 +566,8 @@ struct StreamTable {
     DevMem<float> boxes;       // the track table's boxes [n_slots][tcap][8]: the last frame's first, aged entries behind them
     DevMem<int> ids;           // ... their ids [n_slots][tcap]
     DevMem<int> ages;          // ... and ages [n_slots][tcap]
+    DevMem<float> vel;         // ... and velocities [n_slots][tcap][2], written and read by dt_associate_stream_motion only
+    DevMem<int> vstamp;        // [n_slots]: meta[SM_ASSOC_FRAMES] as the last motion call left it (AssocCarry::vstamp); 0 = no valid velocities
     DevMem<int> meta;          // [n_slots][STREAM_META]
     DevMem<int> list;          // [n_slots]: the slot list of the running call, filled before its launches (never a kernel argument of a captured launch)
     std::vector<char> warm;    // host mirror of meta[SM_FRAMES] != 0: decides between the gates-only launch and a full step at t = 0

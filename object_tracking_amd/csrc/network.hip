@@ -443,6 +443,7 @@ static int streams_fresh(dt_ctx *ctx)
         return DT_OK;
     }
     HIP_TRY(ctx, hipMemsetAsync(S.meta.get(), 0, (size_t)S.n_slots * STREAM_META * sizeof(int), ctx->stream));
+    HIP_TRY(ctx, hipMemsetAsync(S.vstamp.get(), 0, (size_t)S.n_slots * sizeof(int), ctx->stream));      // no slot has velocities
     std::fill(S.warm.begin(), S.warm.end(), 0);
     return DT_OK;
 }
@@ -478,9 +479,12 @@ extern "C" int dt_stream_open_tracks(dt_ctx *ctx, int n_slots, int cap, int tcap
     HIP_TRY(ctx, S.boxes.alloc((size_t)n_slots * tcap * DT_BOX_FLOATS));
     HIP_TRY(ctx, S.ids.alloc((size_t)n_slots * tcap));
     HIP_TRY(ctx, S.ages.alloc((size_t)n_slots * tcap));
+    HIP_TRY(ctx, S.vel.alloc((size_t)n_slots * tcap * 2));
+    HIP_TRY(ctx, S.vstamp.alloc((size_t)n_slots));
     HIP_TRY(ctx, S.meta.alloc((size_t)n_slots * STREAM_META));
     HIP_TRY(ctx, S.list.alloc((size_t)n_slots));
     HIP_TRY(ctx, hipMemsetAsync(S.meta.get(), 0, (size_t)n_slots * STREAM_META * sizeof(int), ctx->stream));
+    HIP_TRY(ctx, hipMemsetAsync(S.vstamp.get(), 0, (size_t)n_slots * sizeof(int), ctx->stream));
     S.n_slots = n_slots; S.cap = cap; S.tcap = tcap; S.row = (int)row;
     S.warm.assign((size_t)n_slots, 0);
     ctx->streams = std::move(S);
@@ -502,6 +506,8 @@ extern "C" int dt_stream_reset(dt_ctx *ctx, const int *h_slots, int n)
     const int rc = streams_check_list(ctx, h_slots, n);
     if (rc) return rc;
     if (launch_stream_slots(ctx->stream, h_slots, n, S.list.get(), S.meta.get())) return dt_fail(ctx, DT_ERR_DEVICE, "stream reset launch failed");
+    // a reset slot's frame counter starts over and would meet an old stamp again: the stamps go with the meta rows
+    if (launch_stream_clear_stamps(ctx->stream, S.list.get(), n, S.vstamp.get())) return dt_fail(ctx, DT_ERR_DEVICE, "stream reset launch failed");
     for (int i = 0; i < n; ++i) S.warm[h_slots[i]] = 0;
     return DT_OK;
 }
@@ -1722,6 +1728,19 @@ extern "C" int dt_associate_mem(dt_ctx *ctx, const float *d_boxes, const int *d_
     return DT_OK;
 }
 
+extern "C" int dt_associate_motion(dt_ctx *ctx, const float *d_boxes, const int *d_counts, int n_clips, int T, int cap,
+                                   float assoc_threshold, int max_age, int tcap, float gain, int *d_ids, int *d_nids, int *d_gaps)
+{
+    if (!ctx || !d_boxes || !d_counts || !d_ids || !d_nids) return dt_fail(ctx, DT_ERR_ARG, "null argument");
+    if (max_age < 0 || tcap < cap) return dt_fail(ctx, DT_ERR_ARG, "max_age must not be negative and tcap not below cap");
+    if (!(gain >= 0.0f && gain <= 1.0f)) return dt_fail(ctx, DT_ERR_ARG, "the motion gain must be in [0, 1]");
+    ProfScope ps(ctx, "associate", 0.0, 4.0 * n_clips * (double)T * cap * 12.0, "motion");
+    const int rc = launch_associate_motion(ctx->stream, d_boxes, d_counts, n_clips, T, cap, assoc_threshold, max_age, tcap, gain, d_ids,
+                                           d_nids, d_gaps, AssocCarry{nullptr, nullptr, nullptr, nullptr, nullptr, 0});
+    if (rc) return dt_fail(ctx, launch_code(rc), "associate launch failed");
+    return DT_OK;
+}
+
 // ---------------------------------------------------------------------------
 // tracker head (ConvLSTM2D + 1x1)
 // ---------------------------------------------------------------------------
@@ -2016,6 +2035,31 @@ extern "C" int dt_associate_stream_mem(dt_ctx *ctx, const float *d_boxes, const 
     ProfScope ps(ctx, "associate", 0.0, 4.0 * n * (double)(T + 2) * cap * 10.0, "stream_memory");
     rc = launch_associate_mem(ctx->stream, d_boxes, d_counts, n, T, cap, assoc_threshold, max_age, S.tcap, d_ids, d_nids, d_gaps,
                               AssocCarry{S.list.get(), S.boxes.get(), S.ids.get(), S.ages.get(), S.meta.get(), S.tcap});
+    if (rc) return dt_fail(ctx, launch_code(rc), "associate launch failed");
+    return DT_OK;
+}
+
+// dt_associate_stream_mem with the track-motion rule: the slot's velocities (StreamTable::vel) are the table's while the slot's stamp
+// says so, and this call's kernel leaves both.  The two older entries above advance the frame counter and not the stamp: after them the
+// table reads as at rest.
+extern "C" int dt_associate_stream_motion(dt_ctx *ctx, const float *d_boxes, const int *d_counts, int n, int T, int cap,
+                                          float assoc_threshold, int max_age, float gain, const int *h_slots, int *d_ids, int *d_nids,
+                                          int *d_gaps)
+{
+    if (!ctx || !d_boxes || !d_counts || !d_ids || !d_nids) return dt_fail(ctx, DT_ERR_ARG, "null argument");
+    if (n <= 0 || T <= 0) return dt_fail(ctx, DT_ERR_ARG, "n and T must be positive");
+    if (max_age < 0) return dt_fail(ctx, DT_ERR_ARG, "max_age must not be negative");
+    if (!(gain >= 0.0f && gain <= 1.0f)) return dt_fail(ctx, DT_ERR_ARG, "the motion gain must be in [0, 1]");
+    int rc = streams_check_list(ctx, h_slots, n);
+    if (rc) return rc;
+    StreamTable &S = ctx->streams;
+    if (cap != S.cap) return dt_fail(ctx, DT_ERR_ARG, "cap %d differs from the stream table's %d", cap, S.cap);
+    // refused before the slot list is written, so that an error launches nothing
+    if (assoc_motion_lds_bytes(T, cap, S.tcap) > 160 * 1024) return dt_fail(ctx, DT_ERR_ARG, "a track table of %d entries with velocities does not fit the LDS", S.tcap);
+    if (launch_stream_slots(ctx->stream, h_slots, n, S.list.get(), nullptr)) return dt_fail(ctx, DT_ERR_DEVICE, "slot list launch failed");
+    ProfScope ps(ctx, "associate", 0.0, 4.0 * n * (double)(T + 2) * cap * 12.0, "stream_motion");
+    rc = launch_associate_motion(ctx->stream, d_boxes, d_counts, n, T, cap, assoc_threshold, max_age, S.tcap, gain, d_ids, d_nids, d_gaps,
+                                 AssocCarry{S.list.get(), S.boxes.get(), S.ids.get(), S.ages.get(), S.meta.get(), S.tcap, S.vel.get(), S.vstamp.get()});
     if (rc) return dt_fail(ctx, launch_code(rc), "associate launch failed");
     return DT_OK;
 }

@@ -66,3 +66,17 @@ int launch_stream_slots(hipStream_t st, const int *h_slots, int n, int *d_list, 
     }
     return 0;
 }
+
+// the listed slots' velocity stamps: zero = the slot's stored velocities belong to no table (dt_internal.h:AssocCarry)
+__global__ __launch_bounds__(256) void stream_clear_stamps_kernel(const int *list, int n, int *vstamp)
+{
+    const int i = blockIdx.x * 256 + threadIdx.x;
+    if (i < n) vstamp[list[i]] = 0;
+}
+
+int launch_stream_clear_stamps(hipStream_t st, const int *d_list, int n, int *vstamp)
+{
+    if (n <= 0) return 0;
+    hipLaunchKernelGGL(stream_clear_stamps_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, d_list, n, vstamp);
+    return hipGetLastError() == hipSuccess ? 0 : 1;
+}

@@ -32,6 +32,7 @@ SYMBOLS = [
     "dt_gemm_split_bf16", "dt_gemm_split", "dt_policy_set", "dt_amax_read",
     "dt_stream_open", "dt_stream_reset", "dt_track_stream_forward", "dt_associate_stream",
     "dt_associate_mem", "dt_stream_open_tracks", "dt_associate_stream_mem",
+    "dt_associate_motion", "dt_associate_stream_motion",
     "dt_tiny_stream_open", "dt_tiny_stream_reset", "dt_tiny_stream_sequence", "dt_tiny_stream_forward",
 ]
 
@@ -79,6 +80,8 @@ def load_library():
     L.dt_associate_mem.argtypes = [vp, vp, vp, ci, ci, ci, cf, ci, ci, vp, vp, vp]
     L.dt_stream_open_tracks.argtypes = [vp, ci, ci, ci]
     L.dt_associate_stream_mem.argtypes = [vp, vp, vp, ci, ci, ci, cf, ci, ctypes.POINTER(ci), vp, vp, vp]
+    L.dt_associate_motion.argtypes = [vp, vp, vp, ci, ci, ci, cf, ci, ci, cf, vp, vp, vp]
+    L.dt_associate_stream_motion.argtypes = [vp, vp, vp, ci, ci, ci, cf, ci, cf, ctypes.POINTER(ci), vp, vp, vp]
     L.dt_track_row_width.argtypes = [vp]
     L.dt_track_detect.argtypes = [vp, vp, ci, ci, vp]
     L.dt_track_recurrent.argtypes = [vp, vp, ci, ci, vp, vp]
@@ -300,16 +303,24 @@ class Context(object):
         self._check(self.lib.dt_bbox_iou(self.h, _dptr(pairs), n, _dptr(out)), "dt_bbox_iou")
         return out
 
-    def associate(self, boxes, counts, assoc_threshold, max_age=0, track_cap=None, want_gaps=False):
+    def associate(self, boxes, counts, assoc_threshold, max_age=0, track_cap=None, want_gaps=False, motion_gain=None):
         """boxes [n_clips,T,cap,8], counts [n_clips,T] int32 -> ids [n_clips,T,cap], nids [n_clips].
         max_age > 0, a track_cap or want_gaps: the track-memory rule (dt_associate_mem) -- a track that misses up to max_age frames keeps
-        its id, the table of tracks holds track_cap (None: cap) entries; with want_gaps the result is (ids, nids, gaps [n_clips,T,cap])."""
+        its id, the table of tracks holds track_cap (None: cap) entries; with want_gaps the result is (ids, nids, gaps [n_clips,T,cap]).
+        motion_gain (a number in [0, 1]; None: none of it): the track-motion rule (dt_associate_motion) -- the memory rule with every
+        track matched where its velocity predicts it, whatever max_age is."""
         t = self.torch
         assert boxes.is_cuda and boxes.is_contiguous() and counts.is_contiguous() and counts.dtype == t.int32
         n_clips, T, cap, _ = boxes.shape
         ids = t.empty((n_clips, T, cap), dtype=t.int32, device=self.device)
         nids = t.empty((n_clips,), dtype=t.int32, device=self.device)
         self._sync_stream()
+        if motion_gain is not None:
+            gaps = t.empty((n_clips, T, cap), dtype=t.int32, device=self.device) if want_gaps else None
+            self._check(self.lib.dt_associate_motion(self.h, _dptr(boxes), _dptr(counts), n_clips, T, cap, float(assoc_threshold), int(max_age),
+                                                     cap if track_cap is None else int(track_cap), float(motion_gain), _dptr(ids), _dptr(nids),
+                                                     _dptr(gaps)), "dt_associate_motion")
+            return (ids, nids, gaps) if want_gaps else (ids, nids)
         if max_age != 0 or track_cap is not None or want_gaps:
             gaps = t.empty((n_clips, T, cap), dtype=t.int32, device=self.device) if want_gaps else None
             self._check(self.lib.dt_associate_mem(self.h, _dptr(boxes), _dptr(counts), n_clips, T, cap, float(assoc_threshold), int(max_age),
@@ -413,11 +424,13 @@ class Context(object):
                                                      _dptr(trk), _dptr(det)), "dt_track_stream_forward")
         return (trk, det) if want_det else trk
 
-    def associate_stream(self, boxes, counts, assoc_threshold, slots, max_age=0, want_gaps=False):
+    def associate_stream(self, boxes, counts, assoc_threshold, slots, max_age=0, want_gaps=False, motion_gain=None):
         """associate on boxes [n,T,cap,8], counts [n,T]: frame 0 of stream i is matched against the last frame slot slots[i] saw,
         ids continue across calls, nids [n] = ids opened by the stream since its reset.
         max_age > 0 or want_gaps: the track-memory rule (dt_associate_stream_mem) against the slot's track table; with want_gaps the
-        result is (ids, nids, gaps [n,T,cap])."""
+        result is (ids, nids, gaps [n,T,cap]).
+        motion_gain (a number in [0, 1]; None: none of it): the track-motion rule (dt_associate_stream_motion); a call without it makes
+        the slot's tracks forget their velocities."""
         t = self.torch
         assert boxes.is_cuda and boxes.is_contiguous() and counts.is_contiguous() and counts.dtype == t.int32
         n, T, cap, _ = boxes.shape
@@ -427,6 +440,12 @@ class Context(object):
         ids = t.empty((n, T, cap), dtype=t.int32, device=self.device)
         nids = t.empty((n,), dtype=t.int32, device=self.device)
         self._sync_stream()
+        if motion_gain is not None:
+            gaps = t.empty((n, T, cap), dtype=t.int32, device=self.device) if want_gaps else None
+            self._check(self.lib.dt_associate_stream_motion(self.h, _dptr(boxes), _dptr(counts), n, T, cap, float(assoc_threshold),
+                                                            int(max_age), float(motion_gain), arr, _dptr(ids), _dptr(nids), _dptr(gaps)),
+                        "dt_associate_stream_motion")
+            return (ids, nids, gaps) if want_gaps else (ids, nids)
         if max_age != 0 or want_gaps:
             gaps = t.empty((n, T, cap), dtype=t.int32, device=self.device) if want_gaps else None
             self._check(self.lib.dt_associate_stream_mem(self.h, _dptr(boxes), _dptr(counts), n, T, cap, float(assoc_threshold),

@@ -130,6 +130,9 @@ class MultiObjDetTracker(object):
     # a table of at most 64 entries, which needs cap <= 64 too, runs in registers)
     MAX_AGE = 0
     TRACK_CAP = None
+    # build-defined track motion: None = none; a number in [0, 1] = a track is matched where its velocity predicts
+    # it, the velocity following the observed one with this gain (whatever MAX_AGE is; the result then always carries `gaps`)
+    MOTION_GAIN = None
 
     train_image_folder = 'data/MOT17/MOT17Det/train/'
     train_annot_folder = 'data/MOT17Ann/train/'
@@ -198,7 +201,7 @@ class MultiObjDetTracker(object):
           counts [n_clips,T]        boxes per frame
           ids    [n_clips,T,cap]    track ids (-1 in unused slots), per clip from 0
           nids   [n_clips]          ids opened per clip
-          gaps   [n_clips,T,cap]    only with MAX_AGE > 0: frames the box's track had missed (0 unbroken, -1 new id / unused)
+          gaps   [n_clips,T,cap]    only with MAX_AGE > 0 or a MOTION_GAIN: frames the box's track had missed (0 unbroken, -1 new id / unused)
         One dt_track_forward (YOLOv2 x T, ConvLSTM recurrence, 1x1), one dt_decode
         over all frames, one dt_associate."""
         return self.decode_and_associate(self.model.forward(frames, want_det=False), cap=cap)
@@ -232,6 +235,10 @@ class MultiObjDetTracker(object):
         r = ctx.decode(flat, self.OBJ_THRESHOLD, self.NMS_THRESHOLD, self.ANCHORS, len(self.LABELS), cap=cap)
         boxes = r["boxes"].reshape(n, T, cap, mi355_dt.DT_BOX_FLOATS)
         counts = r["counts"].reshape(n, T)
+        if self.MOTION_GAIN is not None:
+            ids, nids, gaps = ctx.associate_stream(boxes, counts, self.ASSOC_THRESHOLD, slots, max_age=self.MAX_AGE, want_gaps=True,
+                                                   motion_gain=self.MOTION_GAIN)
+            return dict(boxes=boxes, counts=counts, ids=ids, nids=nids, gaps=gaps, netout=trk)
         if self.MAX_AGE > 0:
             ids, nids, gaps = ctx.associate_stream(boxes, counts, self.ASSOC_THRESHOLD, slots, max_age=self.MAX_AGE, want_gaps=True)
             return dict(boxes=boxes, counts=counts, ids=ids, nids=nids, gaps=gaps, netout=trk)
@@ -249,6 +256,10 @@ class MultiObjDetTracker(object):
         r = ctx.decode(flat, self.OBJ_THRESHOLD, self.NMS_THRESHOLD, self.ANCHORS, len(self.LABELS), cap=cap)
         boxes = r["boxes"].reshape(n_clips, T, cap, mi355_dt.DT_BOX_FLOATS)
         counts = r["counts"].reshape(n_clips, T)
+        if self.MOTION_GAIN is not None:
+            ids, nids, gaps = ctx.associate(boxes, counts, self.ASSOC_THRESHOLD, max_age=self.MAX_AGE, track_cap=self.TRACK_CAP,
+                                            want_gaps=True, motion_gain=self.MOTION_GAIN)
+            return dict(boxes=boxes, counts=counts, ids=ids, nids=nids, gaps=gaps, netout=trk)
         if self.MAX_AGE > 0:
             ids, nids, gaps = ctx.associate(boxes, counts, self.ASSOC_THRESHOLD, max_age=self.MAX_AGE, track_cap=self.TRACK_CAP,
                                             want_gaps=True)
