@@ -40,6 +40,8 @@ extern "C" {
 #define DT_FRAMES_F32 1   /* float32 frames, already normalised */
 
 #define DT_BOX_FLOATS 8   /* x, y, w, h, conf, label, score, cell */
+#define DT_TRACK_FLOATS 8 /* a track read-out row: x, y, w, h, label, vx, vy, 0 (dt_associate_tracks) */
+#define DT_TRACK_INTS 4   /* ... and its integers: id, age, hits, box */
 
 typedef struct dt_ctx dt_ctx;
 
@@ -52,6 +54,7 @@ DT_API int dt_set_stream(dt_ctx *ctx, void *hip_stream);
  * dt_track_stream_forward, dt_associate_stream, and the three track-memory entries dt_associate_mem, dt_stream_open_tracks, dt_associate_stream_mem
  * and the four tiny-tracker stream entries dt_tiny_stream_open, dt_tiny_stream_reset, dt_tiny_stream_sequence, dt_tiny_stream_forward
  * and the two track-motion entries dt_associate_motion, dt_associate_stream_motion
+ * and the two track read-out entries dt_associate_tracks, dt_associate_stream_tracks
  * -- additions only, the number stayed; 1.07: 1.06 + dt_gemm_split, dt_policy_set) */
 DT_API int dt_abi_version(void);
 
@@ -195,12 +198,31 @@ DT_API int dt_associate_mem(dt_ctx *ctx, const float *d_boxes, const int *d_coun
  * opens a new id starts at rest.  Survivors keep box and velocity.  All float32, every operation rounded on its own, no FMA.
  * gain in [0, 1]; gain = 0 is dt_associate_mem bit for bit.  max_age = 0 still uses the velocity: an age-0 entry is matched one step
  * ahead, and in dense scenes that can open a few more ids than dt_associate does.  w / h are not predicted; boxes must be finite.
- * No Kalman filter, no cross-label match, no optimal assignment, no minimum hit count, no read-out of predicted boxes.
+ * No Kalman filter, no cross-label match, no optimal assignment; a minimum hit count and the read-out of predicted boxes: dt_associate_tracks.
  * DT_ERR_ARG: as dt_associate_mem (the LDS tables hold 9 words per entry here, so the largest tcap is smaller), and gain outside
  * [0, 1] or NaN. */
 DT_API int dt_associate_motion(dt_ctx *ctx, const float *d_boxes, const int *d_counts,
                  int n_clips, int T, int cap, float assoc_threshold, int max_age, int tcap, float gain,
                  int *d_ids, int *d_nids, int *d_gaps);
+/* Track read-out (BUILD-DEFINED, DESIGN.md "Track identity"): dt_associate_motion with a hit count per table entry, and the table written
+ * out once per frame.  Match, velocity update, rebuild and capacity cut are dt_associate_motion's bit for bit: d_ids, d_nids, d_gaps are
+ * its outputs for any min_hits.  hits = frames in which the track had a box: 1 for a box that opens an id, the claimed entry's + 1 for a
+ * box that claims one, unchanged for an unclaimed survivor.
+ *   d_hits    [n_clips, T, cap] int32     hits of box i's track after frame t, -1 in unused entries; may be NULL (so may d_gaps)
+ *   d_tracks  [n_clips, T, tcap, DT_TRACK_FLOATS]   x, y, w, h, label, vx, vy, 0 of every CONFIRMED entry (hits >= min_hits) of the table
+ *             after frame t's rebuild and cut, compacted in table order: the frame's boxes in decode order, then the lost tracks.  An
+ *             entry of age 0 reports its stored x, y bits; one of age a >= 1 reports x + (float)a * vx, y + (float)a * vy (one multiply,
+ *             then one add): where the track is expected in frame t.  w, h, vx, vy are the stored values.
+ *   d_tinfo   [n_clips, T, tcap, DT_TRACK_INTS] int32   id, age, hits, box: the index of the entry's box in frame t, -1 for a coasting entry
+ *   d_tcounts [n_clips, T] int32          rows written; rows from there on are zero in d_tracks and -1 in d_tinfo (the buffers may
+ *             arrive uninitialised)
+ * d_tracks, d_tinfo, d_tcounts: all three, or all three NULL (no read-out).  min_hits = 1, max_age = 0: the read-out is the frame's boxes.
+ * Not done here: dropping an unconfirmed track at its first miss, a Kalman filter, a w / h model, cross-label or optimal assignment.
+ * DT_ERR_ARG: as dt_associate_motion (the LDS tables hold 10 words per entry here, so the largest tcap is smaller again), min_hits < 1,
+ * a partial read-out triple. */
+DT_API int dt_associate_tracks(dt_ctx *ctx, const float *d_boxes, const int *d_counts,
+                 int n_clips, int T, int cap, float assoc_threshold, int max_age, int tcap, float gain, int min_hits,
+                 int *d_ids, int *d_nids, int *d_gaps, int *d_hits, float *d_tracks, int *d_tinfo, int *d_tcounts);
 
 /* ---- streaming: ConvLSTM state and track ids carried across calls (addition; the reference's predict() sees one window) ---- *
  * A live stream delivers a frame, or a few, at a time.  The context holds a table of STREAM SLOTS in device memory; per slot the ConvLSTM
@@ -244,6 +266,15 @@ DT_API int dt_associate_stream_mem(dt_ctx *ctx, const float *d_boxes, const int 
  * entries do not fit the LDS; an error leaves the slots as they were. */
 DT_API int dt_associate_stream_motion(dt_ctx *ctx, const float *d_boxes, const int *d_counts, int n, int T, int cap,
                         float thr, int max_age, float gain, const int *h_slots, int *d_ids, int *d_nids, int *d_gaps);
+/* dt_associate_tracks for streams: the slot's table carries velocities and hit counts (a further [tcap] int32 per slot).  Chunks of any
+ * sizes with one max_age, one gain and one min_hits give every output of dt_associate_tracks on the concatenation with tcap = the
+ * table's, bit for bit (d_tracks / d_tinfo rows have the table's tcap).  Mixed with the other stream association entries on one slot:
+ * after dt_associate_stream_motion the velocities carry over and every track reads as hits = 1; after dt_associate_stream or
+ * dt_associate_stream_mem the velocities are forgotten too.  Errors as dt_associate_stream_motion, and DT_ERR_ARG for min_hits < 1, a
+ * partial read-out triple or a table whose 10-word entries do not fit the LDS; an error leaves the slots as they were. */
+DT_API int dt_associate_stream_tracks(dt_ctx *ctx, const float *d_boxes, const int *d_counts, int n, int T, int cap,
+                        float thr, int max_age, float gain, int min_hits, const int *h_slots, int *d_ids, int *d_nids, int *d_gaps,
+                        int *d_hits, float *d_tracks, int *d_tinfo, int *d_tcounts);
 
 /* ---- cross-stream detection exchange (multi-GPU; the reference has no counterpart) ---- *
  * north_star: "RCCL all-gather of detections over xGMI only for cross-stream association".  Each rank packs its

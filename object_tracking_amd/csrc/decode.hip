@@ -1422,6 +1422,401 @@ int launch_associate_motion(hipStream_t st, const float *boxes, const int *count
 }
 
 // ---------------------------------------------------------------------------
+// Track identity with a TRACK READ-OUT (DESIGN.md "Track identity", track read-out): the track-motion rule above, bit for bit, with
+// one more word per table entry -- HITS, the frames in which the track had a box -- and the table written out once per frame.
+// A box that opens a new id starts at hits = 1, a box that claims entry j carries hits_j + 1, an unclaimed survivor keeps its
+// hits; hits take no part in the match.  After frame t's rebuild (the cut at tcap included) the table is walked in table order
+// and every CONFIRMED entry (hits >= min_hits) becomes one row of out.tracks / out.tinfo, compacted: x, y, w, h, label, vx, vy, 0
+// and id, age, hits, box.  An entry of age 0 reports its stored x, y; one of age a >= 1 reports x + float(a)*vx, y + float(a)*vy
+// (one multiply, one add, each rounded).  Rows from the count on are written zero / -1: every row of the frame is written once.
+// A sibling of associate_motion_kernel, same two forms, chosen by the launcher from tcap and T alone.
+// STREAM: the slot's hits live in carry.hits and are the table's only while carry.hstamp[slot] equals the slot's association
+// frame counter; this kernel writes both stamps, associate_motion_kernel the velocity stamp alone -- after it every entry reads
+// as hits = 1.
+// ---------------------------------------------------------------------------
+__device__ __forceinline__ void track_row_store(float *tracks, int *tinfo, long long row, float x, float y, float w, float h, float l,
+                                                float vx, float vy, int id, int age, int hits, int box)
+{
+    float4 *q = reinterpret_cast<float4 *>(tracks + row * DT_TRACK_FLOATS);
+    q[0] = make_float4(x, y, w, h);
+    q[1] = make_float4(l, vx, vy, 0.0f);
+    *reinterpret_cast<int4 *>(tinfo + row * DT_TRACK_INTS) = make_int4(id, age, hits, box);
+}
+__device__ __forceinline__ void track_row_empty(float *tracks, int *tinfo, long long row)
+{
+    track_row_store(tracks, tinfo, row, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f, -1, -1, -1, -1);
+}
+
+template <bool STREAM>
+__global__ __launch_bounds__(64) void associate_tracks_kernel(const float *boxes, const int *counts, int T, int cap, float thr,
+                                                              int max_age, int tcap, float gain, int min_hits, int *ids, int *nids,
+                                                              int *gaps, TrackReadout out, AssocCarry carry)
+{
+    extern __shared__ __attribute__((aligned(16))) float smem[];
+    const int clip = blockIdx.x, lane = threadIdx.x;
+    const float *bx = boxes + (long long)clip * T * cap * DT_BOX_FLOATS;
+    const int *cnt = counts + (long long)clip * T;
+    int *id = ids + (long long)clip * T * cap;
+    int *gp = gaps ? gaps + (long long)clip * T * cap : nullptr;
+    int *hp = out.hits ? out.hits + (long long)clip * T * cap : nullptr;
+    // the read-out of this clip: rows [T][tcap]; null = no read-out
+    float *tk = out.tracks ? out.tracks + (long long)clip * T * tcap * DT_TRACK_FLOATS : nullptr;
+    int *ti = out.tracks ? out.tinfo + (long long)clip * T * tcap * DT_TRACK_INTS : nullptr;
+    int *tc = out.tracks ? out.tcounts + (long long)clip * T : nullptr;
+    int next_id = 0;
+    int nt = 0, n0 = 0;       // entries in the table; of them, leading entries of age 0 (the last frame's boxes)
+    float *sb = nullptr, *sv = nullptr;
+    int *si = nullptr, *sa = nullptr, *sm = nullptr, *ss = nullptr, *sh = nullptr, *shs = nullptr;
+    bool vvalid = false;      // the slot's stored velocities belong to the table it holds
+    bool hvalid = false;      // ... and so do its stored hits
+    if constexpr (STREAM) {
+        const int slot = carry.slots[clip];
+        sb = carry.boxes + (long long)slot * tcap * DT_BOX_FLOATS;
+        si = carry.ids + (long long)slot * tcap;
+        sa = carry.ages + (long long)slot * tcap;
+        sv = carry.vel + (long long)slot * tcap * 2;
+        sh = carry.hits + (long long)slot * tcap;
+        sm = carry.meta + slot * STREAM_META;
+        ss = carry.vstamp + slot;
+        shs = carry.hstamp + slot;
+        const int w = sm[SM_COUNT];
+        n0 = min(w & SM_COUNT_MASK, cap);
+        nt = min(n0 + (int)((unsigned)w >> SM_AGED_SHIFT), tcap);
+        next_id = sm[SM_NEXT_ID];
+        const int f = sm[SM_ASSOC_FRAMES];
+        const bool fok = f > 0 && f <= (1 << 30);
+        vvalid = fok && *ss == f;
+        hvalid = fok && *shs == f;
+    }
+    auto store_meta = [&]() {
+        if (lane == 0) {
+            sm[SM_COUNT] = n0 | ((nt - n0) << SM_AGED_SHIFT);
+            sm[SM_NEXT_ID] = next_id;
+            const int f = sm[SM_ASSOC_FRAMES];
+            const int f1 = f > (1 << 30) ? f : f + T;
+            sm[SM_ASSOC_FRAMES] = f1;
+            *ss = f1;                                   // (a saturated counter never validates: the test above)
+            *shs = f1;
+        }
+    };
+    // ---- register form (tcap <= 64, hence every frame <= 64 boxes; T <= 64) ----
+    // associate_motion_kernel's, with hits in one more register per lane and one more ds_permute in the rebuild.  The read-out
+    // follows the rebuild: a ballot of the confirmed lanes, a popcount below the lane, and every lane writes one row -- a
+    // confirmed lane its own, the others the empty rows behind the count.  Frame t + 1's boxes were requested at the top of
+    // iteration t, in front of these stores, so the wait for them at the top of t + 1 does not wait for the read-out.
+    if (tcap <= 64 && T <= 64) {
+        const int cnt_l = lane < T ? min(cnt[lane], cap) : 0;
+        auto request = [&](int t, float4 &q, float &ql) {
+            const int n = __builtin_amdgcn_readlane(cnt_l, t);
+            const float *src = bx + ((long long)t * cap + (lane < n ? lane : 0)) * DT_BOX_FLOATS;
+            q = *reinterpret_cast<const float4 *>(src);
+            ql = src[5];
+        };
+        float4 nq; float nl;
+        request(0, nq, nl);
+        float tbx = 0.0f, tby = 0.0f, tbw = 0.0f, tbh = 0.0f, tbl = 0.0f, tvx = 0.0f, tvy = 0.0f;
+        int tid = -1, tage = 0, thits = 0, outv = -1, outg = -1, outh = -1;
+        if constexpr (STREAM) {
+            if (lane < nt) {
+                const float *q = sb + lane * DT_BOX_FLOATS;
+                const float4 v = *reinterpret_cast<const float4 *>(q);
+                tbx = v.x; tby = v.y; tbw = v.z; tbh = v.w; tbl = q[5];
+                tid = si[lane];
+                tage = lane < n0 ? 0 : sa[lane];
+                if (vvalid) {
+                    const float2 w = *reinterpret_cast<const float2 *>(sv + lane * 2);
+                    tvx = w.x; tvy = w.y;
+                }
+                thits = hvalid ? sh[lane] : 1;
+            }
+        }
+        const unsigned long long below = (1ull << lane) - 1ull;
+        for (int t = 0; t < T; ++t) {
+            const int n = __builtin_amdgcn_readlane(cnt_l, t);
+            const float cx = nq.x, cy = nq.y, cw = nq.z, ch = nq.w, cl = nl;        // waits for frame t's boxes
+            if (t + 1 < T) request(t + 1, nq, nl);
+            if (t > 0 && lane < cap) {
+                id[(t - 1) * cap + lane] = outv;
+                if (gp) gp[(t - 1) * cap + lane] = outg;
+                if (hp) hp[(t - 1) * cap + lane] = outh;
+            }
+            // the entry's predicted place in this frame
+            const float tk_ = (float)(tage + 1);
+            const float qx = tbx + tk_ * tvx, qy = tby + tk_ * tvy;
+            int cid = -1, cgap = -1, chits = -1;
+            float cvx = 0.0f, cvy = 0.0f;
+            for (int i = 0; i < n; ++i) {
+                const float ax = readlane_f(cx, i), ay = readlane_f(cy, i), aw = readlane_f(cw, i), ah = readlane_f(ch, i);
+                const float al = readlane_f(cl, i);
+                const float iou = bbox_iou_ref(ax, ay, aw, ah, qx, qy, tbw, tbh);
+                const unsigned key = (lane < nt && tid >= 0 && tage <= max_age && tbl == al && iou >= thr) ? __float_as_uint(iou) + 1u : 0u;
+                const unsigned m = wave_umax_dpp(key);
+                int my_id, my_gap = -1, my_hits = 1;    // a new track: one frame with a box
+                float nvx = 0.0f, nvy = 0.0f;           // ... and at rest
+                if (m != 0u) {
+                    const int bj = __ffsll((long long)__ballot(key == m)) - 1;
+                    my_id = __builtin_amdgcn_readlane(tid, bj);
+                    my_gap = __builtin_amdgcn_readlane(tage, bj);
+                    my_hits = __builtin_amdgcn_readlane(thits, bj) + 1;
+                    const float ex = readlane_f(tbx, bj), ey = readlane_f(tby, bj);
+                    const float evx = readlane_f(tvx, bj), evy = readlane_f(tvy, bj);
+                    const float k = (float)(my_gap + 1);
+                    const float ox = (ax - ex) / k, oy = (ay - ey) / k;
+                    nvx = evx + gain * (ox - evx);
+                    nvy = evy + gain * (oy - evy);
+                    tid = lane == bj ? -1 : tid;        // claimed
+                } else {
+                    my_id = next_id++;
+                }
+                cid = lane == i ? my_id : cid;
+                cgap = lane == i ? my_gap : cgap;
+                chits = lane == i ? my_hits : chits;
+                cvx = lane == i ? nvx : cvx;
+                cvy = lane == i ? nvy : cvy;
+            }
+            outv = cid; outg = cgap; outh = chits;      // lanes >= n keep -1
+            // rebuild: frame t's boxes in lanes 0 .. n-1, the kept survivors behind them (associate_mem_kernel's permutation)
+            const bool surv = lane < nt && tid >= 0 && tage < max_age;
+            const unsigned long long sm_ = __ballot(surv);
+            const bool keep = surv && n + __popcll(sm_ & below) < tcap;
+            const unsigned long long km = __ballot(keep);
+            const int kept = __popcll(km);
+            const int dst = keep ? n + __popcll(km & below) : n + kept + __popcll(~km & below);
+            const int da = (dst & 63) << 2;
+            const float px = __int_as_float(__builtin_amdgcn_ds_permute(da, __float_as_int(tbx)));
+            const float py = __int_as_float(__builtin_amdgcn_ds_permute(da, __float_as_int(tby)));
+            const float pw = __int_as_float(__builtin_amdgcn_ds_permute(da, __float_as_int(tbw)));
+            const float ph = __int_as_float(__builtin_amdgcn_ds_permute(da, __float_as_int(tbh)));
+            const float pl = __int_as_float(__builtin_amdgcn_ds_permute(da, __float_as_int(tbl)));
+            const float pvx = __int_as_float(__builtin_amdgcn_ds_permute(da, __float_as_int(tvx)));
+            const float pvy = __int_as_float(__builtin_amdgcn_ds_permute(da, __float_as_int(tvy)));
+            const int pi = __builtin_amdgcn_ds_permute(da, tid);
+            const int pa = __builtin_amdgcn_ds_permute(da, tage);
+            const int phit = __builtin_amdgcn_ds_permute(da, thits);
+            const bool cur = lane < n;
+            tbx = cur ? cx : px; tby = cur ? cy : py; tbw = cur ? cw : pw; tbh = cur ? ch : ph; tbl = cur ? cl : pl;
+            tvx = cur ? cvx : pvx; tvy = cur ? cvy : pvy;
+            tid = cur ? cid : pi;
+            tage = cur ? 0 : pa + 1;
+            thits = cur ? chits : phit;
+            nt = n + kept; n0 = n;      // lanes >= nt: don't-care, every use above and below is guarded by `lane < nt`
+            // read-out of the table as it now stands; lane = table index, so an age-0 entry's box index is the lane
+            if (tk) {
+                const bool conf = lane < nt && thits >= min_hits;
+                const unsigned long long cm = __ballot(conf);
+                const int nc = __popcll(cm);
+                const int row = conf ? __popcll(cm & below) : nc + __popcll(~cm & below);
+                if (row < tcap) {
+                    const long long r = (long long)t * tcap + row;
+                    if (conf) {
+                        const float fa = (float)tage;
+                        const float rx = cur ? tbx : tbx + fa * tvx, ry = cur ? tby : tby + fa * tvy;
+                        track_row_store(tk, ti, r, rx, ry, tbw, tbh, tbl, tvx, tvy, tid, tage, thits, cur ? lane : -1);
+                    } else {
+                        track_row_empty(tk, ti, r);
+                    }
+                }
+                if (lane == 0) tc[t] = nc;
+            }
+        }
+        if (lane < cap) {
+            id[(T - 1) * cap + lane] = outv;
+            if (gp) gp[(T - 1) * cap + lane] = outg;
+            if (hp) hp[(T - 1) * cap + lane] = outh;
+        }
+        if (lane == 0) nids[clip] = next_id;
+        if constexpr (STREAM) {
+            if (lane < nt) {
+                float4 *q = reinterpret_cast<float4 *>(sb + lane * DT_BOX_FLOATS);
+                q[0] = make_float4(tbx, tby, tbw, tbh);
+                q[1] = make_float4(0.0f, tbl, 0.0f, 0.0f);
+                si[lane] = tid;
+                sa[lane] = tage;
+                *reinterpret_cast<float2 *>(sv + lane * 2) = make_float2(tvx, tvy);
+                sh[lane] = thits;
+            }
+            store_meta();
+        }
+        return;
+    }
+    // ---- general form (any tcap): associate_motion_kernel's two LDS tables, of ten words per entry ----
+    const int TS = 10 * tcap;                            // one table: [5][tcap] box fields | [tcap] ids | [tcap] ages | [2][tcap] vx, vy | [tcap] hits
+    float *A = smem, *B = smem + TS;
+    volatile int *cgap = reinterpret_cast<volatile int *>(smem + 2 * TS);      // [cap] gaps of the current frame
+    // read-out of table A (nt entries, as frame t left it): 64 entries per pass compacted by a running count, the way the survivor
+    // pass compacts; then the empty rows behind the count.  Called once the NEXT frame's boxes have been fetched (below), so these
+    // stores stand behind those loads and never in front of them.
+    auto readout = [&](int t) {
+        volatile const int *aid = reinterpret_cast<volatile const int *>(A + 5 * tcap), *aage = aid + tcap;
+        volatile const int *ahit = reinterpret_cast<volatile const int *>(A + 9 * tcap);
+        int run = 0;
+        for (int j0 = 0; j0 < nt; j0 += 64) {
+            const int j = j0 + lane;
+            const bool conf = j < nt && ahit[j] >= min_hits;
+            const unsigned long long bal = __ballot(conf);
+            if (conf) {
+                const long long r = (long long)t * tcap + run + __popcll(bal & ((1ull << lane) - 1ull));
+                const int age = aage[j];
+                const float fa = (float)age;
+                const float x = A[j], y = A[tcap + j], vx = A[7 * tcap + j], vy = A[8 * tcap + j];
+                const float rx = age == 0 ? x : x + fa * vx, ry = age == 0 ? y : y + fa * vy;
+                track_row_store(tk, ti, r, rx, ry, A[2 * tcap + j], A[3 * tcap + j], A[4 * tcap + j], vx, vy, aid[j], age, ahit[j],
+                                age == 0 ? j : -1);
+            }
+            run += __popcll(bal);
+        }
+        for (int j = run + lane; j < tcap; j += 64) track_row_empty(tk, ti, (long long)t * tcap + j);
+        if (lane == 0) tc[t] = run;
+    };
+    if constexpr (STREAM) {
+        volatile int *aid = reinterpret_cast<volatile int *>(A + 5 * tcap), *aage = aid + tcap;
+        volatile int *ahit = reinterpret_cast<volatile int *>(A + 9 * tcap);
+        for (int j = lane; j < nt; j += 64) {
+            const float *q = sb + j * 8;
+            A[j] = q[0]; A[tcap + j] = q[1]; A[2 * tcap + j] = q[2]; A[3 * tcap + j] = q[3]; A[4 * tcap + j] = q[5];
+            aid[j] = si[j];
+            aage[j] = j < n0 ? 0 : sa[j];
+            A[7 * tcap + j] = vvalid ? sv[2 * j] : 0.0f;
+            A[8 * tcap + j] = vvalid ? sv[2 * j + 1] : 0.0f;
+            ahit[j] = hvalid ? sh[j] : 1;
+        }      // (the fence after frame 0's boxes below orders these too)
+    }
+    for (int t = 0; t < T; ++t) {
+        const int n = min(cnt[t], cap);
+        const float *cur = bx + (long long)t * cap * DT_BOX_FLOATS;
+        volatile int *aid = reinterpret_cast<volatile int *>(A + 5 * tcap), *aage = aid + tcap;
+        volatile int *ahit = reinterpret_cast<volatile int *>(A + 9 * tcap);
+        volatile int *bid = reinterpret_cast<volatile int *>(B + 5 * tcap), *bage = bid + tcap;
+        volatile int *bhit = reinterpret_cast<volatile int *>(B + 9 * tcap);
+        for (int j = lane; j < n; j += 64) {
+            const float *q = cur + j * 8;
+            B[j] = q[0]; B[tcap + j] = q[1]; B[2 * tcap + j] = q[2]; B[3 * tcap + j] = q[3]; B[4 * tcap + j] = q[5];
+            bage[j] = 0;
+        }
+        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
+        __builtin_amdgcn_wave_barrier();
+        if (tk && t > 0) readout(t - 1);                  // table A is frame t-1's until the first claim below
+        for (int i = 0; i < n; ++i) {
+            const float ax = B[i], ay = B[tcap + i], aw = B[2 * tcap + i], ah = B[3 * tcap + i], al = B[4 * tcap + i];
+            unsigned bestk = 0u;
+            int bj = 0;
+            for (int j0 = 0; j0 < nt; j0 += 64) {          // 64 candidates per pass, as associate_kernel
+                const int j = j0 + lane;
+                unsigned key = 0u;
+                if (j < nt && aid[j] >= 0 && aage[j] <= max_age && A[4 * tcap + j] == al) {
+                    const float k = (float)(aage[j] + 1);
+                    const float qx = A[j] + k * A[7 * tcap + j], qy = A[tcap + j] + k * A[8 * tcap + j];
+                    const float iou = bbox_iou_ref(ax, ay, aw, ah, qx, qy, A[2 * tcap + j], A[3 * tcap + j]);
+                    if (iou >= thr) key = __float_as_uint(iou) + 1u;
+                }
+                const unsigned m = wave_umax_dpp(key);
+                if (m > bestk) {
+                    bestk = m;
+                    bj = j0 + __ffsll((long long)__ballot(key == m)) - 1;
+                }
+            }
+            int my_id, my_gap = -1, my_hits = 1;        // a new track: one frame with a box
+            float nvx = 0.0f, nvy = 0.0f;               // ... and at rest
+            if (bestk != 0u) {
+                my_id = aid[bj];
+                my_gap = aage[bj];
+                my_hits = ahit[bj] + 1;
+                const float evx = A[7 * tcap + bj], evy = A[8 * tcap + bj];
+                const float k = (float)(my_gap + 1);
+                const float ox = (ax - A[bj]) / k, oy = (ay - A[tcap + bj]) / k;
+                nvx = evx + gain * (ox - evx);
+                nvy = evy + gain * (oy - evy);
+                __builtin_amdgcn_wave_barrier();
+                if (lane == 0) aid[bj] = -1;            // claimed
+            } else {
+                my_id = next_id++;
+            }
+            if (lane == 0) { bid[i] = my_id; cgap[i] = my_gap; bhit[i] = my_hits; B[7 * tcap + i] = nvx; B[8 * tcap + i] = nvy; }
+            __builtin_amdgcn_wave_barrier();
+        }
+        for (int j = lane; j < cap; j += 64) {
+            id[t * cap + j] = j < n ? bid[j] : -1;
+            if (gp) gp[t * cap + j] = j < n ? cgap[j] : -1;
+            if (hp) hp[t * cap + j] = j < n ? bhit[j] : -1;
+        }
+        // survivors, 64 entries per pass, compacted behind the frame's boxes by a wave scan
+        int run = n;
+        for (int j0 = 0; j0 < nt; j0 += 64) {
+            const int j = j0 + lane;
+            const bool surv = j < nt && aid[j] >= 0 && aage[j] < max_age;
+            const unsigned long long bal = __ballot(surv);
+            const int d = run + __popcll(bal & ((1ull << lane) - 1ull));
+            if (surv && d < tcap) {
+                B[d] = A[j]; B[tcap + d] = A[tcap + j]; B[2 * tcap + d] = A[2 * tcap + j]; B[3 * tcap + d] = A[3 * tcap + j];
+                B[4 * tcap + d] = A[4 * tcap + j];
+                bid[d] = aid[j];
+                bage[d] = aage[j] + 1;
+                B[7 * tcap + d] = A[7 * tcap + j]; B[8 * tcap + d] = A[8 * tcap + j];
+                bhit[d] = ahit[j];
+            }
+            run += __popcll(bal);
+        }
+        nt = min(run, tcap); n0 = n;
+        float *sw = A; A = B; B = sw;
+        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
+        __builtin_amdgcn_wave_barrier();
+    }
+    if (tk) readout(T - 1);
+    if (lane == 0) nids[clip] = next_id;
+    if constexpr (STREAM) {
+        volatile int *aid = reinterpret_cast<volatile int *>(A + 5 * tcap), *aage = aid + tcap;
+        volatile int *ahit = reinterpret_cast<volatile int *>(A + 9 * tcap);
+        for (int j = lane; j < nt; j += 64) {
+            float4 *q = reinterpret_cast<float4 *>(sb + j * DT_BOX_FLOATS);
+            q[0] = make_float4(A[j], A[tcap + j], A[2 * tcap + j], A[3 * tcap + j]);
+            q[1] = make_float4(0.0f, A[4 * tcap + j], 0.0f, 0.0f);
+            si[j] = aid[j];
+            sa[j] = aage[j];
+            *reinterpret_cast<float2 *>(sv + j * 2) = make_float2(A[7 * tcap + j], A[8 * tcap + j]);
+            sh[j] = ahit[j];
+        }
+        store_meta();
+    }
+}
+
+// dynamic LDS of associate_tracks_kernel: none in the register form (tcap <= 64, T <= 64); general form: two tables of 10 words per entry
+// and the frame's gaps.  More than 160 KB: launch_associate_tracks refuses the arguments.
+size_t assoc_tracks_lds_bytes(int T, int cap, int tcap)
+{
+    return (tcap <= 64 && T <= 64) ? 0 : ((size_t)20 * tcap + cap) * sizeof(float);
+}
+
+// 0: launched; 1: device error; 2: argument error (nothing launched).  carry.slots == null: the stateless launch.
+int launch_associate_tracks(hipStream_t st, const float *boxes, const int *counts, int n_clips, int T, int cap, float thr,
+                            int max_age, int tcap, float gain, int min_hits, int *ids, int *nids, int *gaps, const TrackReadout &out,
+                            const AssocCarry &carry)
+{
+    if (T <= 0 || cap <= 0 || tcap < cap || tcap > SM_COUNT_MASK || max_age < 0 || min_hits < 1) return 2;
+    if (!(gain >= 0.0f && gain <= 1.0f)) return 2;      // (NaN fails both comparisons)
+    if ((out.tracks != nullptr) != (out.tinfo != nullptr) || (out.tracks != nullptr) != (out.tcounts != nullptr)) return 2;
+    const bool stream = carry.slots != nullptr;
+    if (stream && (carry.tcap != tcap || !carry.vel || !carry.vstamp || !carry.hits || !carry.hstamp)) return 2;
+    const size_t lds = assoc_tracks_lds_bytes(T, cap, tcap);
+    if (lds > 160 * 1024) return 2;
+    if (n_clips <= 0) return 0;
+    static PerDeviceOnce attr;
+    if (attr.ensure(nullptr, [](int) {
+            return hipFuncSetAttribute(reinterpret_cast<const void *>(associate_tracks_kernel<false>), hipFuncAttributeMaxDynamicSharedMemorySize,
+                                       160 * 1024) != hipSuccess ||
+                   hipFuncSetAttribute(reinterpret_cast<const void *>(associate_tracks_kernel<true>), hipFuncAttributeMaxDynamicSharedMemorySize,
+                                       160 * 1024) != hipSuccess;
+        }))
+        return 1;
+    if (stream)
+        hipLaunchKernelGGL(associate_tracks_kernel<true>, dim3((unsigned)n_clips), dim3(64), lds, st, boxes, counts, T, cap, thr, max_age,
+                           tcap, gain, min_hits, ids, nids, gaps, out, carry);
+    else
+        hipLaunchKernelGGL(associate_tracks_kernel<false>, dim3((unsigned)n_clips), dim3(64), lds, st, boxes, counts, T, cap, thr, max_age,
+                           tcap, gain, min_hits, ids, nids, gaps, out, AssocCarry{nullptr, nullptr, nullptr, nullptr, nullptr, 0});
+    return hipGetLastError() == hipSuccess ? 0 : 1;
+}
+
+// ---------------------------------------------------------------------------
 // highest-score box per frame (ties -> lowest index), one wavefront per frame
 // ---------------------------------------------------------------------------
 __global__ __launch_bounds__(64) void top_box_kernel(const float *boxes, const int *counts, int cap, float *out4)

@@ -330,6 +330,9 @@ struct AssocCarry {
     float *vel = nullptr;    // [n_slots][tcap][2] track velocities (vx, vy), dt_associate_stream_motion only; null in every other launch
     int *vstamp = nullptr;   // [n_slots] meta[SM_ASSOC_FRAMES] as the last motion call left it: the slot's velocities belong to its table only
                              // while the two agree (0 and a saturated counter: they never do, and every velocity reads as 0)
+    int *hits = nullptr;     // [n_slots][tcap] frames in which each track had a box, dt_associate_stream_tracks only; null in every other launch
+    int *hstamp = nullptr;   // [n_slots] as vstamp, for `hits`: written by the track read-out call alone, so after any other association entry
+                             // the two differ and every entry reads as hits = 1
 };
 // track memory (decode.hip:associate_mem_kernel): 2 = argument error, nothing launched (tcap < cap, max_age < 0, a table beyond the LDS, carry.tcap != tcap)
 size_t assoc_mem_lds_bytes(int T, int cap, int tcap);      // dynamic LDS the launch needs; above 160 KB the launcher refuses
@@ -342,6 +345,19 @@ int launch_associate_stream(hipStream_t st, const float *boxes, const int *count
 size_t assoc_motion_lds_bytes(int T, int cap, int tcap);   // dynamic LDS the launch needs; above 160 KB the launcher refuses
 int launch_associate_motion(hipStream_t st, const float *boxes, const int *counts, int n_clips, int T, int cap, float thr,
                             int max_age, int tcap, float gain, int *ids, int *nids, int *gaps /*may be null*/, const AssocCarry &carry);
+// track read-out (decode.hip:associate_tracks_kernel): the track-motion rule with a hit count per entry, and the table's confirmed entries
+// (hits >= min_hits) written out once per frame.  tracks / tinfo / tcounts: all three or none.
+// 2 = argument error, nothing launched (those of launch_associate_motion, min_hits < 1, a partial read-out triple, a stream launch without hits / hstamp)
+struct TrackReadout {
+    int *hits;          // [n_clips][T][cap] hits of each box's track after its frame, -1 in unused entries; may be null
+    float *tracks;      // [n_clips][T][tcap][DT_TRACK_FLOATS]
+    int *tinfo;         // [n_clips][T][tcap][DT_TRACK_INTS]
+    int *tcounts;       // [n_clips][T]
+};
+size_t assoc_tracks_lds_bytes(int T, int cap, int tcap);   // dynamic LDS the launch needs; above 160 KB the launcher refuses
+int launch_associate_tracks(hipStream_t st, const float *boxes, const int *counts, int n_clips, int T, int cap, float thr,
+                            int max_age, int tcap, float gain, int min_hits, int *ids, int *nids, int *gaps /*may be null*/,
+                            const TrackReadout &out, const AssocCarry &carry);
 
 // ---------------------------------------------------------------------------
 // stream slots: state that outlives a call (stream_state.hip)
@@ -355,7 +371,8 @@ enum { SM_COUNT_MASK = 0xffff, SM_AGED_SHIFT = 16 };
 // the call's slot list, from the caller's HOST array into the library-owned device list: the numbers travel as kernel arguments of a
 // launch OUTSIDE any captured graph, so neither a host synchronisation nor pinned staging is needed.  reset_meta != null: the listed slots' meta rows are zeroed too
 int launch_stream_slots(hipStream_t st, const int *h_slots, int n, int *d_list, int *reset_meta);
-// vstamp[d_list[i]] = 0 for i < n: the listed slots' velocities are invalid (dt_stream_reset, after launch_stream_slots has filled d_list)
+// vstamp[d_list[i]] = 0 for i < n: the listed slots' velocities are invalid (dt_stream_reset, after launch_stream_slots has filled d_list);
+// the hit stamps (StreamTable::hstamp) are cleared by a second call
 int launch_stream_clear_stamps(hipStream_t st, const int *d_list, int n, int *vstamp);
 struct StateMove {
     const int *slots;      // [n] device
@@ -568,6 +585,8 @@ struct StreamTable {
     DevMem<int> ages;          // ... and ages [n_slots][tcap]
     DevMem<float> vel;         // ... and velocities [n_slots][tcap][2], written and read by dt_associate_stream_motion only
     DevMem<int> vstamp;        // [n_slots]: meta[SM_ASSOC_FRAMES] as the last motion call left it (AssocCarry::vstamp); 0 = no valid velocities
+    DevMem<int> hits;          // ... and hit counts [n_slots][tcap], written and read by dt_associate_stream_tracks only
+    DevMem<int> hstamp;        // [n_slots]: as vstamp, for the hit counts (AssocCarry::hstamp); 0 = no valid hit counts
     DevMem<int> meta;          // [n_slots][STREAM_META]
     DevMem<int> list;          // [n_slots]: the slot list of the running call, filled before its launches (never a kernel argument of a captured launch)
     std::vector<char> warm;    // host mirror of meta[SM_FRAMES] != 0: decides between the gates-only launch and a full step at t = 0

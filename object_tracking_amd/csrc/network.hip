@@ -444,6 +444,7 @@ static int streams_fresh(dt_ctx *ctx)
     }
     HIP_TRY(ctx, hipMemsetAsync(S.meta.get(), 0, (size_t)S.n_slots * STREAM_META * sizeof(int), ctx->stream));
     HIP_TRY(ctx, hipMemsetAsync(S.vstamp.get(), 0, (size_t)S.n_slots * sizeof(int), ctx->stream));      // no slot has velocities
+    HIP_TRY(ctx, hipMemsetAsync(S.hstamp.get(), 0, (size_t)S.n_slots * sizeof(int), ctx->stream));      // ... nor hit counts
     std::fill(S.warm.begin(), S.warm.end(), 0);
     return DT_OK;
 }
@@ -481,10 +482,13 @@ extern "C" int dt_stream_open_tracks(dt_ctx *ctx, int n_slots, int cap, int tcap
     HIP_TRY(ctx, S.ages.alloc((size_t)n_slots * tcap));
     HIP_TRY(ctx, S.vel.alloc((size_t)n_slots * tcap * 2));
     HIP_TRY(ctx, S.vstamp.alloc((size_t)n_slots));
+    HIP_TRY(ctx, S.hits.alloc((size_t)n_slots * tcap));
+    HIP_TRY(ctx, S.hstamp.alloc((size_t)n_slots));
     HIP_TRY(ctx, S.meta.alloc((size_t)n_slots * STREAM_META));
     HIP_TRY(ctx, S.list.alloc((size_t)n_slots));
     HIP_TRY(ctx, hipMemsetAsync(S.meta.get(), 0, (size_t)n_slots * STREAM_META * sizeof(int), ctx->stream));
     HIP_TRY(ctx, hipMemsetAsync(S.vstamp.get(), 0, (size_t)n_slots * sizeof(int), ctx->stream));
+    HIP_TRY(ctx, hipMemsetAsync(S.hstamp.get(), 0, (size_t)n_slots * sizeof(int), ctx->stream));
     S.n_slots = n_slots; S.cap = cap; S.tcap = tcap; S.row = (int)row;
     S.warm.assign((size_t)n_slots, 0);
     ctx->streams = std::move(S);
@@ -508,6 +512,7 @@ extern "C" int dt_stream_reset(dt_ctx *ctx, const int *h_slots, int n)
     if (launch_stream_slots(ctx->stream, h_slots, n, S.list.get(), S.meta.get())) return dt_fail(ctx, DT_ERR_DEVICE, "stream reset launch failed");
     // a reset slot's frame counter starts over and would meet an old stamp again: the stamps go with the meta rows
     if (launch_stream_clear_stamps(ctx->stream, S.list.get(), n, S.vstamp.get())) return dt_fail(ctx, DT_ERR_DEVICE, "stream reset launch failed");
+    if (launch_stream_clear_stamps(ctx->stream, S.list.get(), n, S.hstamp.get())) return dt_fail(ctx, DT_ERR_DEVICE, "stream reset launch failed");
     for (int i = 0; i < n; ++i) S.warm[h_slots[i]] = 0;
     return DT_OK;
 }
@@ -1741,6 +1746,32 @@ extern "C" int dt_associate_motion(dt_ctx *ctx, const float *d_boxes, const int 
     return DT_OK;
 }
 
+// the checks dt_associate_tracks and dt_associate_stream_tracks share; 0 or the message of the refusal
+static const char *tracks_args_refusal(int max_age, float gain, int min_hits, const float *d_tracks, const int *d_tinfo, const int *d_tcounts)
+{
+    if (max_age < 0) return "max_age must not be negative";
+    if (!(gain >= 0.0f && gain <= 1.0f)) return "the motion gain must be in [0, 1]";
+    if (min_hits < 1) return "min_hits must be at least 1";
+    const int given = (d_tracks != nullptr) + (d_tinfo != nullptr) + (d_tcounts != nullptr);
+    if (given != 0 && given != 3) return "d_tracks, d_tinfo and d_tcounts are given all three or none";
+    return nullptr;
+}
+
+extern "C" int dt_associate_tracks(dt_ctx *ctx, const float *d_boxes, const int *d_counts, int n_clips, int T, int cap,
+                                   float assoc_threshold, int max_age, int tcap, float gain, int min_hits, int *d_ids, int *d_nids,
+                                   int *d_gaps, int *d_hits, float *d_tracks, int *d_tinfo, int *d_tcounts)
+{
+    if (!ctx || !d_boxes || !d_counts || !d_ids || !d_nids) return dt_fail(ctx, DT_ERR_ARG, "null argument");
+    if (tcap < cap) return dt_fail(ctx, DT_ERR_ARG, "tcap must not be below cap");
+    if (const char *why = tracks_args_refusal(max_age, gain, min_hits, d_tracks, d_tinfo, d_tcounts)) return dt_fail(ctx, DT_ERR_ARG, "%s", why);
+    ProfScope ps(ctx, "associate", 0.0, 4.0 * n_clips * (double)T * (cap * 13.0 + (d_tracks ? tcap * 12.0 : 0.0)), "tracks");
+    const int rc = launch_associate_tracks(ctx->stream, d_boxes, d_counts, n_clips, T, cap, assoc_threshold, max_age, tcap, gain, min_hits,
+                                           d_ids, d_nids, d_gaps, TrackReadout{d_hits, d_tracks, d_tinfo, d_tcounts},
+                                           AssocCarry{nullptr, nullptr, nullptr, nullptr, nullptr, 0});
+    if (rc) return dt_fail(ctx, launch_code(rc), "associate launch failed");
+    return DT_OK;
+}
+
 // ---------------------------------------------------------------------------
 // tracker head (ConvLSTM2D + 1x1)
 // ---------------------------------------------------------------------------
@@ -2060,6 +2091,32 @@ extern "C" int dt_associate_stream_motion(dt_ctx *ctx, const float *d_boxes, con
     ProfScope ps(ctx, "associate", 0.0, 4.0 * n * (double)(T + 2) * cap * 12.0, "stream_motion");
     rc = launch_associate_motion(ctx->stream, d_boxes, d_counts, n, T, cap, assoc_threshold, max_age, S.tcap, gain, d_ids, d_nids, d_gaps,
                                  AssocCarry{S.list.get(), S.boxes.get(), S.ids.get(), S.ages.get(), S.meta.get(), S.tcap, S.vel.get(), S.vstamp.get()});
+    if (rc) return dt_fail(ctx, launch_code(rc), "associate launch failed");
+    return DT_OK;
+}
+
+// dt_associate_stream_motion with a hit count per entry and the read-out of the confirmed tracks: the slot's hit counts (StreamTable::hits)
+// are the table's while the slot's second stamp says so, and this call's kernel leaves both stamps.  dt_associate_stream_motion advances the
+// velocity stamp alone: after it every track reads as hits = 1; after the two older entries the velocities are forgotten too.
+extern "C" int dt_associate_stream_tracks(dt_ctx *ctx, const float *d_boxes, const int *d_counts, int n, int T, int cap,
+                                          float assoc_threshold, int max_age, float gain, int min_hits, const int *h_slots, int *d_ids,
+                                          int *d_nids, int *d_gaps, int *d_hits, float *d_tracks, int *d_tinfo, int *d_tcounts)
+{
+    if (!ctx || !d_boxes || !d_counts || !d_ids || !d_nids) return dt_fail(ctx, DT_ERR_ARG, "null argument");
+    if (n <= 0 || T <= 0) return dt_fail(ctx, DT_ERR_ARG, "n and T must be positive");
+    if (const char *why = tracks_args_refusal(max_age, gain, min_hits, d_tracks, d_tinfo, d_tcounts)) return dt_fail(ctx, DT_ERR_ARG, "%s", why);
+    int rc = streams_check_list(ctx, h_slots, n);
+    if (rc) return rc;
+    StreamTable &S = ctx->streams;
+    if (cap != S.cap) return dt_fail(ctx, DT_ERR_ARG, "cap %d differs from the stream table's %d", cap, S.cap);
+    // refused before the slot list is written, so that an error launches nothing
+    if (assoc_tracks_lds_bytes(T, cap, S.tcap) > 160 * 1024) return dt_fail(ctx, DT_ERR_ARG, "a track table of %d entries with velocities and hit counts does not fit the LDS", S.tcap);
+    if (launch_stream_slots(ctx->stream, h_slots, n, S.list.get(), nullptr)) return dt_fail(ctx, DT_ERR_DEVICE, "slot list launch failed");
+    ProfScope ps(ctx, "associate", 0.0, 4.0 * n * ((double)(T + 2) * cap * 13.0 + (d_tracks ? (double)T * S.tcap * 12.0 : 0.0)), "stream_tracks");
+    rc = launch_associate_tracks(ctx->stream, d_boxes, d_counts, n, T, cap, assoc_threshold, max_age, S.tcap, gain, min_hits, d_ids, d_nids, d_gaps,
+                                 TrackReadout{d_hits, d_tracks, d_tinfo, d_tcounts},
+                                 AssocCarry{S.list.get(), S.boxes.get(), S.ids.get(), S.ages.get(), S.meta.get(), S.tcap, S.vel.get(), S.vstamp.get(),
+                                            S.hits.get(), S.hstamp.get()});
     if (rc) return dt_fail(ctx, launch_code(rc), "associate launch failed");
     return DT_OK;
 }

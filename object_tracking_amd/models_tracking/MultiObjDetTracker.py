@@ -133,6 +133,10 @@ class MultiObjDetTracker(object):
     # build-defined track motion: None = none; a number in [0, 1] = a track is matched where its velocity predicts
     # it, the velocity following the observed one with this gain (whatever MAX_AGE is; the result then always carries `gaps`)
     MOTION_GAIN = None
+    # build-defined track read-out: None = none; an int >= 1 = the result also carries `hits` and, per frame, the
+    # tracks that have had a box in at least MIN_HITS frames -- the lost ones (up to MAX_AGE frames) at their predicted place.  The
+    # match is the track-motion rule with MOTION_GAIN (None: gain 0, the track-memory rule)
+    MIN_HITS = None
 
     train_image_folder = 'data/MOT17/MOT17Det/train/'
     train_annot_folder = 'data/MOT17Ann/train/'
@@ -201,7 +205,10 @@ class MultiObjDetTracker(object):
           counts [n_clips,T]        boxes per frame
           ids    [n_clips,T,cap]    track ids (-1 in unused slots), per clip from 0
           nids   [n_clips]          ids opened per clip
-          gaps   [n_clips,T,cap]    only with MAX_AGE > 0 or a MOTION_GAIN: frames the box's track had missed (0 unbroken, -1 new id / unused)
+          gaps   [n_clips,T,cap]    only with MAX_AGE > 0, a MOTION_GAIN or MIN_HITS: frames the box's track had missed (0 unbroken, -1 new id / unused)
+        and only with MIN_HITS (the track read-out, mi355_dt.Context.associate_tracks):
+          hits   [n_clips,T,cap]    frames in which the box's track has had a box
+          tracks [n_clips,T,tcap,8], track_info [n_clips,T,tcap,4], track_counts [n_clips,T]   the confirmed tracks of every frame
         One dt_track_forward (YOLOv2 x T, ConvLSTM recurrence, 1x1), one dt_decode
         over all frames, one dt_associate."""
         return self.decode_and_associate(self.model.forward(frames, want_det=False), cap=cap)
@@ -235,6 +242,10 @@ class MultiObjDetTracker(object):
         r = ctx.decode(flat, self.OBJ_THRESHOLD, self.NMS_THRESHOLD, self.ANCHORS, len(self.LABELS), cap=cap)
         boxes = r["boxes"].reshape(n, T, cap, mi355_dt.DT_BOX_FLOATS)
         counts = r["counts"].reshape(n, T)
+        if self.MIN_HITS is not None:
+            a = ctx.associate_stream_tracks(boxes, counts, self.ASSOC_THRESHOLD, slots, self.MAX_AGE,
+                                            0.0 if self.MOTION_GAIN is None else self.MOTION_GAIN, self.MIN_HITS)
+            return dict(a, boxes=boxes, counts=counts, netout=trk)
         if self.MOTION_GAIN is not None:
             ids, nids, gaps = ctx.associate_stream(boxes, counts, self.ASSOC_THRESHOLD, slots, max_age=self.MAX_AGE, want_gaps=True,
                                                    motion_gain=self.MOTION_GAIN)
@@ -256,6 +267,10 @@ class MultiObjDetTracker(object):
         r = ctx.decode(flat, self.OBJ_THRESHOLD, self.NMS_THRESHOLD, self.ANCHORS, len(self.LABELS), cap=cap)
         boxes = r["boxes"].reshape(n_clips, T, cap, mi355_dt.DT_BOX_FLOATS)
         counts = r["counts"].reshape(n_clips, T)
+        if self.MIN_HITS is not None:
+            a = ctx.associate_tracks(boxes, counts, self.ASSOC_THRESHOLD, self.MAX_AGE, 0.0 if self.MOTION_GAIN is None else self.MOTION_GAIN,
+                                     self.MIN_HITS, track_cap=self.TRACK_CAP)
+            return dict(a, boxes=boxes, counts=counts, netout=trk)
         if self.MOTION_GAIN is not None:
             ids, nids, gaps = ctx.associate(boxes, counts, self.ASSOC_THRESHOLD, max_age=self.MAX_AGE, track_cap=self.TRACK_CAP,
                                             want_gaps=True, motion_gain=self.MOTION_GAIN)
@@ -274,8 +289,14 @@ class MultiObjDetTracker(object):
         if cap is None:
             cap = self.GRID_H * self.GRID_W * self.BOX
         z = lambda shape, dt: torch.zeros(shape, dtype=dt, device=ctx.device)
-        return dict(boxes=z((0, T, cap, mi355_dt.DT_BOX_FLOATS), torch.float32), counts=z((0, T), torch.int32),
-                    ids=z((0, T, cap), torch.int32), nids=z((0,), torch.int32), netout=None)
+        res = dict(boxes=z((0, T, cap, mi355_dt.DT_BOX_FLOATS), torch.float32), counts=z((0, T), torch.int32),
+                   ids=z((0, T, cap), torch.int32), nids=z((0,), torch.int32), netout=None)
+        if self.MIN_HITS is not None:
+            tcap = cap if self.TRACK_CAP is None else self.TRACK_CAP
+            res.update(gaps=z((0, T, cap), torch.int32), hits=z((0, T, cap), torch.int32),
+                       tracks=z((0, T, tcap, mi355_dt.DT_TRACK_FLOATS), torch.float32),
+                       track_info=z((0, T, tcap, mi355_dt.DT_TRACK_INTS), torch.int32), track_counts=z((0, T), torch.int32))
+        return res
 
     @staticmethod
     def boxes_from_result(res, clip=0):
@@ -284,6 +305,7 @@ class MultiObjDetTracker(object):
         counts = res["counts"][clip].cpu().numpy()
         ids = res["ids"][clip].cpu().numpy()
         gaps = res["gaps"][clip].cpu().numpy() if res.get("gaps") is not None else None
+        hits = res["hits"][clip].cpu().numpy() if res.get("hits") is not None else None
         out = []
         for t in range(boxes.shape[0]):
             n = min(int(counts[t]), boxes.shape[1])
@@ -296,6 +318,33 @@ class MultiObjDetTracker(object):
                 bb.track_id = int(ids[t, i])
                 # frames the track had gone without a box (0: unbroken, -1: a new id); None when the result carries no gaps (MAX_AGE = 0)
                 bb.track_gap = int(gaps[t, i]) if gaps is not None else None
+                # frames in which the track has had a box, this one included; None when the result carries no hits (MIN_HITS = None)
+                bb.track_hits = int(hits[t, i]) if hits is not None else None
+                lst.append(bb)
+            out.append(lst)
+        return out
+
+    @staticmethod
+    def tracks_from_result(res, clip=0):
+        """Host view of the track read-out (MIN_HITS set) for one clip: list over t of BoundBox lists, one box per confirmed track
+        in table order -- the frame's confirmed boxes, then the lost tracks where their velocity predicts them.  Each carries
+        .label, .track_id, .track_age (0: seen in this frame), .track_hits; a track seen in this frame has the conf and score of its
+        box, a coasting one 0."""
+        boxes = res["boxes"][clip].cpu().numpy()
+        tracks = res["tracks"][clip].cpu().numpy()
+        info = res["track_info"][clip].cpu().numpy()
+        tcounts = res["track_counts"][clip].cpu().numpy()
+        out = []
+        for t in range(tracks.shape[0]):
+            lst = []
+            for k in range(int(tcounts[t])):
+                x, y, w, h, lab = tracks[t, k, :5]
+                tid, age, nhits, box = (int(v) for v in info[t, k])
+                c, sc = (boxes[t, box, 4], boxes[t, box, 6]) if box >= 0 else (0.0, 0.0)
+                bb = BoundBox(x, y, w, h, c, None)
+                bb.label = int(lab)
+                bb.score = sc
+                bb.track_id, bb.track_age, bb.track_hits = tid, age, nhits
                 lst.append(bb)
             out.append(lst)
         return out
@@ -304,7 +353,8 @@ class MultiObjDetTracker(object):
         """Intended behaviour of MultiObjDetTracker.py:295-315: read SEQUENCE_LENGTH
         frames, one forward of the tracker, decode the TRACKING grid of every
         time step, draw and save each frame.  Returns the per-frame box lists
-        (each box carries .track_id)."""
+        (each box carries .track_id).  With MIN_HITS set the confirmed tracks are drawn and returned instead
+        (tracks_from_result): an unconfirmed box is left out, a lost track is drawn where it is expected."""
         assert len(input_paths) == self.SEQUENCE_LENGTH
         x = np.zeros((1, self.SEQUENCE_LENGTH, self.IMAGE_H, self.IMAGE_W, 3), dtype=np.uint8)
         images = []
@@ -313,7 +363,7 @@ class MultiObjDetTracker(object):
             images.append(image)
             x[0, i] = resized
         res = self.track_clips(x)
-        per_frame = self.boxes_from_result(res, 0)
+        per_frame = self.tracks_from_result(res, 0) if self.MIN_HITS is not None else self.boxes_from_result(res, 0)
         for i, boxes in enumerate(per_frame):
             image = draw_boxes(images[i], boxes, self.LABELS)
             print(len(boxes), 'Bounding Boxes Found')
