@@ -43,6 +43,10 @@ extern "C" {
 #define DT_TRACK_FLOATS 8 /* a track read-out row: x, y, w, h, label, vx, vy, 0 (dt_associate_tracks) */
 #define DT_TRACK_INTS 4   /* ... and its integers: id, age, hits, box */
 
+#define DT_MATCH_DECODE_ORDER 0 /* track match policy (dt_associate_tracks_match): boxes in decode order, entries of the box's label */
+#define DT_MATCH_BEST_FIRST 1   /* ... bit: the candidate pairs are taken best IoU first */
+#define DT_MATCH_ANY_LABEL 2    /* ... bit: labels are not compared */
+
 typedef struct dt_ctx dt_ctx;
 
 /* ---- context ---------------------------------------------------------- */
@@ -55,6 +59,7 @@ DT_API int dt_set_stream(dt_ctx *ctx, void *hip_stream);
  * and the four tiny-tracker stream entries dt_tiny_stream_open, dt_tiny_stream_reset, dt_tiny_stream_sequence, dt_tiny_stream_forward
  * and the two track-motion entries dt_associate_motion, dt_associate_stream_motion
  * and the two track read-out entries dt_associate_tracks, dt_associate_stream_tracks
+ * and the two track match policy entries dt_associate_tracks_match, dt_associate_stream_tracks_match
  * -- additions only, the number stayed; 1.07: 1.06 + dt_gemm_split, dt_policy_set) */
 DT_API int dt_abi_version(void);
 
@@ -217,11 +222,30 @@ DT_API int dt_associate_motion(dt_ctx *ctx, const float *d_boxes, const int *d_c
  *   d_tcounts [n_clips, T] int32          rows written; rows from there on are zero in d_tracks and -1 in d_tinfo (the buffers may
  *             arrive uninitialised)
  * d_tracks, d_tinfo, d_tcounts: all three, or all three NULL (no read-out).  min_hits = 1, max_age = 0: the read-out is the frame's boxes.
- * Not done here: dropping an unconfirmed track at its first miss, a Kalman filter, a w / h model, cross-label or optimal assignment.
+ * Not done here: dropping an unconfirmed track at its first miss, a Kalman filter, a w / h model, an optimal assignment; cross-label
+ * matching and a best-IoU-first order: dt_associate_tracks_match.
  * DT_ERR_ARG: as dt_associate_motion (the LDS tables hold 10 words per entry here, so the largest tcap is smaller again), min_hits < 1,
  * a partial read-out triple. */
 DT_API int dt_associate_tracks(dt_ctx *ctx, const float *d_boxes, const int *d_counts,
                  int n_clips, int T, int cap, float assoc_threshold, int max_age, int tcap, float gain, int min_hits,
+                 int *d_ids, int *d_nids, int *d_gaps, int *d_hits, float *d_tracks, int *d_tinfo, int *d_tcounts);
+/* Track match policy (BUILD-DEFINED, DESIGN.md "Track match policy"): dt_associate_tracks with the MATCH of a frame's boxes to the table
+ * chosen by the call; prediction, velocity update, hits, gaps, rebuild, capacity cut and read-out are dt_associate_tracks' bit for bit.
+ * match is a set of DT_MATCH_* bits, 0 to 3; match = 0 is dt_associate_tracks bit for bit.
+ * Candidates of a frame: pairs (box i, table entry j with age <= max_age) whose IoU -- box i against entry j's predicted box -- is at
+ * least assoc_threshold; the labels must be equal unless DT_MATCH_ANY_LABEL is set, which leaves them uncompared.
+ * Without DT_MATCH_BEST_FIRST the boxes are visited in decode order and each takes its unclaimed candidate entry of the largest IoU,
+ * ties to the lowest j.  With it the candidate pair of the largest IoU (compared as float32; ties to the lowest i, then the lowest j) is
+ * taken repeatedly: box i claims entry j, every candidate of box i and of entry j leaves the set, until the set is empty -- a result
+ * that does not depend on the order in which the frame's boxes arrive, ties apart.  Then the boxes that claimed nothing open new ids
+ * in decode order; whenever both orders find the same pairs every output is the same bit for bit.  A box that claims an entry of another
+ * label carries on its id, hits and velocity; the rebuilt entry has the box's label.
+ * Not done here: an optimal (Hungarian) assignment, a cost other than IoU.
+ * DT_ERR_ARG: as dt_associate_tracks, and match outside 0..3.  With DT_MATCH_BEST_FIRST the LDS also holds three words per box (best
+ * candidate key, its entry, claimed), 20 * tcap + 4 * cap words in all: tcap = cap fits up to 1706 (1950 without the bit); a table
+ * with tcap <= 64 and T <= 64 runs in registers and keeps only the frame's keys, 256 * cap bytes, in the LDS. */
+DT_API int dt_associate_tracks_match(dt_ctx *ctx, const float *d_boxes, const int *d_counts,
+                 int n_clips, int T, int cap, float assoc_threshold, int max_age, int tcap, float gain, int min_hits, int match,
                  int *d_ids, int *d_nids, int *d_gaps, int *d_hits, float *d_tracks, int *d_tinfo, int *d_tcounts);
 
 /* ---- streaming: ConvLSTM state and track ids carried across calls (addition; the reference's predict() sees one window) ---- *
@@ -275,6 +299,14 @@ DT_API int dt_associate_stream_motion(dt_ctx *ctx, const float *d_boxes, const i
 DT_API int dt_associate_stream_tracks(dt_ctx *ctx, const float *d_boxes, const int *d_counts, int n, int T, int cap,
                         float thr, int max_age, float gain, int min_hits, const int *h_slots, int *d_ids, int *d_nids, int *d_gaps,
                         int *d_hits, float *d_tracks, int *d_tinfo, int *d_tcounts);
+/* dt_associate_tracks_match for streams: dt_associate_stream_tracks with the match policy of the call; match = 0 is that entry bit for
+ * bit.  The policy leaves nothing in the slot and the slot layout is dt_associate_stream_tracks': calls with different match values may
+ * follow each other on one slot, and chunks of any sizes give what dt_associate_tracks_match gives on the concatenation when every
+ * chunk uses the same match.  Errors as dt_associate_stream_tracks, and DT_ERR_ARG for match outside 0..3 or, with DT_MATCH_BEST_FIRST,
+ * a table that does not fit the LDS beside the order's three words per box; an error leaves the slots as they were. */
+DT_API int dt_associate_stream_tracks_match(dt_ctx *ctx, const float *d_boxes, const int *d_counts, int n, int T, int cap,
+                        float thr, int max_age, float gain, int min_hits, int match, const int *h_slots, int *d_ids, int *d_nids,
+                        int *d_gaps, int *d_hits, float *d_tracks, int *d_tinfo, int *d_tcounts);
 
 /* ---- cross-stream detection exchange (multi-GPU; the reference has no counterpart) ---- *
  * north_star: "RCCL all-gather of detections over xGMI only for cross-stream association".  Each rank packs its

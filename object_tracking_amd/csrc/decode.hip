@@ -1433,6 +1433,11 @@ int launch_associate_motion(hipStream_t st, const float *boxes, const int *count
 // STREAM: the slot's hits live in carry.hits and are the table's only while carry.hstamp[slot] equals the slot's association
 // frame counter; this kernel writes both stamps, associate_motion_kernel the velocity stamp alone -- after it every entry reads
 // as hits = 1.
+// MATCH (DESIGN.md "Track identity", track match policy): DT_MATCH_* bits chosen by the call, a template parameter so that 0 is the
+// code this kernel had.  ANY_LABEL drops the label comparison from the candidate test.  BEST_FIRST replaces the match block of each
+// form: instead of the boxes in decode order, the candidate pair (box, entry) with the largest IoU key is taken repeatedly, ties to
+// the lowest box, then the lowest entry; the boxes left over open their ids in decode order afterwards.  Load, rebuild, hits,
+// read-out and store are shared by all four.
 // ---------------------------------------------------------------------------
 __device__ __forceinline__ void track_row_store(float *tracks, int *tinfo, long long row, float x, float y, float w, float h, float l,
                                                 float vx, float vy, int id, int age, int hits, int box)
@@ -1447,11 +1452,12 @@ __device__ __forceinline__ void track_row_empty(float *tracks, int *tinfo, long 
     track_row_store(tracks, tinfo, row, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f, -1, -1, -1, -1);
 }
 
-template <bool STREAM>
+template <bool STREAM, int MATCH>
 __global__ __launch_bounds__(64) void associate_tracks_kernel(const float *boxes, const int *counts, int T, int cap, float thr,
                                                               int max_age, int tcap, float gain, int min_hits, int *ids, int *nids,
                                                               int *gaps, TrackReadout out, AssocCarry carry)
 {
+    constexpr bool BEST = (MATCH & DT_MATCH_BEST_FIRST) != 0, ANY = (MATCH & DT_MATCH_ANY_LABEL) != 0;
     extern __shared__ __attribute__((aligned(16))) float smem[];
     const int clip = blockIdx.x, lane = threadIdx.x;
     const float *bx = boxes + (long long)clip * T * cap * DT_BOX_FLOATS;
@@ -1545,11 +1551,82 @@ __global__ __launch_bounds__(64) void associate_tracks_kernel(const float *boxes
             const float qx = tbx + tk_ * tvx, qy = tby + tk_ * tvy;
             int cid = -1, cgap = -1, chits = -1;
             float cvx = 0.0f, cvy = 0.0f;
+            if constexpr (BEST) {
+                // best-IoU-first order: the frame's keys are an [n][64] tile of dynamic LDS, column = lane = entry, and a lane
+                // reads and writes its own column only.  Each lane caches its column's best remaining (key, box), ties to the
+                // lowest box.  A round: the wave-wide largest cached key, among its lanes the lowest box, among those the
+                // lowest lane; box bi claims entry bj; the lanes whose cached box was bi walk their column again.  The rounds only
+                // note the claim (lane bi keeps bj): what the box inherits is fetched and computed once per frame behind them,
+                // lane = box, with the decode-order loop's operations on the same operands.
+                unsigned *km = reinterpret_cast<unsigned *>(smem) + lane;
+                const bool live = lane < nt && tid >= 0 && tage <= max_age;
+                unsigned bk = 0u;
+                int bb = 0;
+                for (int i = 0; i < n; ++i) {
+                    const float ax = readlane_f(cx, i), ay = readlane_f(cy, i), aw = readlane_f(cw, i), ah = readlane_f(ch, i);
+                    const float al = readlane_f(cl, i);
+                    const float iou = bbox_iou_ref(ax, ay, aw, ah, qx, qy, tbw, tbh);
+                    const unsigned key = (live && (ANY || tbl == al) && iou >= thr) ? __float_as_uint(iou) + 1u : 0u;
+                    km[i * 64] = key;
+                    if (key > bk) { bk = key; bb = i; }
+                }
+                unsigned long long taken = 0ull;        // boxes that have claimed an entry
+                const int tid0 = tid;                   // the entries' ids before the claims mark them
+                int cent = -1;                          // lane = box: the entry it claimed
+                for (;;) {
+                    const unsigned m = wave_umax_dpp(bk);
+                    if (m == 0u) break;
+                    const int bi = 64 - (int)wave_umax_dpp(bk == m ? (unsigned)(64 - bb) : 0u);
+                    const int bj = __ffsll((long long)__ballot(bk == m && bb == bi)) - 1;
+                    cent = lane == bi ? bj : cent;
+                    taken |= 1ull << bi;
+                    if (lane == bj) {
+                        tid = -1;                       // claimed
+                        bk = 0u;
+                    } else if (bk != 0u && bb == bi) {
+                        bk = 0u;
+                        for (int i = 0; i < n; i += 4) {        // four keys of the column in flight
+                            unsigned k4[4];
+#pragma unroll
+                            for (int u = 0; u < 4; ++u) k4[u] = km[min(i + u, n - 1) * 64];
+#pragma unroll
+                            for (int u = 0; u < 4; ++u) {
+                                const int iu = i + u;
+                                const unsigned key = (iu < n && !((taken >> (iu & 63)) & 1ull)) ? k4[u] : 0u;
+                                if (key > bk) { bk = key; bb = iu; }
+                            }
+                        }
+                    }
+                }
+                // what a box inherits from the entry it claimed (every lane takes part in the lane reads)
+                {
+                    const int src = (cent >= 0 ? cent : 0) << 2;
+                    const int e_id = __builtin_amdgcn_ds_bpermute(src, tid0);
+                    const int e_age = __builtin_amdgcn_ds_bpermute(src, tage);
+                    const int e_hits = __builtin_amdgcn_ds_bpermute(src, thits);
+                    const float ex = __int_as_float(__builtin_amdgcn_ds_bpermute(src, __float_as_int(tbx)));
+                    const float ey = __int_as_float(__builtin_amdgcn_ds_bpermute(src, __float_as_int(tby)));
+                    const float evx = __int_as_float(__builtin_amdgcn_ds_bpermute(src, __float_as_int(tvx)));
+                    const float evy = __int_as_float(__builtin_amdgcn_ds_bpermute(src, __float_as_int(tvy)));
+                    if (cent >= 0) {
+                        const float k = (float)(e_age + 1);
+                        const float ox = (cx - ex) / k, oy = (cy - ey) / k;
+                        cid = e_id; cgap = e_age; chits = e_hits + 1;
+                        cvx = evx + gain * (ox - evx);
+                        cvy = evy + gain * (oy - evy);
+                    }
+                }
+                // the boxes that claimed nothing open ids in decode order, at hits = 1 and at rest
+                const bool fresh = lane < n && cent < 0;
+                const unsigned long long fm = __ballot(fresh);
+                if (fresh) { cid = next_id + __popcll(fm & below); cgap = -1; chits = 1; }
+                next_id += __popcll(fm);
+            } else
             for (int i = 0; i < n; ++i) {
                 const float ax = readlane_f(cx, i), ay = readlane_f(cy, i), aw = readlane_f(cw, i), ah = readlane_f(ch, i);
                 const float al = readlane_f(cl, i);
                 const float iou = bbox_iou_ref(ax, ay, aw, ah, qx, qy, tbw, tbh);
-                const unsigned key = (lane < nt && tid >= 0 && tage <= max_age && tbl == al && iou >= thr) ? __float_as_uint(iou) + 1u : 0u;
+                const unsigned key = (lane < nt && tid >= 0 && tage <= max_age && (ANY || tbl == al) && iou >= thr) ? __float_as_uint(iou) + 1u : 0u;
                 const unsigned m = wave_umax_dpp(key);
                 int my_id, my_gap = -1, my_hits = 1;    // a new track: one frame with a box
                 float nvx = 0.0f, nvy = 0.0f;           // ... and at rest
@@ -1643,6 +1720,10 @@ __global__ __launch_bounds__(64) void associate_tracks_kernel(const float *boxes
     const int TS = 10 * tcap;                            // one table: [5][tcap] box fields | [tcap] ids | [tcap] ages | [2][tcap] vx, vy | [tcap] hits
     float *A = smem, *B = smem + TS;
     volatile int *cgap = reinterpret_cast<volatile int *>(smem + 2 * TS);      // [cap] gaps of the current frame
+    // best-IoU-first order only: per box its best remaining candidate (key, entry) and whether it has claimed one, [cap] each
+    volatile unsigned *bkey = reinterpret_cast<volatile unsigned *>(smem + 2 * TS + cap);
+    volatile int *bent = reinterpret_cast<volatile int *>(smem + 2 * TS + 2 * cap);
+    volatile int *bdone = reinterpret_cast<volatile int *>(smem + 2 * TS + 3 * cap);
     // read-out of table A (nt entries, as frame t left it): 64 entries per pass compacted by a running count, the way the survivor
     // pass compacts; then the empty rows behind the count.  Called once the NEXT frame's boxes have been fetched (below), so these
     // stores stand behind those loads and never in front of them.
@@ -1692,10 +1773,93 @@ __global__ __launch_bounds__(64) void associate_tracks_kernel(const float *boxes
             const float *q = cur + j * 8;
             B[j] = q[0]; B[tcap + j] = q[1]; B[2 * tcap + j] = q[2]; B[3 * tcap + j] = q[3]; B[4 * tcap + j] = q[5];
             bage[j] = 0;
+            if constexpr (BEST) bdone[j] = 0;
         }
         __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
         __builtin_amdgcn_wave_barrier();
         if (tk && t > 0) readout(t - 1);                  // table A is frame t-1's until the first claim below
+        if constexpr (BEST) {
+            // best-IoU-first order.  scan(i): box i's best candidate among the unclaimed entries, 64 entries per pass, ties to the
+            // lowest entry -- the decode-order match's inner loop -- cached in bkey / bent.  A round: the largest cached key over
+            // the boxes, 64 per pass, ties to the lowest box; that box claims its cached entry; the boxes still unmatched whose
+            // cached entry it was are scanned again.  A matched box's key is 0, so the rounds end when no candidate is left.
+            // A claim marks the entry by complementing its id (negative, like the decode-order loop's -1, and still readable)
+            // and leaves the box's cached entry standing; what the boxes inherit is computed behind the rounds, lane = box.
+            auto scan = [&](int i) {
+                const float ax = B[i], ay = B[tcap + i], aw = B[2 * tcap + i], ah = B[3 * tcap + i], al = B[4 * tcap + i];
+                unsigned bestk = 0u;
+                int bj = 0;
+                for (int j0 = 0; j0 < nt; j0 += 64) {
+                    const int j = j0 + lane;
+                    unsigned key = 0u;
+                    if (j < nt && aid[j] >= 0 && aage[j] <= max_age && (ANY || A[4 * tcap + j] == al)) {
+                        const float k = (float)(aage[j] + 1);
+                        const float qx = A[j] + k * A[7 * tcap + j], qy = A[tcap + j] + k * A[8 * tcap + j];
+                        const float iou = bbox_iou_ref(ax, ay, aw, ah, qx, qy, A[2 * tcap + j], A[3 * tcap + j]);
+                        if (iou >= thr) key = __float_as_uint(iou) + 1u;
+                    }
+                    const unsigned m = wave_umax_dpp(key);
+                    if (m > bestk) {
+                        bestk = m;
+                        bj = j0 + __ffsll((long long)__ballot(key == m)) - 1;
+                    }
+                }
+                if (lane == 0) { bkey[i] = bestk; bent[i] = bj; }
+            };
+            for (int i = 0; i < n; ++i) scan(i);
+            __builtin_amdgcn_wave_barrier();
+            for (;;) {
+                unsigned bestk = 0u;
+                int bi = 0;
+                for (int i0 = 0; i0 < n; i0 += 64) {
+                    const int i = i0 + lane;
+                    const unsigned key = i < n ? bkey[i] : 0u;
+                    const unsigned m = wave_umax_dpp(key);
+                    if (m > bestk) {
+                        bestk = m;
+                        bi = i0 + __ffsll((long long)__ballot(key == m)) - 1;
+                    }
+                }
+                if (bestk == 0u) break;
+                const int bj = bent[bi];
+                __builtin_amdgcn_wave_barrier();
+                if (lane == 0) {
+                    aid[bj] = ~aid[bj];                 // claimed
+                    bkey[bi] = 0u; bdone[bi] = 1;
+                }
+                __builtin_amdgcn_wave_barrier();
+                for (int i0 = 0; i0 < n; i0 += 64) {
+                    const int i = i0 + lane;
+                    unsigned long long again = __ballot(i < n && bkey[i] != 0u && bent[i] == bj);
+                    while (again) {
+                        scan(i0 + __ffsll((long long)again) - 1);
+                        again &= again - 1ull;
+                    }
+                }
+                __builtin_amdgcn_wave_barrier();
+            }
+            // a box that claimed an entry inherits from it; the others open ids in decode order, at hits = 1 and at rest
+            for (int i0 = 0; i0 < n; i0 += 64) {
+                const int i = i0 + lane;
+                const bool fresh = i < n && !bdone[i];
+                const unsigned long long fm = __ballot(fresh);
+                if (fresh) {
+                    bid[i] = next_id + __popcll(fm & ((1ull << lane) - 1ull));
+                    cgap[i] = -1; bhit[i] = 1; B[7 * tcap + i] = 0.0f; B[8 * tcap + i] = 0.0f;
+                } else if (i < n) {
+                    const int bj = bent[i];
+                    const int my_gap = aage[bj];
+                    const float evx = A[7 * tcap + bj], evy = A[8 * tcap + bj];
+                    const float k = (float)(my_gap + 1);
+                    const float ox = (B[i] - A[bj]) / k, oy = (B[tcap + i] - A[tcap + bj]) / k;
+                    bid[i] = ~aid[bj]; cgap[i] = my_gap; bhit[i] = ahit[bj] + 1;
+                    B[7 * tcap + i] = evx + gain * (ox - evx);
+                    B[8 * tcap + i] = evy + gain * (oy - evy);
+                }
+                next_id += __popcll(fm);
+            }
+            __builtin_amdgcn_wave_barrier();
+        } else
         for (int i = 0; i < n; ++i) {
             const float ax = B[i], ay = B[tcap + i], aw = B[2 * tcap + i], ah = B[3 * tcap + i], al = B[4 * tcap + i];
             unsigned bestk = 0u;
@@ -1703,7 +1867,7 @@ __global__ __launch_bounds__(64) void associate_tracks_kernel(const float *boxes
             for (int j0 = 0; j0 < nt; j0 += 64) {          // 64 candidates per pass, as associate_kernel
                 const int j = j0 + lane;
                 unsigned key = 0u;
-                if (j < nt && aid[j] >= 0 && aage[j] <= max_age && A[4 * tcap + j] == al) {
+                if (j < nt && aid[j] >= 0 && aage[j] <= max_age && (ANY || A[4 * tcap + j] == al)) {
                     const float k = (float)(aage[j] + 1);
                     const float qx = A[j] + k * A[7 * tcap + j], qy = A[tcap + j] + k * A[8 * tcap + j];
                     const float iou = bbox_iou_ref(ax, ay, aw, ah, qx, qy, A[2 * tcap + j], A[3 * tcap + j]);
@@ -1780,40 +1944,62 @@ __global__ __launch_bounds__(64) void associate_tracks_kernel(const float *boxes
 }
 
 // dynamic LDS of associate_tracks_kernel: none in the register form (tcap <= 64, T <= 64); general form: two tables of 10 words per entry
-// and the frame's gaps.  More than 160 KB: launch_associate_tracks refuses the arguments.
-size_t assoc_tracks_lds_bytes(int T, int cap, int tcap)
+// and the frame's gaps.  The best-IoU-first order adds a 64-column key tile of the frame's boxes in the register form and three words
+// per box in the general form.  More than 160 KB: launch_associate_tracks refuses the arguments.
+size_t assoc_tracks_lds_bytes(int T, int cap, int tcap, int match)
 {
-    return (tcap <= 64 && T <= 64) ? 0 : ((size_t)20 * tcap + cap) * sizeof(float);
+    const bool best = (match & DT_MATCH_BEST_FIRST) != 0;
+    if (tcap <= 64 && T <= 64) return best ? (size_t)64 * cap * sizeof(unsigned) : 0;      // the frame's keys, [cap][64]
+    return ((size_t)20 * tcap + (best ? 4 : 1) * cap) * sizeof(float);                     // + key, entry, claimed per box
+}
+
+// one launch of associate_tracks_kernel<STREAM, MATCH>; the attribute is set once per device and instantiation
+template <bool STREAM, int MATCH>
+static int launch_associate_tracks_as(hipStream_t st, size_t lds, const float *boxes, const int *counts, int n_clips, int T, int cap, float thr,
+                                      int max_age, int tcap, float gain, int min_hits, int *ids, int *nids, int *gaps, const TrackReadout &out,
+                                      const AssocCarry &carry)
+{
+    static PerDeviceOnce attr;
+    if (attr.ensure(nullptr, [](int) {
+            return hipFuncSetAttribute(reinterpret_cast<const void *>(associate_tracks_kernel<STREAM, MATCH>),
+                                       hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) != hipSuccess;
+        }))
+        return 1;
+    hipLaunchKernelGGL((associate_tracks_kernel<STREAM, MATCH>), dim3((unsigned)n_clips), dim3(64), lds, st, boxes, counts, T, cap, thr, max_age,
+                       tcap, gain, min_hits, ids, nids, gaps, out, carry);
+    return hipGetLastError() == hipSuccess ? 0 : 1;
 }
 
 // 0: launched; 1: device error; 2: argument error (nothing launched).  carry.slots == null: the stateless launch.
+// match: DT_MATCH_* bits, 0 = decode order within a label (the instantiation every call took before the bits existed).
 int launch_associate_tracks(hipStream_t st, const float *boxes, const int *counts, int n_clips, int T, int cap, float thr,
-                            int max_age, int tcap, float gain, int min_hits, int *ids, int *nids, int *gaps, const TrackReadout &out,
-                            const AssocCarry &carry)
+                            int max_age, int tcap, float gain, int min_hits, int match, int *ids, int *nids, int *gaps,
+                            const TrackReadout &out, const AssocCarry &carry)
 {
     if (T <= 0 || cap <= 0 || tcap < cap || tcap > SM_COUNT_MASK || max_age < 0 || min_hits < 1) return 2;
+    if (match < 0 || match > (DT_MATCH_BEST_FIRST | DT_MATCH_ANY_LABEL)) return 2;
     if (!(gain >= 0.0f && gain <= 1.0f)) return 2;      // (NaN fails both comparisons)
     if ((out.tracks != nullptr) != (out.tinfo != nullptr) || (out.tracks != nullptr) != (out.tcounts != nullptr)) return 2;
     const bool stream = carry.slots != nullptr;
     if (stream && (carry.tcap != tcap || !carry.vel || !carry.vstamp || !carry.hits || !carry.hstamp)) return 2;
-    const size_t lds = assoc_tracks_lds_bytes(T, cap, tcap);
+    const size_t lds = assoc_tracks_lds_bytes(T, cap, tcap, match);
     if (lds > 160 * 1024) return 2;
     if (n_clips <= 0) return 0;
-    static PerDeviceOnce attr;
-    if (attr.ensure(nullptr, [](int) {
-            return hipFuncSetAttribute(reinterpret_cast<const void *>(associate_tracks_kernel<false>), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                       160 * 1024) != hipSuccess ||
-                   hipFuncSetAttribute(reinterpret_cast<const void *>(associate_tracks_kernel<true>), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                       160 * 1024) != hipSuccess;
-        }))
-        return 1;
-    if (stream)
-        hipLaunchKernelGGL(associate_tracks_kernel<true>, dim3((unsigned)n_clips), dim3(64), lds, st, boxes, counts, T, cap, thr, max_age,
-                           tcap, gain, min_hits, ids, nids, gaps, out, carry);
-    else
-        hipLaunchKernelGGL(associate_tracks_kernel<false>, dim3((unsigned)n_clips), dim3(64), lds, st, boxes, counts, T, cap, thr, max_age,
-                           tcap, gain, min_hits, ids, nids, gaps, out, AssocCarry{nullptr, nullptr, nullptr, nullptr, nullptr, 0});
-    return hipGetLastError() == hipSuccess ? 0 : 1;
+    const AssocCarry none{nullptr, nullptr, nullptr, nullptr, nullptr, 0};
+#define DT_TRACKS_LAUNCH(M)                                                                                                                  \
+    case M:                                                                                                                                  \
+        return stream ? launch_associate_tracks_as<true, M>(st, lds, boxes, counts, n_clips, T, cap, thr, max_age, tcap, gain, min_hits, ids, \
+                                                            nids, gaps, out, carry)                                                          \
+                      : launch_associate_tracks_as<false, M>(st, lds, boxes, counts, n_clips, T, cap, thr, max_age, tcap, gain, min_hits, ids, \
+                                                             nids, gaps, out, none);
+    switch (match) {
+        DT_TRACKS_LAUNCH(0)
+        DT_TRACKS_LAUNCH(1)
+        DT_TRACKS_LAUNCH(2)
+        DT_TRACKS_LAUNCH(3)
+    }
+#undef DT_TRACKS_LAUNCH
+    return 2;
 }
 
 // ---------------------------------------------------------------------------

@@ -354,9 +354,11 @@ struct TrackReadout {
     int *tinfo;         // [n_clips][T][tcap][DT_TRACK_INTS]
     int *tcounts;       // [n_clips][T]
 };
-size_t assoc_tracks_lds_bytes(int T, int cap, int tcap);   // dynamic LDS the launch needs; above 160 KB the launcher refuses
+// match: the track match policy, DT_MATCH_* bits (0 = decode order within a label); outside 0..3 is an argument error too.  The
+// best-IoU-first order needs LDS of its own: the frame's keys [cap][64] in the register form, three more words per box in the general one.
+size_t assoc_tracks_lds_bytes(int T, int cap, int tcap, int match);   // dynamic LDS the launch needs; above 160 KB the launcher refuses
 int launch_associate_tracks(hipStream_t st, const float *boxes, const int *counts, int n_clips, int T, int cap, float thr,
-                            int max_age, int tcap, float gain, int min_hits, int *ids, int *nids, int *gaps /*may be null*/,
+                            int max_age, int tcap, float gain, int min_hits, int match, int *ids, int *nids, int *gaps /*may be null*/,
                             const TrackReadout &out, const AssocCarry &carry);
 
 // ---------------------------------------------------------------------------

@@ -1757,19 +1757,31 @@ static const char *tracks_args_refusal(int max_age, float gain, int min_hits, co
     return nullptr;
 }
 
-extern "C" int dt_associate_tracks(dt_ctx *ctx, const float *d_boxes, const int *d_counts, int n_clips, int T, int cap,
-                                   float assoc_threshold, int max_age, int tcap, float gain, int min_hits, int *d_ids, int *d_nids,
-                                   int *d_gaps, int *d_hits, float *d_tracks, int *d_tinfo, int *d_tcounts)
+static bool match_valid(int match) { return match >= 0 && match <= (DT_MATCH_BEST_FIRST | DT_MATCH_ANY_LABEL); }
+
+// dt_associate_tracks with the track match policy of the call (DESIGN.md "Track match policy"); match = 0 is dt_associate_tracks itself
+extern "C" int dt_associate_tracks_match(dt_ctx *ctx, const float *d_boxes, const int *d_counts, int n_clips, int T, int cap,
+                                         float assoc_threshold, int max_age, int tcap, float gain, int min_hits, int match, int *d_ids,
+                                         int *d_nids, int *d_gaps, int *d_hits, float *d_tracks, int *d_tinfo, int *d_tcounts)
 {
     if (!ctx || !d_boxes || !d_counts || !d_ids || !d_nids) return dt_fail(ctx, DT_ERR_ARG, "null argument");
     if (tcap < cap) return dt_fail(ctx, DT_ERR_ARG, "tcap must not be below cap");
     if (const char *why = tracks_args_refusal(max_age, gain, min_hits, d_tracks, d_tinfo, d_tcounts)) return dt_fail(ctx, DT_ERR_ARG, "%s", why);
-    ProfScope ps(ctx, "associate", 0.0, 4.0 * n_clips * (double)T * (cap * 13.0 + (d_tracks ? tcap * 12.0 : 0.0)), "tracks");
+    if (!match_valid(match)) return dt_fail(ctx, DT_ERR_ARG, "match must be a combination of DT_MATCH_BEST_FIRST and DT_MATCH_ANY_LABEL");
+    ProfScope ps(ctx, "associate", 0.0, 4.0 * n_clips * (double)T * (cap * 13.0 + (d_tracks ? tcap * 12.0 : 0.0)), match ? "tracks_match" : "tracks");
     const int rc = launch_associate_tracks(ctx->stream, d_boxes, d_counts, n_clips, T, cap, assoc_threshold, max_age, tcap, gain, min_hits,
-                                           d_ids, d_nids, d_gaps, TrackReadout{d_hits, d_tracks, d_tinfo, d_tcounts},
+                                           match, d_ids, d_nids, d_gaps, TrackReadout{d_hits, d_tracks, d_tinfo, d_tcounts},
                                            AssocCarry{nullptr, nullptr, nullptr, nullptr, nullptr, 0});
     if (rc) return dt_fail(ctx, launch_code(rc), "associate launch failed");
     return DT_OK;
+}
+
+extern "C" int dt_associate_tracks(dt_ctx *ctx, const float *d_boxes, const int *d_counts, int n_clips, int T, int cap,
+                                   float assoc_threshold, int max_age, int tcap, float gain, int min_hits, int *d_ids, int *d_nids,
+                                   int *d_gaps, int *d_hits, float *d_tracks, int *d_tinfo, int *d_tcounts)
+{
+    return dt_associate_tracks_match(ctx, d_boxes, d_counts, n_clips, T, cap, assoc_threshold, max_age, tcap, gain, min_hits, 0, d_ids, d_nids,
+                                     d_gaps, d_hits, d_tracks, d_tinfo, d_tcounts);
 }
 
 // ---------------------------------------------------------------------------
@@ -2098,27 +2110,41 @@ extern "C" int dt_associate_stream_motion(dt_ctx *ctx, const float *d_boxes, con
 // dt_associate_stream_motion with a hit count per entry and the read-out of the confirmed tracks: the slot's hit counts (StreamTable::hits)
 // are the table's while the slot's second stamp says so, and this call's kernel leaves both stamps.  dt_associate_stream_motion advances the
 // velocity stamp alone: after it every track reads as hits = 1; after the two older entries the velocities are forgotten too.
-extern "C" int dt_associate_stream_tracks(dt_ctx *ctx, const float *d_boxes, const int *d_counts, int n, int T, int cap,
-                                          float assoc_threshold, int max_age, float gain, int min_hits, const int *h_slots, int *d_ids,
-                                          int *d_nids, int *d_gaps, int *d_hits, float *d_tracks, int *d_tinfo, int *d_tcounts)
+// The match policy belongs to the call and leaves no trace in the slot: calls with different `match` may follow each other on one slot.
+extern "C" int dt_associate_stream_tracks_match(dt_ctx *ctx, const float *d_boxes, const int *d_counts, int n, int T, int cap,
+                                                float assoc_threshold, int max_age, float gain, int min_hits, int match, const int *h_slots,
+                                                int *d_ids, int *d_nids, int *d_gaps, int *d_hits, float *d_tracks, int *d_tinfo,
+                                                int *d_tcounts)
 {
     if (!ctx || !d_boxes || !d_counts || !d_ids || !d_nids) return dt_fail(ctx, DT_ERR_ARG, "null argument");
     if (n <= 0 || T <= 0) return dt_fail(ctx, DT_ERR_ARG, "n and T must be positive");
     if (const char *why = tracks_args_refusal(max_age, gain, min_hits, d_tracks, d_tinfo, d_tcounts)) return dt_fail(ctx, DT_ERR_ARG, "%s", why);
+    if (!match_valid(match)) return dt_fail(ctx, DT_ERR_ARG, "match must be a combination of DT_MATCH_BEST_FIRST and DT_MATCH_ANY_LABEL");
     int rc = streams_check_list(ctx, h_slots, n);
     if (rc) return rc;
     StreamTable &S = ctx->streams;
     if (cap != S.cap) return dt_fail(ctx, DT_ERR_ARG, "cap %d differs from the stream table's %d", cap, S.cap);
     // refused before the slot list is written, so that an error launches nothing
-    if (assoc_tracks_lds_bytes(T, cap, S.tcap) > 160 * 1024) return dt_fail(ctx, DT_ERR_ARG, "a track table of %d entries with velocities and hit counts does not fit the LDS", S.tcap);
+    if (assoc_tracks_lds_bytes(T, cap, S.tcap, match) > 160 * 1024)
+        return dt_fail(ctx, DT_ERR_ARG, "a track table of %d entries with velocities and hit counts%s does not fit the LDS", S.tcap,
+                       (match & DT_MATCH_BEST_FIRST) ? " and the best-first order's words per box" : "");
     if (launch_stream_slots(ctx->stream, h_slots, n, S.list.get(), nullptr)) return dt_fail(ctx, DT_ERR_DEVICE, "slot list launch failed");
-    ProfScope ps(ctx, "associate", 0.0, 4.0 * n * ((double)(T + 2) * cap * 13.0 + (d_tracks ? (double)T * S.tcap * 12.0 : 0.0)), "stream_tracks");
-    rc = launch_associate_tracks(ctx->stream, d_boxes, d_counts, n, T, cap, assoc_threshold, max_age, S.tcap, gain, min_hits, d_ids, d_nids, d_gaps,
+    ProfScope ps(ctx, "associate", 0.0, 4.0 * n * ((double)(T + 2) * cap * 13.0 + (d_tracks ? (double)T * S.tcap * 12.0 : 0.0)),
+                 match ? "stream_tracks_match" : "stream_tracks");
+    rc = launch_associate_tracks(ctx->stream, d_boxes, d_counts, n, T, cap, assoc_threshold, max_age, S.tcap, gain, min_hits, match, d_ids, d_nids, d_gaps,
                                  TrackReadout{d_hits, d_tracks, d_tinfo, d_tcounts},
                                  AssocCarry{S.list.get(), S.boxes.get(), S.ids.get(), S.ages.get(), S.meta.get(), S.tcap, S.vel.get(), S.vstamp.get(),
                                             S.hits.get(), S.hstamp.get()});
     if (rc) return dt_fail(ctx, launch_code(rc), "associate launch failed");
     return DT_OK;
+}
+
+extern "C" int dt_associate_stream_tracks(dt_ctx *ctx, const float *d_boxes, const int *d_counts, int n, int T, int cap,
+                                          float assoc_threshold, int max_age, float gain, int min_hits, const int *h_slots, int *d_ids,
+                                          int *d_nids, int *d_gaps, int *d_hits, float *d_tracks, int *d_tinfo, int *d_tcounts)
+{
+    return dt_associate_stream_tracks_match(ctx, d_boxes, d_counts, n, T, cap, assoc_threshold, max_age, gain, min_hits, 0, h_slots, d_ids,
+                                            d_nids, d_gaps, d_hits, d_tracks, d_tinfo, d_tcounts);
 }
 
 // The two halves of dt_track_forward for a FRAME-sharded deployment (BASELINE.json configs[4]):

@@ -21,6 +21,8 @@ DT_FRAMES_F32 = 1
 DT_BOX_FLOATS = 8
 DT_TRACK_FLOATS = 8      # a track read-out row: x, y, w, h, label, vx, vy, 0
 DT_TRACK_INTS = 4        # ... and its integers: id, age, hits, box
+DT_MATCH_BEST_FIRST = 1  # track match policy bits (dt_associate_tracks_match): candidate pairs taken best IoU first
+DT_MATCH_ANY_LABEL = 2   # ... labels not compared
 
 SYMBOLS = [
     "dt_create", "dt_destroy", "dt_last_error", "dt_set_stream", "dt_abi_version",
@@ -36,6 +38,7 @@ SYMBOLS = [
     "dt_associate_mem", "dt_stream_open_tracks", "dt_associate_stream_mem",
     "dt_associate_motion", "dt_associate_stream_motion",
     "dt_associate_tracks", "dt_associate_stream_tracks",
+    "dt_associate_tracks_match", "dt_associate_stream_tracks_match",
     "dt_tiny_stream_open", "dt_tiny_stream_reset", "dt_tiny_stream_sequence", "dt_tiny_stream_forward",
 ]
 
@@ -87,6 +90,8 @@ def load_library():
     L.dt_associate_stream_motion.argtypes = [vp, vp, vp, ci, ci, ci, cf, ci, cf, ctypes.POINTER(ci), vp, vp, vp]
     L.dt_associate_tracks.argtypes = [vp, vp, vp, ci, ci, ci, cf, ci, ci, cf, ci, vp, vp, vp, vp, vp, vp, vp]
     L.dt_associate_stream_tracks.argtypes = [vp, vp, vp, ci, ci, ci, cf, ci, cf, ci, ctypes.POINTER(ci), vp, vp, vp, vp, vp, vp, vp]
+    L.dt_associate_tracks_match.argtypes = [vp, vp, vp, ci, ci, ci, cf, ci, ci, cf, ci, ci, vp, vp, vp, vp, vp, vp, vp]
+    L.dt_associate_stream_tracks_match.argtypes = [vp, vp, vp, ci, ci, ci, cf, ci, cf, ci, ci, ctypes.POINTER(ci), vp, vp, vp, vp, vp, vp, vp]
     L.dt_track_row_width.argtypes = [vp]
     L.dt_track_detect.argtypes = [vp, vp, ci, ci, vp]
     L.dt_track_recurrent.argtypes = [vp, vp, ci, ci, vp, vp]
@@ -337,29 +342,39 @@ class Context(object):
         return ids, nids
 
     # ---- cross-stream exchange ------------------------------------------
-    def _tracks_outputs(self, n, T, cap, tcap):
+    def _tracks_outputs(self, n, T, cap, tcap, readout=True):
         t = self.torch
         i32 = lambda *shape: t.empty(shape, dtype=t.int32, device=self.device)
+        if not readout:
+            return dict(ids=i32(n, T, cap), nids=i32(n), gaps=i32(n, T, cap), hits=i32(n, T, cap))
         return dict(ids=i32(n, T, cap), nids=i32(n), gaps=i32(n, T, cap), hits=i32(n, T, cap),
                     tracks=t.empty((n, T, tcap, DT_TRACK_FLOATS), dtype=t.float32, device=self.device),
                     track_info=i32(n, T, tcap, DT_TRACK_INTS), track_counts=i32(n, T))
 
-    def associate_tracks(self, boxes, counts, assoc_threshold, max_age, gain, min_hits, track_cap=None):
+    def associate_tracks(self, boxes, counts, assoc_threshold, max_age, gain, min_hits, track_cap=None, match=0, readout=True):
         """The track-motion rule with a hit count per track and the read-out of the confirmed tracks (dt_associate_tracks).
         boxes [n_clips,T,cap,8], counts [n_clips,T] int32 -> dict: ids, gaps, hits [n_clips,T,cap], nids [n_clips] (ids, nids, gaps are
         associate(..., motion_gain=gain)'s; hits = frames in which the box's track has had a box), and per frame the tracks with
         hits >= min_hits in table order -- the frame's boxes, then the lost tracks at their predicted place:
         tracks [n_clips,T,tcap,8] (x, y, w, h, label, vx, vy, 0), track_info [n_clips,T,tcap,4] (id, age, hits, box; box = -1 for a
-        coasting track), track_counts [n_clips,T]; rows from the count on are 0 / -1.  tcap = track_cap (None: cap)."""
+        coasting track), track_counts [n_clips,T]; rows from the count on are 0 / -1.  tcap = track_cap (None: cap).
+        match: the track match policy, DT_MATCH_BEST_FIRST | DT_MATCH_ANY_LABEL bits (dt_associate_tracks_match); 0 = boxes in decode
+        order, entries of the box's label (dt_associate_tracks).  readout=False: no tracks / track_info / track_counts (the NULL triple)."""
         t = self.torch
         assert boxes.is_cuda and boxes.is_contiguous() and counts.is_contiguous() and counts.dtype == t.int32
         n_clips, T, cap, _ = boxes.shape
         tcap = cap if track_cap is None else int(track_cap)
-        r = self._tracks_outputs(n_clips, T, cap, max(tcap, 0))
+        r = self._tracks_outputs(n_clips, T, cap, max(tcap, 0), readout)
         self._sync_stream()
+        if match != 0:
+            self._check(self.lib.dt_associate_tracks_match(self.h, _dptr(boxes), _dptr(counts), n_clips, T, cap, float(assoc_threshold),
+                                                           int(max_age), tcap, float(gain), int(min_hits), int(match), _dptr(r["ids"]),
+                                                           _dptr(r["nids"]), _dptr(r["gaps"]), _dptr(r["hits"]), _dptr(r.get("tracks")),
+                                                           _dptr(r.get("track_info")), _dptr(r.get("track_counts"))), "dt_associate_tracks_match")
+            return r
         self._check(self.lib.dt_associate_tracks(self.h, _dptr(boxes), _dptr(counts), n_clips, T, cap, float(assoc_threshold), int(max_age),
                                                  tcap, float(gain), int(min_hits), _dptr(r["ids"]), _dptr(r["nids"]), _dptr(r["gaps"]),
-                                                 _dptr(r["hits"]), _dptr(r["tracks"]), _dptr(r["track_info"]), _dptr(r["track_counts"])),
+                                                 _dptr(r["hits"]), _dptr(r.get("tracks")), _dptr(r.get("track_info")), _dptr(r.get("track_counts"))),
                     "dt_associate_tracks")
         return r
 
@@ -487,22 +502,31 @@ class Context(object):
                                                  arr, _dptr(ids), _dptr(nids)), "dt_associate_stream")
         return ids, nids
 
-    def associate_stream_tracks(self, boxes, counts, assoc_threshold, slots, max_age, gain, min_hits):
+    def associate_stream_tracks(self, boxes, counts, assoc_threshold, slots, max_age, gain, min_hits, match=0, readout=True):
         """associate_tracks for streams (dt_associate_stream_tracks): the slot's track table carries velocities and hit counts across
         calls; the read-out has the table's track_cap rows per frame.  The dict of associate_tracks.  After a call of associate_stream
-        with a motion_gain the slot's tracks read as hits = 1; after one without, their velocities are forgotten too."""
+        with a motion_gain the slot's tracks read as hits = 1; after one without, their velocities are forgotten too.
+        match: the track match policy of this call (dt_associate_stream_tracks_match); it leaves nothing in the slot.
+        readout=False: no tracks / track_info / track_counts."""
         t = self.torch
         assert boxes.is_cuda and boxes.is_contiguous() and counts.is_contiguous() and counts.dtype == t.int32
         n, T, cap, _ = boxes.shape
         ns, arr = self._slot_array(slots)
         if ns != n:
             raise NativeError("dt_associate_stream_tracks failed (1): %d slots for %d streams" % (ns, n))
-        r = self._tracks_outputs(n, T, cap, getattr(self, "_stream_tcap", None) or cap)
+        r = self._tracks_outputs(n, T, cap, getattr(self, "_stream_tcap", None) or cap, readout)
         self._sync_stream()
+        if match != 0:
+            self._check(self.lib.dt_associate_stream_tracks_match(self.h, _dptr(boxes), _dptr(counts), n, T, cap, float(assoc_threshold),
+                                                                  int(max_age), float(gain), int(min_hits), int(match), arr, _dptr(r["ids"]),
+                                                                  _dptr(r["nids"]), _dptr(r["gaps"]), _dptr(r["hits"]), _dptr(r.get("tracks")),
+                                                                  _dptr(r.get("track_info")), _dptr(r.get("track_counts"))),
+                        "dt_associate_stream_tracks_match")
+            return r
         self._check(self.lib.dt_associate_stream_tracks(self.h, _dptr(boxes), _dptr(counts), n, T, cap, float(assoc_threshold), int(max_age),
                                                         float(gain), int(min_hits), arr, _dptr(r["ids"]), _dptr(r["nids"]), _dptr(r["gaps"]),
-                                                        _dptr(r["hits"]), _dptr(r["tracks"]), _dptr(r["track_info"]),
-                                                        _dptr(r["track_counts"])), "dt_associate_stream_tracks")
+                                                        _dptr(r["hits"]), _dptr(r.get("tracks")), _dptr(r.get("track_info")),
+                                                        _dptr(r.get("track_counts"))), "dt_associate_stream_tracks")
         return r
 
     def track_row_width(self):

@@ -137,6 +137,13 @@ class MultiObjDetTracker(object):
     # tracks that have had a box in at least MIN_HITS frames -- the lost ones (up to MAX_AGE frames) at their predicted place.  The
     # match is the track-motion rule with MOTION_GAIN (None: gain 0, the track-memory rule)
     MIN_HITS = None
+    # build-defined track match policy: how a frame's boxes are matched to the table of tracks.  Both False: boxes
+    # in decode order, each against the tracks of its own label.  MATCH_BEST_FIRST: the (box, track) pairs are taken best IoU first, so
+    # the result does not depend on the order of the frame's boxes.  MATCH_ANY_LABEL: labels are not compared, so a track survives a
+    # flipped label.  With either set the result carries `gaps` and `hits` (the match runs in the track read-out's kernel; the read-out
+    # itself still appears only with MIN_HITS)
+    MATCH_BEST_FIRST = False
+    MATCH_ANY_LABEL = False
 
     train_image_folder = 'data/MOT17/MOT17Det/train/'
     train_annot_folder = 'data/MOT17Ann/train/'
@@ -193,6 +200,9 @@ class MultiObjDetTracker(object):
         except (IndexError, ValueError):
             pass
 
+    def _match_policy(self):
+        return (mi355_dt.DT_MATCH_BEST_FIRST if self.MATCH_BEST_FIRST else 0) | (mi355_dt.DT_MATCH_ANY_LABEL if self.MATCH_ANY_LABEL else 0)
+
     def train(self):
         raise NotImplementedError("training (custom_loss_*, fit_generator) is outside the MI355X hot path this "
                                   "build covers (SURVEY.md C7/C8); only inference entry points are implemented")
@@ -205,9 +215,9 @@ class MultiObjDetTracker(object):
           counts [n_clips,T]        boxes per frame
           ids    [n_clips,T,cap]    track ids (-1 in unused slots), per clip from 0
           nids   [n_clips]          ids opened per clip
-          gaps   [n_clips,T,cap]    only with MAX_AGE > 0, a MOTION_GAIN or MIN_HITS: frames the box's track had missed (0 unbroken, -1 new id / unused)
+          gaps   [n_clips,T,cap]    only with MAX_AGE > 0, a MOTION_GAIN, MIN_HITS or a MATCH_* policy: frames the box's track had missed (0 unbroken, -1 new id / unused)
         and only with MIN_HITS (the track read-out, mi355_dt.Context.associate_tracks):
-          hits   [n_clips,T,cap]    frames in which the box's track has had a box
+          hits   [n_clips,T,cap]    frames in which the box's track has had a box (also with a MATCH_* policy alone)
           tracks [n_clips,T,tcap,8], track_info [n_clips,T,tcap,4], track_counts [n_clips,T]   the confirmed tracks of every frame
         One dt_track_forward (YOLOv2 x T, ConvLSTM recurrence, 1x1), one dt_decode
         over all frames, one dt_associate."""
@@ -242,9 +252,11 @@ class MultiObjDetTracker(object):
         r = ctx.decode(flat, self.OBJ_THRESHOLD, self.NMS_THRESHOLD, self.ANCHORS, len(self.LABELS), cap=cap)
         boxes = r["boxes"].reshape(n, T, cap, mi355_dt.DT_BOX_FLOATS)
         counts = r["counts"].reshape(n, T)
-        if self.MIN_HITS is not None:
+        match = self._match_policy()
+        if self.MIN_HITS is not None or match:
             a = ctx.associate_stream_tracks(boxes, counts, self.ASSOC_THRESHOLD, slots, self.MAX_AGE,
-                                            0.0 if self.MOTION_GAIN is None else self.MOTION_GAIN, self.MIN_HITS)
+                                            0.0 if self.MOTION_GAIN is None else self.MOTION_GAIN, self.MIN_HITS or 1, match=match,
+                                            readout=self.MIN_HITS is not None)
             return dict(a, boxes=boxes, counts=counts, netout=trk)
         if self.MOTION_GAIN is not None:
             ids, nids, gaps = ctx.associate_stream(boxes, counts, self.ASSOC_THRESHOLD, slots, max_age=self.MAX_AGE, want_gaps=True,
@@ -267,9 +279,10 @@ class MultiObjDetTracker(object):
         r = ctx.decode(flat, self.OBJ_THRESHOLD, self.NMS_THRESHOLD, self.ANCHORS, len(self.LABELS), cap=cap)
         boxes = r["boxes"].reshape(n_clips, T, cap, mi355_dt.DT_BOX_FLOATS)
         counts = r["counts"].reshape(n_clips, T)
-        if self.MIN_HITS is not None:
+        match = self._match_policy()
+        if self.MIN_HITS is not None or match:
             a = ctx.associate_tracks(boxes, counts, self.ASSOC_THRESHOLD, self.MAX_AGE, 0.0 if self.MOTION_GAIN is None else self.MOTION_GAIN,
-                                     self.MIN_HITS, track_cap=self.TRACK_CAP)
+                                     self.MIN_HITS or 1, track_cap=self.TRACK_CAP, match=match, readout=self.MIN_HITS is not None)
             return dict(a, boxes=boxes, counts=counts, netout=trk)
         if self.MOTION_GAIN is not None:
             ids, nids, gaps = ctx.associate(boxes, counts, self.ASSOC_THRESHOLD, max_age=self.MAX_AGE, track_cap=self.TRACK_CAP,
@@ -291,6 +304,8 @@ class MultiObjDetTracker(object):
         z = lambda shape, dt: torch.zeros(shape, dtype=dt, device=ctx.device)
         res = dict(boxes=z((0, T, cap, mi355_dt.DT_BOX_FLOATS), torch.float32), counts=z((0, T), torch.int32),
                    ids=z((0, T, cap), torch.int32), nids=z((0,), torch.int32), netout=None)
+        if self.MIN_HITS is None and self._match_policy():
+            res.update(gaps=z((0, T, cap), torch.int32), hits=z((0, T, cap), torch.int32))
         if self.MIN_HITS is not None:
             tcap = cap if self.TRACK_CAP is None else self.TRACK_CAP
             res.update(gaps=z((0, T, cap), torch.int32), hits=z((0, T, cap), torch.int32),
