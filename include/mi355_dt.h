@@ -60,6 +60,7 @@ DT_API int dt_set_stream(dt_ctx *ctx, void *hip_stream);
  * and the two track-motion entries dt_associate_motion, dt_associate_stream_motion
  * and the two track read-out entries dt_associate_tracks, dt_associate_stream_tracks
  * and the two track match policy entries dt_associate_tracks_match, dt_associate_stream_tracks_match
+ * and the one frame-ingest entry dt_ingest_frames
  * -- additions only, the number stayed; 1.07: 1.06 + dt_gemm_split, dt_policy_set) */
 DT_API int dt_abi_version(void);
 
@@ -113,6 +114,44 @@ DT_API int dt_detector_extract(dt_ctx *ctx, const void *d_frames, int frames_dty
  *   d_src [n, src_h, src_w, 3] uint8  ->  d_dst [n, dst_h, dst_w, 3] uint8 */
 DT_API int dt_ingest_resize(dt_ctx *ctx, const uint8_t *d_src, int n, int src_h, int src_w,
                      uint8_t *d_dst, int dst_h, int dst_w);
+
+/* Frames as a video decoder or a cropped view hands them out (addition; BUILD-DEFINED): NV12 or 3-byte interleaved
+ * frames, each with its own size and row pitches, converted and resized to the uint8 network input in one call.
+ * Output frame i = resize(convert(h_desc[i])):
+ *   convert, RGB24: the three bytes of a pixel as they lie.
+ *   convert, NV12:  Y = plane0[r*pitch0 + c], (U, V) = plane1[(r/2)*pitch1 + (c/2)*2 + {0, 1}] -- chroma is NOT interpolated -- and, in
+ *                   int32 with an arithmetic >>:  y = max(Y - 16, 0) * 1220542, u = U - 128, v = V - 128,
+ *                     R = clamp((y + 1673527*v             + 524288) >> 20, 0, 255)
+ *                     G = clamp((y -  852492*v - 409993*u  + 524288) >> 20, 0, 255)
+ *                     B = clamp((y + 2116026*u             + 524288) >> 20, 0, 255)
+ *                   (BT.601 limited range, the fixed-point constants OpenCV publishes for its 8-bit YUV420 conversions; parity with cv2
+ *                   itself is unpinned, as for the resize); output channel order (R, G, B).
+ *   DT_PIX_SWAP_RB: channels 0 and 2 of the converted pixel exchanged, for either format.
+ *   resize:         dt_ingest_resize's scheme on the converted 8-bit values, bit for bit.
+ * h_desc is a HOST array of n descriptors, consumed before the call returns (like h_slots); the call is asynchronous on the context's
+ * stream.  The descriptors travel as kernel arguments, 64 frames per launch: a call makes ceil(n / 64) launches and no device upload,
+ * keeps nothing per size in the context and never waits for the device, whatever sizes it mixes.  (dt_ingest_resize keeps its
+ * per-size table and remains the entry for tight same-size batches.)
+ * DT_ERR_ARG, with the frame index in the message where a descriptor is at fault: a null ctx, h_desc, d_dst or needed plane; n <= 0;
+ * dst_h / dst_w outside dt_ingest_resize's bounds; height or width < 1 or > 16384; NV12 with an odd height or width; a pitch below its
+ * minimum; an unknown format value or flag bit; reserved != 0.  The whole array is validated before anything is launched: an error
+ * leaves d_dst untouched.
+ * Not done here, on purpose: full-range and BT.709 matrices, chroma interpolation, planar I420, 10-bit surfaces, crop rectangles,
+ * letterboxing. */
+#define DT_PIX_RGB24   0   /* 3 interleaved bytes per pixel, taken in the order they lie (what dt_ingest_resize reads) */
+#define DT_PIX_NV12    1   /* plane0 = Y [height][pitch0]; plane1 = U,V interleaved [height/2][pitch1], one pair per 2x2 pixels */
+#define DT_PIX_SWAP_RB 16  /* flag, or-ed in: output channels 0 and 2 exchanged */
+
+typedef struct dt_frame_desc {
+    const void *d_plane0, *d_plane1;   /* device pointers; plane1 ignored (may be NULL) for RGB24 */
+    int32_t height, width;             /* pixels; NV12: both even */
+    int32_t pitch0, pitch1;            /* bytes per row; RGB24: pitch0 >= 3*width; NV12: pitch0 >= width, pitch1 >= width */
+    int32_t format;                    /* DT_PIX_* [| DT_PIX_SWAP_RB] */
+    int32_t reserved;                  /* 0 */
+} dt_frame_desc;
+
+DT_API int dt_ingest_frames(dt_ctx *ctx, const dt_frame_desc *h_desc, int n,
+                            uint8_t *d_dst, int dst_h, int dst_w);
 
 /* ---- decode_netout + NMS (utility/utils.py:208-257) -------------------- */
 /*   d_netout  [batch, GH, GW, NB, 5+NC]  raw logits (NOT modified)

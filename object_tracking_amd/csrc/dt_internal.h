@@ -393,6 +393,9 @@ int launch_rect_from_heatmap(hipStream_t st, const float *heat, int n, int hs, f
 void ingest_tables(int src, int dst, int *tab);
 int launch_ingest_resize(hipStream_t st, const unsigned char *src, int n, int Hs, int Ws, unsigned char *dst, int Hd,
                          int Wd, const int *xt, const int *yt);
+// dt_ingest_frames: frames base .. base + count - 1 of a validated host descriptor array, as ONE launch whose arguments hold the descriptors
+#define INGEST_FRAMES_PER_LAUNCH 64
+int launch_ingest_frames(hipStream_t st, const dt_frame_desc *h_desc, int base, int count, unsigned char *dst, int Hd, int Wd);
 #define DT_MAX_ANCHOR_BOXES 16
 int launch_encode_targets(hipStream_t st, const int *objs, const int *counts, const int *dims, const double *aug,
                           int n, int cap, int GH, int GW, int NB, int C, int IH, int IW, int TBB,

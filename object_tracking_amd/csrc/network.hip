@@ -1649,6 +1649,37 @@ extern "C" int dt_ingest_resize(dt_ctx *ctx, const uint8_t *d_src, int n, int sr
     return DT_OK;
 }
 
+// NV12 / RGB24 frames at per-frame sizes and pitches.  Nothing here depends on an earlier call: no table, no workspace, no key (the
+// coefficients are computed in the kernel), so a call never waits for the device and leaves dt_ingest_resize's cached table alone.
+extern "C" int dt_ingest_frames(dt_ctx *ctx, const dt_frame_desc *h_desc, int n, uint8_t *d_dst, int dst_h, int dst_w)
+{
+    if (!ctx || !h_desc || !d_dst) return dt_fail(ctx, DT_ERR_ARG, "null argument");
+    if (n <= 0 || dst_h <= 0 || dst_w <= 0 || dst_h > 65535) return dt_fail(ctx, DT_ERR_ARG, "bad ingest shape");
+    for (int i = 0; i < n; ++i) {
+        const dt_frame_desc &f = h_desc[i];
+        if (f.reserved != 0) return dt_fail(ctx, DT_ERR_ARG, "frame %d: reserved must be 0", i);
+        if (f.format & ~(DT_PIX_SWAP_RB | DT_PIX_NV12)) return dt_fail(ctx, DT_ERR_ARG, "frame %d: unknown pixel format or flag bits 0x%x", i, (unsigned)f.format);
+        const bool nv12 = (f.format & ~DT_PIX_SWAP_RB) == DT_PIX_NV12;
+        if (f.height < 1 || f.height > 16384 || f.width < 1 || f.width > 16384)
+            return dt_fail(ctx, DT_ERR_ARG, "frame %d: size %dx%d is outside [1, 16384]", i, f.height, f.width);
+        if (!f.d_plane0 || (nv12 && !f.d_plane1)) return dt_fail(ctx, DT_ERR_ARG, "frame %d: null plane", i);
+        if (nv12 && ((f.height | f.width) & 1)) return dt_fail(ctx, DT_ERR_ARG, "frame %d: NV12 needs an even height and width, got %dx%d", i, f.height, f.width);
+        if (f.pitch0 < (nv12 ? f.width : 3 * f.width)) return dt_fail(ctx, DT_ERR_ARG, "frame %d: pitch0 %d is below a row's %d bytes", i, f.pitch0, nv12 ? f.width : 3 * f.width);
+        if (nv12 && f.pitch1 < f.width) return dt_fail(ctx, DT_ERR_ARG, "frame %d: pitch1 %d is below a chroma row's %d bytes", i, f.pitch1, f.width);
+    }
+    for (int base = 0; base < n; base += INGEST_FRAMES_PER_LAUNCH) {
+        const int count = n - base < INGEST_FRAMES_PER_LAUNCH ? n - base : INGEST_FRAMES_PER_LAUNCH;
+        double bytes = 0.0;      // algorithmic: every source byte once (1.5 per NV12 pixel, 3 per RGB24 pixel) + the frames written
+        for (int j = 0; j < count; ++j) {
+            const dt_frame_desc &f = h_desc[base + j];
+            bytes += ((f.format & ~DT_PIX_SWAP_RB) == DT_PIX_NV12 ? 1.5 : 3.0) * f.height * f.width + 3.0 * dst_h * dst_w;
+        }
+        ProfScope ps(ctx, "ingest", 0.0, bytes);
+        if (launch_ingest_frames(ctx->stream, h_desc, base, count, d_dst, dst_h, dst_w)) return dt_fail(ctx, DT_ERR_DEVICE, "ingest launch failed");
+    }
+    return DT_OK;
+}
+
 // ---------------------------------------------------------------------------
 // decode / iou / associate
 // ---------------------------------------------------------------------------

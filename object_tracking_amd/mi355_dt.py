@@ -23,6 +23,9 @@ DT_TRACK_FLOATS = 8      # a track read-out row: x, y, w, h, label, vx, vy, 0
 DT_TRACK_INTS = 4        # ... and its integers: id, age, hits, box
 DT_MATCH_BEST_FIRST = 1  # track match policy bits (dt_associate_tracks_match): candidate pairs taken best IoU first
 DT_MATCH_ANY_LABEL = 2   # ... labels not compared
+DT_PIX_RGB24 = 0         # pixel formats of dt_frame_desc (dt_ingest_frames): 3 interleaved bytes per pixel, as they lie
+DT_PIX_NV12 = 1          # ... plane0 = Y, plane1 = U,V interleaved, one pair per 2x2 pixels
+DT_PIX_SWAP_RB = 16      # ... flag: output channels 0 and 2 exchanged
 
 SYMBOLS = [
     "dt_create", "dt_destroy", "dt_last_error", "dt_set_stream", "dt_abi_version",
@@ -40,6 +43,7 @@ SYMBOLS = [
     "dt_associate_tracks", "dt_associate_stream_tracks",
     "dt_associate_tracks_match", "dt_associate_stream_tracks_match",
     "dt_tiny_stream_open", "dt_tiny_stream_reset", "dt_tiny_stream_sequence", "dt_tiny_stream_forward",
+    "dt_ingest_frames",
 ]
 
 _lib = None
@@ -47,6 +51,14 @@ _lib = None
 
 class NativeError(RuntimeError):
     pass
+
+
+class FrameDesc(ctypes.Structure):
+    """dt_frame_desc (include/mi355_dt.h): one frame of dt_ingest_frames"""
+    _fields_ = [("d_plane0", ctypes.c_void_p), ("d_plane1", ctypes.c_void_p),
+                ("height", ctypes.c_int32), ("width", ctypes.c_int32),
+                ("pitch0", ctypes.c_int32), ("pitch1", ctypes.c_int32),
+                ("format", ctypes.c_int32), ("reserved", ctypes.c_int32)]
 
 
 def load_library():
@@ -73,6 +85,7 @@ def load_library():
     L.dt_detector_tap.argtypes = [vp, ctypes.c_char_p, ci, vp]
     L.dt_detector_extract.argtypes = [vp, vp, ci, ci, ctypes.c_char_p, vp, csz, ctypes.POINTER(ci)]
     L.dt_ingest_resize.argtypes = [vp, vp, ci, ci, ci, vp, ci, ci]
+    L.dt_ingest_frames.argtypes = [vp, ctypes.POINTER(FrameDesc), ci, vp, ci, ci]
     L.dt_decode.argtypes = [vp, vp, ci, ci, ci, ci, ci, cf, cf, vp, ci, vp, vp, vp, vp]
     L.dt_bbox_iou.argtypes = [vp, vp, ci, vp]
     L.dt_decode_per_frame.argtypes = [vp, vp, ci, ci, ci, ci, ci, vp, vp, ci, vp, vp, vp, vp]
@@ -270,6 +283,61 @@ class Context(object):
         self._sync_stream()
         self._check(self.lib.dt_ingest_resize(self.h, _dptr(frames), n, Hs, Ws, _dptr(out), out_h, out_w),
                     "dt_ingest_resize")
+        return out
+
+    def _frame_desc(self, i, item, flags):
+        """item i of ingest_frames -> FrameDesc; the tensors are read as they lie (no copy)"""
+        t = self.torch
+
+        def plane(x, what, dims):
+            if not t.is_tensor(x):
+                raise NativeError("dt_ingest_frames failed (1): frame %d: %s is not a tensor" % (i, what))
+            if not x.is_cuda or x.dtype != t.uint8:
+                raise NativeError("dt_ingest_frames failed (1): frame %d: %s must be a uint8 device tensor, got %s on %s"
+                                  % (i, what, x.dtype, x.device))
+            if x.dim() != dims:
+                raise NativeError("dt_ingest_frames failed (1): frame %d: %s has %d axes, not %d" % (i, what, x.dim(), dims))
+            return x
+
+        def pitch(x, what, inner):
+            """rows at any pitch, the bytes of a row dense: strides (pitch, *inner); the stride of an axis of one element says nothing"""
+            st, row = tuple(x.stride()), int(np.prod(x.shape[1:]))
+            if any(x.shape[1 + k] > 1 and st[1 + k] != v for k, v in enumerate(inner)) or (x.shape[0] > 1 and st[0] < row):
+                raise NativeError("dt_ingest_frames failed (1): frame %d: %s has strides %s; a row must be dense and the rows apart, strides (pitch, %s)"
+                                  % (i, what, st, ", ".join(str(v) for v in inner)))
+            return int(st[0]) if x.shape[0] > 1 else row
+
+        if isinstance(item, (tuple, list)):
+            if len(item) != 2:
+                raise NativeError("dt_ingest_frames failed (1): frame %d: an NV12 item is a pair (y, uv), got %d items" % (i, len(item)))
+            y, uv = plane(item[0], "y", 2), plane(item[1], "uv", 3)
+            H, W = int(y.shape[0]), int(y.shape[1])
+            if tuple(uv.shape) != (H // 2, W // 2, 2) or H % 2 or W % 2:
+                raise NativeError("dt_ingest_frames failed (1): frame %d: y is %dx%d (both must be even) and uv must be [%d, %d, 2], got %s"
+                                  % (i, H, W, H // 2, W // 2, tuple(uv.shape)))
+            return FrameDesc(y.data_ptr(), uv.data_ptr(), H, W, pitch(y, "y", (1,)), pitch(uv, "uv", (2, 1)), DT_PIX_NV12 | flags, 0)
+        x = plane(item, "the frame", 3)
+        if x.shape[2] != 3:
+            raise NativeError("dt_ingest_frames failed (1): frame %d: an RGB24 frame is [H, W, 3], got %s" % (i, tuple(x.shape)))
+        return FrameDesc(x.data_ptr(), None, int(x.shape[0]), int(x.shape[1]), pitch(x, "the frame", (3, 1)), 0, DT_PIX_RGB24 | flags, 0)
+
+    def ingest_frames(self, frames, out_h, out_w, swap_rb=False, out=None):
+        """frames: a sequence whose items are uint8 device tensors [H,W,3] with strides (pitch, 3, 1) (a row-pitched view is taken as it
+        lies) or NV12 pairs (y [H,W] at strides (pitch, 1), uv [H/2,W/2,2] at strides (pitch, 2, 1)), every item at its own size
+        -> uint8 [n,out_h,out_w,3] (dt_ingest_frames: NV12 -> RGB where needed, then dt_ingest_resize's resize).  swap_rb: channels 0 and
+        2 of the result exchanged.  out: a preallocated contiguous [n,out_h,out_w,3] uint8 device tensor to fill instead."""
+        t = self.torch
+        if t.is_tensor(frames) or not isinstance(frames, (list, tuple)):
+            raise NativeError("dt_ingest_frames failed (1): frames must be a list or tuple of frames, got %s" % type(frames).__name__)
+        n = len(frames)
+        flags = DT_PIX_SWAP_RB if swap_rb else 0
+        desc = (FrameDesc * max(1, n))(*[self._frame_desc(i, item, flags) for i, item in enumerate(frames)])
+        if out is None:
+            out = t.empty((n, out_h, out_w, 3), dtype=t.uint8, device=self.device)
+        elif not (t.is_tensor(out) and out.is_cuda and out.dtype == t.uint8 and out.is_contiguous() and tuple(out.shape) == (n, out_h, out_w, 3)):
+            raise NativeError("dt_ingest_frames failed (1): out must be a contiguous uint8 device tensor [%d, %d, %d, 3]" % (n, out_h, out_w))
+        self._sync_stream()
+        self._check(self.lib.dt_ingest_frames(self.h, desc, n, _dptr(out), int(out_h), int(out_w)), "dt_ingest_frames")
         return out
 
     # ---- decode -------------------------------------------------------

@@ -141,6 +141,10 @@ class KerasYOLO(object):
     valid_image_folder = 'data/coco/val2014/'
     valid_annot_folder = 'data/coco/val2014ann/'
 
+    # build-defined (frame ingest): detect() on a LIST of device frames exchanges channels 0 and 2 while ingesting (the
+    # reference's predict feeds BGR, its generators RGB; NV12 converts to R, G, B)
+    INGEST_SWAP_RB = False
+
     model = None
 
     def __init__(self, argv={}, weights=None):
@@ -208,7 +212,12 @@ class KerasYOLO(object):
 
     def detect(self, frames):
         """Batched device path (addition): frames [B,H,W,3] uint8/float32 (numpy or
-        device tensor) -> dict(boxes [B,cap,8], counts [B]) as device tensors."""
+        device tensor) -> dict(boxes [B,cap,8], counts [B]) as device tensors.
+        frames may also be a LIST of B device frames as decoders and crops hand them out -- uint8 [H,W,3] tensors (row-pitched views
+        allowed) and NV12 pairs (y, uv), each at its own size (mi355_dt.Context.ingest_frames): they are converted and resized to
+        IMAGE_H x IMAGE_W on the device first, channels 0 and 2 exchanged with INGEST_SWAP_RB."""
+        if isinstance(frames, (list, tuple)):
+            frames = self.model.ctx.ingest_frames(frames, self.IMAGE_H, self.IMAGE_W, swap_rb=self.INGEST_SWAP_RB)
         netout = self.model.forward(frames)
         return self.model.ctx.decode(netout, self.OBJ_THRESHOLD, self.NMS_THRESHOLD, self.ANCHORS,
                                      len(self.LABELS))

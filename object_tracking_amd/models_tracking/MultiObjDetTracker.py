@@ -144,6 +144,8 @@ class MultiObjDetTracker(object):
     # itself still appears only with MIN_HITS)
     MATCH_BEST_FIRST = False
     MATCH_ANY_LABEL = False
+    # build-defined frame ingest: track_stream on lists of device frames exchanges channels 0 and 2 while ingesting
+    INGEST_SWAP_RB = False
 
     train_image_folder = 'data/MOT17/MOT17Det/train/'
     train_annot_folder = 'data/MOT17Ann/train/'
@@ -242,8 +244,13 @@ class MultiObjDetTracker(object):
         """track_clips for live streams.  frames [n,T,H,W,3]: the next T frames of n streams, stream i living in slot slots[i]
         (distinct numbers below open_streams' n_slots; see models_tracking/streams.py:StreamTable for a key -> slot map).
         Returns the track_clips dict; a stream fed in chunks of any sizes gives what track_clips gives on the concatenation:
-        `ids` continue across calls and `nids` counts the ids a stream has opened since its reset."""
+        `ids` continue across calls and `nids` counts the ids a stream has opened since its reset.
+        frames may also be a LIST of n streams, each a list of its next T device frames as decoders and crops hand them out -- uint8
+        [H,W,3] tensors (row-pitched views allowed) and NV12 pairs (y, uv), every frame at its own size, equal T
+        (mi355_dt.Context.ingest_frames): one ingest call converts and resizes them to IMAGE_H x IMAGE_W on the device."""
         ctx = self.model.ctx
+        if isinstance(frames, (list, tuple)):
+            frames = self._ingest_streams(frames)
         if cap is None:
             cap = getattr(self, "_stream_cap", None) or self.GRID_H * self.GRID_W * self.BOX
         trk = self.model.forward_stream(frames, slots, want_det=False)
@@ -267,6 +274,19 @@ class MultiObjDetTracker(object):
             return dict(boxes=boxes, counts=counts, ids=ids, nids=nids, gaps=gaps, netout=trk)
         ids, nids = ctx.associate_stream(boxes, counts, self.ASSOC_THRESHOLD, slots)
         return dict(boxes=boxes, counts=counts, ids=ids, nids=nids, netout=trk)
+
+    def _ingest_streams(self, streams):
+        """a list (streams) of lists (T frames each) -> uint8 [n, T, IMAGE_H, IMAGE_W, 3] on the device, one dt_ingest_frames call"""
+        n = len(streams)
+        if n == 0 or any(not isinstance(s, (list, tuple)) for s in streams):
+            raise mi355_dt.NativeError("track_stream: frames must be a tensor or a list (streams) of lists (the frames of each)")
+        T = len(streams[0])
+        for i, s in enumerate(streams):
+            if len(s) != T or T == 0:
+                raise mi355_dt.NativeError("track_stream: stream %d has %d frames, stream 0 has %d (equal, and at least one)" % (i, len(s), T))
+        flat = [f for s in streams for f in s]
+        out = self.model.ctx.ingest_frames(flat, self.IMAGE_H, self.IMAGE_W, swap_rb=self.INGEST_SWAP_RB)
+        return out.reshape(n, T, self.IMAGE_H, self.IMAGE_W, 3)
 
     def decode_and_associate(self, trk, cap=None):
         """tracking grid [n_clips,T,G,G,BOX,5+C] (device) -> the track_clips result dict: one dt_decode over all frames

@@ -33,6 +33,32 @@ def resize_bilinear_u8(image, out_h, out_w, ctx=None):
     return ctx.ingest_resize(d, out_h, out_w)[0].cpu().numpy()
 
 
+def nv12_planes(surface, height, width, pitch=None):
+    """One NV12 surface as a video decoder returns it -- a uint8 tensor of at least (height + height/2) * pitch bytes: `height` rows of Y,
+    then height/2 rows of interleaved U,V, every row `pitch` bytes apart (default: width) -- -> the pair (y [height, width],
+    uv [height/2, width/2, 2]) that ingest_frames takes.  Both are VIEWS of the surface: nothing is copied."""
+    pitch = width if pitch is None else int(pitch)
+    if height < 2 or width < 2 or height % 2 or width % 2:
+        raise ValueError("an NV12 surface has an even height and width, got %dx%d" % (height, width))
+    if pitch < width:
+        raise ValueError("pitch %d is below the width %d" % (pitch, width))
+    rows = height + height // 2
+    flat = surface.reshape(-1)
+    if flat.numel() < rows * pitch:
+        raise ValueError("a %dx%d NV12 surface at pitch %d holds %d bytes, got %d" % (height, width, pitch, rows * pitch, flat.numel()))
+    y = flat.as_strided((height, width), (pitch, 1))
+    uv = flat.as_strided((height // 2, width // 2, 2), (pitch, 2, 1), height * pitch)
+    return y, uv
+
+
+def ingest_frames(frames, image_h, image_w, ctx=None, swap_rb=False):
+    """A list of device frames -- uint8 [H,W,3] tensors (row-pitched views allowed) and NV12 pairs (y, uv), each at its own size -- ->
+    uint8 [n, image_h, image_w, 3] on the device, the network input (dt_ingest_frames: one fused launch per 64 frames, no host wait)."""
+    import mi355_dt
+    ctx = ctx if ctx is not None else mi355_dt.default_context()
+    return ctx.ingest_frames(frames, image_h, image_w, swap_rb=swap_rb)
+
+
 def load_frame(path, image_h, image_w, ctx=None):
     """Returns (original BGR image, resized uint8 BGR frame)."""
     image = imread_bgr(path)
