@@ -61,6 +61,7 @@ DT_API int dt_set_stream(dt_ctx *ctx, void *hip_stream);
  * and the two track read-out entries dt_associate_tracks, dt_associate_stream_tracks
  * and the two track match policy entries dt_associate_tracks_match, dt_associate_stream_tracks_match
  * and the one frame-ingest entry dt_ingest_frames
+ * and the four frame-view entries dt_view_fit, dt_view_affine, dt_ingest_views, dt_boxes_map
  * -- additions only, the number stayed; 1.07: 1.06 + dt_gemm_split, dt_policy_set) */
 DT_API int dt_abi_version(void);
 
@@ -136,8 +137,8 @@ DT_API int dt_ingest_resize(dt_ctx *ctx, const uint8_t *d_src, int n, int src_h,
  * dst_h / dst_w outside dt_ingest_resize's bounds; height or width < 1 or > 16384; NV12 with an odd height or width; a pitch below its
  * minimum; an unknown format value or flag bit; reserved != 0.  The whole array is validated before anything is launched: an error
  * leaves d_dst untouched.
- * Not done here, on purpose: full-range and BT.709 matrices, chroma interpolation, planar I420, 10-bit surfaces, crop rectangles,
- * letterboxing. */
+ * Not done here, on purpose: full-range and BT.709 matrices, chroma interpolation, planar I420, 10-bit surfaces.  Crop rectangles and
+ * letterboxing are not this entry's either: they are dt_ingest_views', further down. */
 #define DT_PIX_RGB24   0   /* 3 interleaved bytes per pixel, taken in the order they lie (what dt_ingest_resize reads) */
 #define DT_PIX_NV12    1   /* plane0 = Y [height][pitch0]; plane1 = U,V interleaved [height/2][pitch1], one pair per 2x2 pixels */
 #define DT_PIX_SWAP_RB 16  /* flag, or-ed in: output channels 0 and 2 exchanged */
@@ -152,6 +153,66 @@ typedef struct dt_frame_desc {
 
 DT_API int dt_ingest_frames(dt_ctx *ctx, const dt_frame_desc *h_desc, int n,
                             uint8_t *d_dst, int dst_h, int dst_w);
+
+/* Frame VIEWS (addition; BUILD-DEFINED): a frame of dt_ingest_frames plus a source rectangle (a crop), a destination
+ * rectangle inside the network input (a placement, e.g. a letterbox) and a fill colour around it -- converted, cropped, resized and placed
+ * in one launch -- and the map that takes the decoded boxes back to the SOURCE frame's normalised coordinates.  Integer arithmetic only.
+ *   source rectangle       (src_x, src_y, src_w, src_h) in pixels of the frame: src_w, src_h >= 1, inside the frame.  Any parity is
+ *                          allowed for NV12: chroma is addressed by the ABSOLUTE pixel position, plane1[((src_y+r)/2)*pitch1 +
+ *                          ((src_x+c)/2)*2 + {0, 1}] -- the conversion is pointwise, so cropping commutes with it.
+ *   destination rectangle  (dst_x, dst_y, dst_w, dst_h) in pixels of the output frame [out_h, out_w]: dst_w, dst_h >= 1, inside it.
+ *   fill                   three bytes, written as they are to channels 0, 1, 2 of every output pixel outside the destination rectangle;
+ *                          DT_PIX_SWAP_RB does not touch them.
+ * Inside the destination rectangle, output pixel (dst_y + r, dst_x + c) is pixel (r, c) of dt_ingest_frames' resize of
+ * crop(convert(frame)) from src_h x src_w to dst_h x dst_w: the coefficients are those of (src_w, dst_w, c) and (src_h, dst_h, r),
+ * operation for operation, and the source indices are offset by (src_y, src_x).  A view whose source rectangle is the whole frame and
+ * whose destination rectangle is the whole output is dt_ingest_frames, bit for bit.
+ *
+ * dt_view_fit: the destination rectangle rect = (x, y, w, h) that fits a src_w x src_h source into an out_w x out_h output.  A host
+ * function without a context or a device.
+ *   DT_FIT_STRETCH    (0, 0, out_w, out_h)
+ *   DT_FIT_LETTERBOX  in 64-bit integers with truncating divisions (round half up, centred, the odd pixel below and to the right):
+ *                       if src_w*out_h >= src_h*out_w:  w = out_w, h = max(1, (src_h*out_w + src_w/2) / src_w)
+ *                       otherwise:                      h = out_h, w = max(1, (src_w*out_h + src_h/2) / src_h)
+ *                       x = (out_w - w)/2, y = (out_h - h)/2
+ *                     1920x1080 -> 416x416 gives (0, 91, 416, 234); 1080x1920 gives (91, 0, 234, 416).
+ *   DT_ERR_ARG: a size < 1, an unknown mode, a null rect.
+ *
+ * dt_view_affine: affine = (ax, bx, ay, by), the map from decode's boxes -- normalised to the network input -- to the view's source
+ * frame, normalised to the WHOLE frame (width, height), not to the crop.  A host function without a context or a device.
+ *   ax = (float)((double)(out_w*src_w) / (double)(dst_w*width)),  bx = (float)((double)(src_x*dst_w - dst_x*src_w) / (double)(dst_w*width))
+ *   ay, by likewise with out_h, src_h, dst_h, height, src_y, dst_y.  The integer products are exact in int64; one double division, then
+ *   one rounding to float.  DT_ERR_ARG: a null pointer or one of those sizes < 1.
+ * A box maps as x' = x*ax + bx, y' = y*ay + by, w' = w*ax, h' = h*ay in float32, the product rounded and then the sum rounded (no FMA).
+ * Boxes whose centre lies in the fill are NOT clipped or dropped: they map to coordinates outside the crop (or outside [0, 1]).
+ *
+ * dt_ingest_views keeps dt_ingest_frames' contract: h_views is a HOST array consumed before the call returns; the views travel as
+ * kernel arguments, 32 views per launch (32 x 80 bytes and the other arguments stay within HIP's 4096 bytes of kernel arguments): a
+ * call makes ceil(n / 32) launches, no upload, uses no workspace, never waits for the device and keeps nothing per size.  The whole
+ * array is validated before the first launch -- everything dt_ingest_frames checks on the embedded descriptor, both rectangles as
+ * defined above, both reserved fields 0 -- and an error (DT_ERR_ARG) names the frame and leaves d_dst untouched.
+ *
+ * dt_boxes_map applies per-frame affines in place to floats 0..3 of rows < min(d_counts[i], cap) of frame i of d_boxes
+ * [n][cap][DT_BOX_FLOATS]; every other float and every other row keeps its bits.  h_affine is a HOST array [n][4], consumed before the
+ * call returns; the affines travel as kernel arguments, 128 frames per launch.  DT_ERR_ARG: a null pointer, n <= 0, cap <= 0, a
+ * non-finite affine (nothing is launched then). */
+#define DT_FIT_STRETCH   0
+#define DT_FIT_LETTERBOX 1
+
+typedef struct dt_frame_view {
+    dt_frame_desc frame;                     /* as for dt_ingest_frames, reserved == 0 */
+    int32_t src_x, src_y, src_w, src_h;      /* the crop, pixels of the frame */
+    int32_t dst_x, dst_y, dst_w, dst_h;      /* the placement, pixels of the output frame */
+    uint8_t fill[3]; uint8_t reserved0;      /* channels 0, 1, 2 outside the placement; 0 */
+    int32_t reserved;                        /* 0 */
+} dt_frame_view;                             /* 80 bytes */
+
+DT_API int dt_view_fit(int src_w, int src_h, int out_w, int out_h, int mode, int32_t rect[4]);
+DT_API int dt_view_affine(const dt_frame_view *v, int out_w, int out_h, float affine[4]);
+DT_API int dt_ingest_views(dt_ctx *ctx, const dt_frame_view *h_views, int n,
+                           uint8_t *d_dst, int out_h, int out_w);
+DT_API int dt_boxes_map(dt_ctx *ctx, float *d_boxes, const int *d_counts, int n, int cap,
+                        const float *h_affine);
 
 /* ---- decode_netout + NMS (utility/utils.py:208-257) -------------------- */
 /*   d_netout  [batch, GH, GW, NB, 5+NC]  raw logits (NOT modified)

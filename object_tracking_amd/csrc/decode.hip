@@ -2031,3 +2031,38 @@ int launch_top_box(hipStream_t st, const float *boxes, const int *counts, int n_
     hipLaunchKernelGGL(top_box_kernel, dim3((unsigned)n_frames), dim3(64), 0, st, boxes, counts, cap, out4);
     return hipGetLastError() == hipSuccess ? 0 : 1;
 }
+
+// ---------------------------------------------------------------------------
+// dt_boxes_map: decode's boxes, normalised to the network input, taken to a view's source frame
+// ---------------------------------------------------------------------------
+// One thread per (frame, row).  x' = x*ax + bx, y' = y*ay + by, w' = w*ax, h' = h*ay: the product is rounded, then the sum -- this
+// file is built without FMA contraction.  The affines of a launch travel as kernel arguments; blockIdx.y picks the frame, so they are
+// the same in every lane of a wave.  Rows from min(count, cap) on, and floats 4..7 of every row, are neither read nor written.
+struct BoxesMapChunk { float a[BOXES_MAP_FRAMES_PER_LAUNCH][4]; };
+static_assert(sizeof(BoxesMapChunk) + 2 * sizeof(void *) + sizeof(int) <= 4096, "a launch's affines and its other arguments fit HIP's 4096 bytes of kernel arguments");
+
+__global__ __launch_bounds__(256) void boxes_map_kernel(BoxesMapChunk c, float *boxes, const int *counts, int cap)
+{
+    const int row = blockIdx.x * blockDim.x + threadIdx.x;
+    const int f = blockIdx.y;
+    if (row >= min(counts[f], cap)) return;
+    const float ax = c.a[f][0], bx = c.a[f][1], ay = c.a[f][2], by = c.a[f][3];
+    float *b = boxes + ((long long)f * cap + row) * DT_BOX_FLOATS;
+    const float x = b[0], y = b[1], w = b[2], h = b[3];
+    b[0] = x * ax + bx;
+    b[1] = y * ay + by;
+    b[2] = w * ax;
+    b[3] = h * ay;
+}
+
+int launch_boxes_map(hipStream_t st, float *boxes, const int *counts, int base, int count, int cap, const float *h_affine)
+{
+    if (count <= 0) return 0;
+    if (count > BOXES_MAP_FRAMES_PER_LAUNCH || cap <= 0) return 2;
+    BoxesMapChunk c;
+    for (int j = 0; j < BOXES_MAP_FRAMES_PER_LAUNCH; ++j)
+        for (int k = 0; k < 4; ++k) c.a[j][k] = h_affine[(size_t)(base + (j < count ? j : 0)) * 4 + k];
+    dim3 grid((unsigned)((cap + 255) / 256), (unsigned)count);
+    hipLaunchKernelGGL(boxes_map_kernel, grid, dim3(256), 0, st, c, boxes + (size_t)base * cap * DT_BOX_FLOATS, counts + base, cap);
+    return hipGetLastError() == hipSuccess ? 0 : 1;
+}

@@ -396,6 +396,12 @@ int launch_ingest_resize(hipStream_t st, const unsigned char *src, int n, int Hs
 // dt_ingest_frames: frames base .. base + count - 1 of a validated host descriptor array, as ONE launch whose arguments hold the descriptors
 #define INGEST_FRAMES_PER_LAUNCH 64
 int launch_ingest_frames(hipStream_t st, const dt_frame_desc *h_desc, int base, int count, unsigned char *dst, int Hd, int Wd);
+// dt_ingest_views: views base .. base + count - 1 of a validated host array, as ONE launch whose arguments hold the views
+#define INGEST_VIEWS_PER_LAUNCH 32
+int launch_ingest_views(hipStream_t st, const dt_frame_view *h_views, int base, int count, unsigned char *dst, int Hd, int Wd);
+// dt_boxes_map: frames base .. base + count - 1 of a validated host affine array [n][4], as ONE launch whose arguments hold the affines
+#define BOXES_MAP_FRAMES_PER_LAUNCH 128
+int launch_boxes_map(hipStream_t st, float *boxes, const int *counts, int base, int count, int cap, const float *h_affine);
 #define DT_MAX_ANCHOR_BOXES 16
 int launch_encode_targets(hipStream_t st, const int *objs, const int *counts, const int *dims, const double *aug,
                           int n, int cap, int GH, int GW, int NB, int C, int IH, int IW, int TBB,

@@ -146,6 +146,95 @@ int launch_ingest_frames(hipStream_t st, const dt_frame_desc *h_desc, int base, 
     return hipGetLastError() == hipSuccess ? 0 : 1;
 }
 
+// ---------------------------------------------------------------------------
+// dt_ingest_views: a crop of each frame, resized into a rectangle of the output, a fill colour around it; one launch per 32 views
+// ---------------------------------------------------------------------------
+// ingest_frames_kernel with a source rectangle and a destination rectangle.  What that kernel learned is kept: only
+// ADDRESSES are selected, every load is issued before the first wait, no load sits under a lane-divergent condition.  A lane outside
+// the destination rectangle clamps its column into it -- it loads what the nearest column inside loads -- and selects the fill at the
+// store.  blockIdx.y and the view are the same in every lane, so an output row that lies wholly in the fill leaves through a
+// wave-uniform branch before any coefficient or load.
+struct IngestViewChunk { dt_frame_view v[INGEST_VIEWS_PER_LAUNCH]; };
+static_assert(sizeof(dt_frame_view) == 80, "dt_frame_view is 80 bytes");
+static_assert(sizeof(IngestViewChunk) + sizeof(unsigned char *) + 2 * sizeof(int) <= 4096, "a launch's views and its other arguments fit HIP's 4096 bytes of kernel arguments");
+
+__global__ __launch_bounds__(256) void ingest_views_kernel(IngestViewChunk c, unsigned char *dst, int Hd, int Wd)
+{
+    const int x = blockIdx.x * blockDim.x + threadIdx.x;
+    const int y = blockIdx.y;
+    if (x >= Wd) return;
+    const dt_frame_view &v = c.v[blockIdx.z];
+    unsigned char *o = dst + (((long long)blockIdx.z * Hd + y) * Wd + x) * 3;
+    // the fill's three bytes and reserved0 (0) as one word of the arguments, read once for both ways out
+    const unsigned fw = (unsigned)v.fill[0] | (unsigned)v.fill[1] << 8 | (unsigned)v.fill[2] << 16;
+    const int f0 = fw & 255, f1 = (fw >> 8) & 255, f2 = fw >> 16;
+    const int ry = y - v.dst_y;
+    if (ry < 0 || ry >= v.dst_h) {                         // (the same in every lane) a row of fill: nothing is read
+        o[0] = (unsigned char)f0;
+        o[1] = (unsigned char)f1;
+        o[2] = (unsigned char)f2;
+        return;
+    }
+    const dt_frame_desc &d = v.frame;
+    const bool nv12 = (d.format & ~DT_PIX_SWAP_RB) == DT_PIX_NV12, swap = (d.format & DT_PIX_SWAP_RB) != 0;
+    const int rx = x - v.dst_x;
+    const bool inside = rx >= 0 && rx < v.dst_w;
+    int xs[2], ys[2], a[2], b[2];
+    ingest_coef(v.src_w, v.dst_w, min(max(rx, 0), v.dst_w - 1), xs[0], xs[1], a[0], a[1]);
+    ingest_coef(v.src_h, v.dst_h, ry, ys[0], ys[1], b[0], b[1]);      // (the same in every lane)
+    // from here on the indices are those of the frame: chroma is addressed by the absolute position, so a crop may start at an odd pixel
+    xs[0] += v.src_x; xs[1] += v.src_x;
+    ys[0] += v.src_y; ys[1] += v.src_y;
+    const unsigned char *p0 = static_cast<const unsigned char *>(d.d_plane0);
+    const unsigned char *pc = nv12 ? static_cast<const unsigned char *>(d.d_plane1) : p0 + 1;
+    const long long pitch_c = nv12 ? d.pitch1 : d.pitch0;
+    const int sh = nv12 ? 1 : 0;
+    const int m0 = nv12 ? 1 : 3, mc = nv12 ? 2 : 3;
+    int px[2][2][3];      // [row][column][channel]
+#pragma unroll
+    for (int r = 0; r < 2; ++r) {
+        const unsigned char *row0 = p0 + (long long)ys[r] * d.pitch0;
+        const unsigned char *rowc = pc + (long long)(ys[r] >> sh) * pitch_c;
+#pragma unroll
+        for (int k = 0; k < 2; ++k) {
+            const int o0 = xs[k] * m0, oc = (xs[k] >> sh) * mc;
+            px[r][k][0] = row0[o0];
+            px[r][k][1] = rowc[oc];
+            px[r][k][2] = rowc[oc + 1];
+        }
+    }
+    if (nv12) {
+#pragma unroll
+        for (int r = 0; r < 2; ++r)
+#pragma unroll
+            for (int k = 0; k < 2; ++k) nv12_to_rgb(px[r][k][0], px[r][k][1], px[r][k][2]);
+    }
+    int out[3];
+#pragma unroll
+    for (int ch = 0; ch < 3; ++ch) {
+        const int S0 = px[0][0][ch] * a[0] + px[0][1][ch] * a[1];
+        const int S1 = px[1][0][ch] * a[0] + px[1][1][ch] * a[1];
+        const int t = (((b[0] * (S0 >> 4)) >> 16) + ((b[1] * (S1 >> 4)) >> 16) + 2) >> 2;
+        out[ch] = min(max(t, 0), 255);
+    }
+    // the fill is written as it is: the channel exchange is the frame's, not the fill's
+    o[0] = (unsigned char)(inside ? (swap ? out[2] : out[0]) : f0);
+    o[1] = (unsigned char)(inside ? out[1] : f1);
+    o[2] = (unsigned char)(inside ? (swap ? out[0] : out[2]) : f2);
+}
+
+// h_views: a validated host array; frame i of dst [n][Hd][Wd][3] comes from h_views[i]
+int launch_ingest_views(hipStream_t st, const dt_frame_view *h_views, int base, int count, unsigned char *dst, int Hd, int Wd)
+{
+    if (count <= 0) return 0;
+    if (count > INGEST_VIEWS_PER_LAUNCH || Hd <= 0 || Hd > 65535 || Wd <= 0) return 2;
+    IngestViewChunk c;
+    for (int j = 0; j < INGEST_VIEWS_PER_LAUNCH; ++j) c.v[j] = h_views[base + (j < count ? j : 0)];
+    dim3 grid((unsigned)((Wd + 255) / 256), (unsigned)Hd, (unsigned)count);
+    hipLaunchKernelGGL(ingest_views_kernel, grid, dim3(256), 0, st, c, dst + (size_t)base * Hd * Wd * 3, Hd, Wd);
+    return hipGetLastError() == hipSuccess ? 0 : 1;
+}
+
 // same formula as oracle.c:orc_resize_tables
 void ingest_tables(int src, int dst, int *tab /*[4][dst]*/)
 {

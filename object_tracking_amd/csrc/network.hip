@@ -1649,24 +1649,29 @@ extern "C" int dt_ingest_resize(dt_ctx *ctx, const uint8_t *d_src, int n, int sr
     return DT_OK;
 }
 
+// one descriptor of dt_ingest_frames / dt_ingest_views, frame i of the call: DT_OK, or DT_ERR_ARG with the frame named in the message
+static int check_frame_desc(dt_ctx *ctx, const dt_frame_desc &f, int i)
+{
+    if (f.reserved != 0) return dt_fail(ctx, DT_ERR_ARG, "frame %d: reserved must be 0", i);
+    if (f.format & ~(DT_PIX_SWAP_RB | DT_PIX_NV12)) return dt_fail(ctx, DT_ERR_ARG, "frame %d: unknown pixel format or flag bits 0x%x", i, (unsigned)f.format);
+    const bool nv12 = (f.format & ~DT_PIX_SWAP_RB) == DT_PIX_NV12;
+    if (f.height < 1 || f.height > 16384 || f.width < 1 || f.width > 16384)
+        return dt_fail(ctx, DT_ERR_ARG, "frame %d: size %dx%d is outside [1, 16384]", i, f.height, f.width);
+    if (!f.d_plane0 || (nv12 && !f.d_plane1)) return dt_fail(ctx, DT_ERR_ARG, "frame %d: null plane", i);
+    if (nv12 && ((f.height | f.width) & 1)) return dt_fail(ctx, DT_ERR_ARG, "frame %d: NV12 needs an even height and width, got %dx%d", i, f.height, f.width);
+    if (f.pitch0 < (nv12 ? f.width : 3 * f.width)) return dt_fail(ctx, DT_ERR_ARG, "frame %d: pitch0 %d is below a row's %d bytes", i, f.pitch0, nv12 ? f.width : 3 * f.width);
+    if (nv12 && f.pitch1 < f.width) return dt_fail(ctx, DT_ERR_ARG, "frame %d: pitch1 %d is below a chroma row's %d bytes", i, f.pitch1, f.width);
+    return DT_OK;
+}
+
 // NV12 / RGB24 frames at per-frame sizes and pitches.  Nothing here depends on an earlier call: no table, no workspace, no key (the
 // coefficients are computed in the kernel), so a call never waits for the device and leaves dt_ingest_resize's cached table alone.
 extern "C" int dt_ingest_frames(dt_ctx *ctx, const dt_frame_desc *h_desc, int n, uint8_t *d_dst, int dst_h, int dst_w)
 {
     if (!ctx || !h_desc || !d_dst) return dt_fail(ctx, DT_ERR_ARG, "null argument");
     if (n <= 0 || dst_h <= 0 || dst_w <= 0 || dst_h > 65535) return dt_fail(ctx, DT_ERR_ARG, "bad ingest shape");
-    for (int i = 0; i < n; ++i) {
-        const dt_frame_desc &f = h_desc[i];
-        if (f.reserved != 0) return dt_fail(ctx, DT_ERR_ARG, "frame %d: reserved must be 0", i);
-        if (f.format & ~(DT_PIX_SWAP_RB | DT_PIX_NV12)) return dt_fail(ctx, DT_ERR_ARG, "frame %d: unknown pixel format or flag bits 0x%x", i, (unsigned)f.format);
-        const bool nv12 = (f.format & ~DT_PIX_SWAP_RB) == DT_PIX_NV12;
-        if (f.height < 1 || f.height > 16384 || f.width < 1 || f.width > 16384)
-            return dt_fail(ctx, DT_ERR_ARG, "frame %d: size %dx%d is outside [1, 16384]", i, f.height, f.width);
-        if (!f.d_plane0 || (nv12 && !f.d_plane1)) return dt_fail(ctx, DT_ERR_ARG, "frame %d: null plane", i);
-        if (nv12 && ((f.height | f.width) & 1)) return dt_fail(ctx, DT_ERR_ARG, "frame %d: NV12 needs an even height and width, got %dx%d", i, f.height, f.width);
-        if (f.pitch0 < (nv12 ? f.width : 3 * f.width)) return dt_fail(ctx, DT_ERR_ARG, "frame %d: pitch0 %d is below a row's %d bytes", i, f.pitch0, nv12 ? f.width : 3 * f.width);
-        if (nv12 && f.pitch1 < f.width) return dt_fail(ctx, DT_ERR_ARG, "frame %d: pitch1 %d is below a chroma row's %d bytes", i, f.pitch1, f.width);
-    }
+    for (int i = 0; i < n; ++i)
+        if (int rc = check_frame_desc(ctx, h_desc[i], i)) return rc;
     for (int base = 0; base < n; base += INGEST_FRAMES_PER_LAUNCH) {
         const int count = n - base < INGEST_FRAMES_PER_LAUNCH ? n - base : INGEST_FRAMES_PER_LAUNCH;
         double bytes = 0.0;      // algorithmic: every source byte once (1.5 per NV12 pixel, 3 per RGB24 pixel) + the frames written
@@ -1676,6 +1681,87 @@ extern "C" int dt_ingest_frames(dt_ctx *ctx, const dt_frame_desc *h_desc, int n,
         }
         ProfScope ps(ctx, "ingest", 0.0, bytes);
         if (launch_ingest_frames(ctx->stream, h_desc, base, count, d_dst, dst_h, dst_w)) return dt_fail(ctx, DT_ERR_DEVICE, "ingest launch failed");
+    }
+    return DT_OK;
+}
+
+// ---- frame views ----
+// The two host functions need neither a context nor a device: integer arithmetic in int64, for the affine one double division each.
+extern "C" int dt_view_fit(int src_w, int src_h, int out_w, int out_h, int mode, int32_t rect[4])
+{
+    if (!rect || src_w < 1 || src_h < 1 || out_w < 1 || out_h < 1) return DT_ERR_ARG;
+    if (mode == DT_FIT_STRETCH) {
+        rect[0] = 0; rect[1] = 0; rect[2] = out_w; rect[3] = out_h;
+        return DT_OK;
+    }
+    if (mode != DT_FIT_LETTERBOX) return DT_ERR_ARG;
+    const long long sw = src_w, sh = src_h, ow = out_w, oh = out_h;
+    long long w, h;
+    if (sw * oh >= sh * ow) {
+        w = ow;
+        h = (sh * ow + sw / 2) / sw;
+        if (h < 1) h = 1;
+    } else {
+        h = oh;
+        w = (sw * oh + sh / 2) / sh;
+        if (w < 1) w = 1;
+    }
+    rect[0] = (int32_t)((ow - w) / 2); rect[1] = (int32_t)((oh - h) / 2); rect[2] = (int32_t)w; rect[3] = (int32_t)h;
+    return DT_OK;
+}
+
+extern "C" int dt_view_affine(const dt_frame_view *v, int out_w, int out_h, float affine[4])
+{
+    if (!v || !affine || out_w < 1 || out_h < 1 || v->dst_w < 1 || v->dst_h < 1 || v->frame.width < 1 || v->frame.height < 1) return DT_ERR_ARG;
+    const long long dw = v->dst_w, dh = v->dst_h, fw = v->frame.width, fh = v->frame.height;
+    affine[0] = (float)((double)((long long)out_w * v->src_w) / (double)(dw * fw));
+    affine[1] = (float)((double)((long long)v->src_x * dw - (long long)v->dst_x * v->src_w) / (double)(dw * fw));
+    affine[2] = (float)((double)((long long)out_h * v->src_h) / (double)(dh * fh));
+    affine[3] = (float)((double)((long long)v->src_y * dh - (long long)v->dst_y * v->src_h) / (double)(dh * fh));
+    return DT_OK;
+}
+
+// dt_ingest_frames with a crop, a placement and a fill per frame.  As there: no table, no workspace, no key, no wait.
+extern "C" int dt_ingest_views(dt_ctx *ctx, const dt_frame_view *h_views, int n, uint8_t *d_dst, int out_h, int out_w)
+{
+    if (!ctx || !h_views || !d_dst) return dt_fail(ctx, DT_ERR_ARG, "null argument");
+    if (n <= 0 || out_h <= 0 || out_w <= 0 || out_h > 65535) return dt_fail(ctx, DT_ERR_ARG, "bad ingest shape");
+    for (int i = 0; i < n; ++i) {
+        const dt_frame_view &v = h_views[i];
+        if (int rc = check_frame_desc(ctx, v.frame, i)) return rc;
+        if (v.reserved != 0 || v.reserved0 != 0) return dt_fail(ctx, DT_ERR_ARG, "frame %d: the view's reserved fields must be 0", i);
+        // (written as subtractions: x + w could wrap an int32)
+        if (v.src_w < 1 || v.src_h < 1 || v.src_x < 0 || v.src_y < 0 || v.src_x > v.frame.width - v.src_w || v.src_y > v.frame.height - v.src_h)
+            return dt_fail(ctx, DT_ERR_ARG, "frame %d: source rectangle (%d, %d, %d, %d) is empty or not inside the %dx%d frame", i, v.src_x, v.src_y,
+                           v.src_w, v.src_h, v.frame.width, v.frame.height);
+        if (v.dst_w < 1 || v.dst_h < 1 || v.dst_x < 0 || v.dst_y < 0 || v.dst_w > out_w || v.dst_h > out_h || v.dst_x > out_w - v.dst_w || v.dst_y > out_h - v.dst_h)
+            return dt_fail(ctx, DT_ERR_ARG, "frame %d: destination rectangle (%d, %d, %d, %d) is empty or not inside the %dx%d output", i, v.dst_x,
+                           v.dst_y, v.dst_w, v.dst_h, out_w, out_h);
+    }
+    for (int base = 0; base < n; base += INGEST_VIEWS_PER_LAUNCH) {
+        const int count = n - base < INGEST_VIEWS_PER_LAUNCH ? n - base : INGEST_VIEWS_PER_LAUNCH;
+        double bytes = 0.0;      // algorithmic: every byte of the source rectangles once (1.5 per NV12 pixel, 3 per RGB24 pixel) + the frames written
+        for (int j = 0; j < count; ++j) {
+            const dt_frame_view &v = h_views[base + j];
+            bytes += ((v.frame.format & ~DT_PIX_SWAP_RB) == DT_PIX_NV12 ? 1.5 : 3.0) * v.src_h * v.src_w + 3.0 * out_h * out_w;
+        }
+        ProfScope ps(ctx, "ingest", 0.0, bytes);
+        if (launch_ingest_views(ctx->stream, h_views, base, count, d_dst, out_h, out_w)) return dt_fail(ctx, DT_ERR_DEVICE, "ingest launch failed");
+    }
+    return DT_OK;
+}
+
+extern "C" int dt_boxes_map(dt_ctx *ctx, float *d_boxes, const int *d_counts, int n, int cap, const float *h_affine)
+{
+    if (!ctx || !d_boxes || !d_counts || !h_affine) return dt_fail(ctx, DT_ERR_ARG, "null argument");
+    if (n <= 0 || cap <= 0) return dt_fail(ctx, DT_ERR_ARG, "bad boxes_map shape");
+    for (int i = 0; i < n; ++i)
+        for (int k = 0; k < 4; ++k)
+            if (!std::isfinite(h_affine[(size_t)i * 4 + k])) return dt_fail(ctx, DT_ERR_ARG, "frame %d: affine element %d is not finite", i, k);
+    for (int base = 0; base < n; base += BOXES_MAP_FRAMES_PER_LAUNCH) {
+        const int count = n - base < BOXES_MAP_FRAMES_PER_LAUNCH ? n - base : BOXES_MAP_FRAMES_PER_LAUNCH;
+        ProfScope ps(ctx, "boxes_map", 0.0, 32.0 * count * cap);
+        if (launch_boxes_map(ctx->stream, d_boxes, d_counts, base, count, cap, h_affine)) return dt_fail(ctx, DT_ERR_DEVICE, "boxes_map launch failed");
     }
     return DT_OK;
 }

@@ -26,6 +26,9 @@ DT_MATCH_ANY_LABEL = 2   # ... labels not compared
 DT_PIX_RGB24 = 0         # pixel formats of dt_frame_desc (dt_ingest_frames): 3 interleaved bytes per pixel, as they lie
 DT_PIX_NV12 = 1          # ... plane0 = Y, plane1 = U,V interleaved, one pair per 2x2 pixels
 DT_PIX_SWAP_RB = 16      # ... flag: output channels 0 and 2 exchanged
+DT_FIT_STRETCH = 0       # fit modes of dt_view_fit: the whole output
+DT_FIT_LETTERBOX = 1     # ... the largest centred rectangle of the source's aspect ratio
+FIT_MODES = {"stretch": DT_FIT_STRETCH, "letterbox": DT_FIT_LETTERBOX}
 
 SYMBOLS = [
     "dt_create", "dt_destroy", "dt_last_error", "dt_set_stream", "dt_abi_version",
@@ -44,6 +47,7 @@ SYMBOLS = [
     "dt_associate_tracks_match", "dt_associate_stream_tracks_match",
     "dt_tiny_stream_open", "dt_tiny_stream_reset", "dt_tiny_stream_sequence", "dt_tiny_stream_forward",
     "dt_ingest_frames",
+    "dt_view_fit", "dt_view_affine", "dt_ingest_views", "dt_boxes_map",
 ]
 
 _lib = None
@@ -59,6 +63,14 @@ class FrameDesc(ctypes.Structure):
                 ("height", ctypes.c_int32), ("width", ctypes.c_int32),
                 ("pitch0", ctypes.c_int32), ("pitch1", ctypes.c_int32),
                 ("format", ctypes.c_int32), ("reserved", ctypes.c_int32)]
+
+
+class FrameView(ctypes.Structure):
+    """dt_frame_view (include/mi355_dt.h): one view of dt_ingest_views -- a frame, a source and a destination rectangle, a fill"""
+    _fields_ = [("frame", FrameDesc),
+                ("src_x", ctypes.c_int32), ("src_y", ctypes.c_int32), ("src_w", ctypes.c_int32), ("src_h", ctypes.c_int32),
+                ("dst_x", ctypes.c_int32), ("dst_y", ctypes.c_int32), ("dst_w", ctypes.c_int32), ("dst_h", ctypes.c_int32),
+                ("fill", ctypes.c_uint8 * 3), ("reserved0", ctypes.c_uint8), ("reserved", ctypes.c_int32)]
 
 
 def load_library():
@@ -86,6 +98,10 @@ def load_library():
     L.dt_detector_extract.argtypes = [vp, vp, ci, ci, ctypes.c_char_p, vp, csz, ctypes.POINTER(ci)]
     L.dt_ingest_resize.argtypes = [vp, vp, ci, ci, ci, vp, ci, ci]
     L.dt_ingest_frames.argtypes = [vp, ctypes.POINTER(FrameDesc), ci, vp, ci, ci]
+    L.dt_view_fit.argtypes = [ci, ci, ci, ci, ci, ctypes.POINTER(ctypes.c_int32)]
+    L.dt_view_affine.argtypes = [ctypes.POINTER(FrameView), ci, ci, ctypes.POINTER(cf)]
+    L.dt_ingest_views.argtypes = [vp, ctypes.POINTER(FrameView), ci, vp, ci, ci]
+    L.dt_boxes_map.argtypes = [vp, vp, vp, ci, ci, vp]
     L.dt_decode.argtypes = [vp, vp, ci, ci, ci, ci, ci, cf, cf, vp, ci, vp, vp, vp, vp]
     L.dt_bbox_iou.argtypes = [vp, vp, ci, vp]
     L.dt_decode_per_frame.argtypes = [vp, vp, ci, ci, ci, ci, ci, vp, vp, ci, vp, vp, vp, vp]
@@ -147,6 +163,26 @@ def load_library():
     L.dt_packed_row_ints.restype = ctypes.c_size_t
     _lib = L
     return L
+
+
+def view_fit(src_w, src_h, out_w, out_h, mode="letterbox"):
+    """dt_view_fit: the destination rectangle (x, y, w, h) of a src_w x src_h source in an out_w x out_h output; mode "letterbox" /
+    "stretch" (or DT_FIT_*).  A host function: no context, no device."""
+    rect = (ctypes.c_int32 * 4)()
+    m = FIT_MODES.get(mode, mode)
+    if not isinstance(m, int) or load_library().dt_view_fit(int(src_w), int(src_h), int(out_w), int(out_h), m, rect) != 0:
+        raise NativeError("dt_view_fit failed (1): sizes %dx%d -> %dx%d must be >= 1 and the mode \"letterbox\" or \"stretch\", got %r"
+                          % (src_w, src_h, out_w, out_h, mode))
+    return tuple(int(v) for v in rect)
+
+
+def view_affine(view, out_w, out_h):
+    """dt_view_affine: (ax, bx, ay, by) of a mi355_dt.FrameView as a float32 numpy array [4] -- x' = x*ax + bx, y' = y*ay + by,
+    w' = w*ax, h' = h*ay take a box normalised to the out_h x out_w network input to the view's whole source frame."""
+    a = (ctypes.c_float * 4)()
+    if load_library().dt_view_affine(ctypes.byref(view), int(out_w), int(out_h), a) != 0:
+        raise NativeError("dt_view_affine failed (1): the output, the destination rectangle and the frame must be at least 1x1")
+    return np.array(a[:], dtype=np.float32)
 
 
 def _hptr(a):
@@ -285,40 +321,41 @@ class Context(object):
                     "dt_ingest_resize")
         return out
 
-    def _frame_desc(self, i, item, flags):
-        """item i of ingest_frames -> FrameDesc; the tensors are read as they lie (no copy)"""
+    def _frame_desc(self, i, item, flags, entry="dt_ingest_frames"):
+        """item i of ingest_frames / ingest_views -> FrameDesc; the tensors are read as they lie (no copy)"""
         t = self.torch
+        head = "%s failed (1): frame %d: " % (entry, i)
 
         def plane(x, what, dims):
             if not t.is_tensor(x):
-                raise NativeError("dt_ingest_frames failed (1): frame %d: %s is not a tensor" % (i, what))
+                raise NativeError(head + "%s is not a tensor" % what)
             if not x.is_cuda or x.dtype != t.uint8:
-                raise NativeError("dt_ingest_frames failed (1): frame %d: %s must be a uint8 device tensor, got %s on %s"
-                                  % (i, what, x.dtype, x.device))
+                raise NativeError(head + "%s must be a uint8 device tensor, got %s on %s"
+                                  % (what, x.dtype, x.device))
             if x.dim() != dims:
-                raise NativeError("dt_ingest_frames failed (1): frame %d: %s has %d axes, not %d" % (i, what, x.dim(), dims))
+                raise NativeError(head + "%s has %d axes, not %d" % (what, x.dim(), dims))
             return x
 
         def pitch(x, what, inner):
             """rows at any pitch, the bytes of a row dense: strides (pitch, *inner); the stride of an axis of one element says nothing"""
             st, row = tuple(x.stride()), int(np.prod(x.shape[1:]))
             if any(x.shape[1 + k] > 1 and st[1 + k] != v for k, v in enumerate(inner)) or (x.shape[0] > 1 and st[0] < row):
-                raise NativeError("dt_ingest_frames failed (1): frame %d: %s has strides %s; a row must be dense and the rows apart, strides (pitch, %s)"
-                                  % (i, what, st, ", ".join(str(v) for v in inner)))
+                raise NativeError(head + "%s has strides %s; a row must be dense and the rows apart, strides (pitch, %s)"
+                                  % (what, st, ", ".join(str(v) for v in inner)))
             return int(st[0]) if x.shape[0] > 1 else row
 
         if isinstance(item, (tuple, list)):
             if len(item) != 2:
-                raise NativeError("dt_ingest_frames failed (1): frame %d: an NV12 item is a pair (y, uv), got %d items" % (i, len(item)))
+                raise NativeError(head + "an NV12 item is a pair (y, uv), got %d items" % len(item))
             y, uv = plane(item[0], "y", 2), plane(item[1], "uv", 3)
             H, W = int(y.shape[0]), int(y.shape[1])
             if tuple(uv.shape) != (H // 2, W // 2, 2) or H % 2 or W % 2:
-                raise NativeError("dt_ingest_frames failed (1): frame %d: y is %dx%d (both must be even) and uv must be [%d, %d, 2], got %s"
-                                  % (i, H, W, H // 2, W // 2, tuple(uv.shape)))
+                raise NativeError(head + "y is %dx%d (both must be even) and uv must be [%d, %d, 2], got %s"
+                                  % (H, W, H // 2, W // 2, tuple(uv.shape)))
             return FrameDesc(y.data_ptr(), uv.data_ptr(), H, W, pitch(y, "y", (1,)), pitch(uv, "uv", (2, 1)), DT_PIX_NV12 | flags, 0)
         x = plane(item, "the frame", 3)
         if x.shape[2] != 3:
-            raise NativeError("dt_ingest_frames failed (1): frame %d: an RGB24 frame is [H, W, 3], got %s" % (i, tuple(x.shape)))
+            raise NativeError(head + "an RGB24 frame is [H, W, 3], got %s" % (tuple(x.shape),))
         return FrameDesc(x.data_ptr(), None, int(x.shape[0]), int(x.shape[1]), pitch(x, "the frame", (3, 1)), 0, DT_PIX_RGB24 | flags, 0)
 
     def ingest_frames(self, frames, out_h, out_w, swap_rb=False, out=None):
@@ -339,6 +376,85 @@ class Context(object):
         self._sync_stream()
         self._check(self.lib.dt_ingest_frames(self.h, desc, n, _dptr(out), int(out_h), int(out_w)), "dt_ingest_frames")
         return out
+
+    def _frame_view(self, i, item, flags, out_h, out_w, fit, fill):
+        """item i of ingest_views -> FrameView.  An item with a `.frame` attribute is a view description (utility.frames.FrameView:
+        frame, crop, fit, fill, dst); anything else is a frame of ingest_frames, taken whole with the call's fit and fill."""
+        head = "dt_ingest_views failed (1): frame %d: " % i
+        crop = dst = None
+        if hasattr(item, "frame"):
+            crop, dst = getattr(item, "crop", None), getattr(item, "dst", None)
+            fit = getattr(item, "fit", None) or fit
+            fill = getattr(item, "fill", None) or fill
+            item = item.frame
+
+        def rect(r, what):
+            try:
+                r = tuple(r)
+                ok = len(r) == 4 and all(int(v) == v and -2 ** 31 <= v < 2 ** 31 for v in r)
+            except (TypeError, ValueError):
+                ok = False
+            if not ok:
+                raise NativeError(head + "%s must be four integers (x, y, w, h), got %r" % (what, r))
+            return tuple(int(v) for v in r)
+
+        d = self._frame_desc(i, item, flags, entry="dt_ingest_views")
+        sx, sy, sw, sh = (0, 0, d.width, d.height) if crop is None else rect(crop, "crop")
+        if dst is not None:
+            dx, dy, dw, dh = rect(dst, "dst")
+        else:
+            if fit not in FIT_MODES:
+                raise NativeError(head + "fit must be \"letterbox\" or \"stretch\", got %r" % (fit,))
+            if sw < 1 or sh < 1:
+                raise NativeError(head + "crop (%d, %d, %d, %d) is empty" % (sx, sy, sw, sh))
+            dx, dy, dw, dh = view_fit(sw, sh, out_w, out_h, fit)
+        try:
+            fill = tuple(fill)
+            ok = len(fill) == 3 and all(int(v) == v and 0 <= v <= 255 for v in fill)
+        except (TypeError, ValueError):
+            ok = False
+        if not ok:
+            raise NativeError(head + "fill must be three bytes, got %r" % (fill,))
+        return FrameView(d, sx, sy, sw, sh, dx, dy, dw, dh, (ctypes.c_uint8 * 3)(*[int(v) for v in fill]), 0, 0)
+
+    def ingest_views(self, views, out_h, out_w, swap_rb=False, out=None, fit="letterbox", fill=(128, 128, 128)):
+        """views: a sequence whose items are view descriptions (utility.frames.FrameView: a frame, a crop, a fit or an explicit
+        destination rectangle, a fill) or plain frames of ingest_frames, which are taken whole with this call's `fit` and `fill`
+        -> (frames uint8 [n,out_h,out_w,3], affine float32 numpy [n,4]) (dt_ingest_views: every crop converted, resized into its
+        destination rectangle, the fill around it; dt_view_affine: the (ax, bx, ay, by) that boxes_map takes).  swap_rb and out as for
+        ingest_frames; the fill is written as it is, whatever swap_rb says."""
+        t = self.torch
+        if t.is_tensor(views) or not isinstance(views, (list, tuple)):
+            raise NativeError("dt_ingest_views failed (1): views must be a list or tuple of views, got %s" % type(views).__name__)
+        n = len(views)
+        flags = DT_PIX_SWAP_RB if swap_rb else 0
+        arr = (FrameView * max(1, n))(*[self._frame_view(i, item, flags, int(out_h), int(out_w), fit, fill) for i, item in enumerate(views)])
+        if out is None:
+            out = t.empty((n, out_h, out_w, 3), dtype=t.uint8, device=self.device)
+        elif not (t.is_tensor(out) and out.is_cuda and out.dtype == t.uint8 and out.is_contiguous() and tuple(out.shape) == (n, out_h, out_w, 3)):
+            raise NativeError("dt_ingest_views failed (1): out must be a contiguous uint8 device tensor [%d, %d, %d, 3]" % (n, out_h, out_w))
+        self._sync_stream()
+        self._check(self.lib.dt_ingest_views(self.h, arr, n, _dptr(out), int(out_h), int(out_w)), "dt_ingest_views")
+        affine = np.empty((n, 4), dtype=np.float32)
+        for i in range(n):
+            affine[i] = view_affine(arr[i], out_w, out_h)
+        return out, affine
+
+    def boxes_map(self, boxes, counts, affine):
+        """boxes [..., cap, 8] device float32, counts int32 of the leading shape, affine float32 [frames, 4] on the host (ingest_views'):
+        x, y, w, h of rows < min(count, cap) of every frame mapped IN PLACE (dt_boxes_map); [R, T, cap, 8] counts as R*T frames.
+        Returns boxes."""
+        t = self.torch
+        assert boxes.is_cuda and boxes.dtype == t.float32 and boxes.is_contiguous() and boxes.dim() >= 2 and boxes.shape[-1] == DT_BOX_FLOATS
+        assert counts.is_cuda and counts.dtype == t.int32 and counts.is_contiguous()
+        cap = int(boxes.shape[-2])
+        n = boxes.numel() // max(1, cap * DT_BOX_FLOATS)
+        a = np.ascontiguousarray(affine, dtype=np.float32).reshape(-1, 4)
+        if counts.numel() != n or a.shape[0] != n:
+            raise NativeError("dt_boxes_map failed (1): %d frames of boxes, %d counts, %d affines" % (n, counts.numel(), a.shape[0]))
+        self._sync_stream()
+        self._check(self.lib.dt_boxes_map(self.h, _dptr(boxes), _dptr(counts), n, cap, a.ctypes.data_as(ctypes.c_void_p)), "dt_boxes_map")
+        return boxes
 
     # ---- decode -------------------------------------------------------
     def decode(self, netout, obj_threshold, nms_threshold, anchors, nb_class, cap=None,

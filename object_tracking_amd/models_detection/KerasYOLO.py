@@ -144,6 +144,11 @@ class KerasYOLO(object):
     # build-defined (frame ingest): detect() on a LIST of device frames exchanges channels 0 and 2 while ingesting (the
     # reference's predict feeds BGR, its generators RGB; NV12 converts to R, G, B)
     INGEST_SWAP_RB = False
+    # build-defined (frame views): None = a list given to detect() is stretched to IMAGE_H x IMAGE_W (dt_ingest_frames);
+    # "letterbox" / "stretch" = the list goes through dt_ingest_views -- its items may be utility.frames.FrameView too, a plain frame is
+    # fitted whole by this rule -- and the returned boxes are mapped to the SOURCE frames' normalised coordinates, the result carrying
+    # `affine` [B, 4].  predict(path, ...) keeps the reference's stretch.
+    INGEST_FIT = None
 
     model = None
 
@@ -215,12 +220,21 @@ class KerasYOLO(object):
         device tensor) -> dict(boxes [B,cap,8], counts [B]) as device tensors.
         frames may also be a LIST of B device frames as decoders and crops hand them out -- uint8 [H,W,3] tensors (row-pitched views
         allowed) and NV12 pairs (y, uv), each at its own size (mi355_dt.Context.ingest_frames): they are converted and resized to
-        IMAGE_H x IMAGE_W on the device first, channels 0 and 2 exchanged with INGEST_SWAP_RB."""
+        IMAGE_H x IMAGE_W on the device first, channels 0 and 2 exchanged with INGEST_SWAP_RB.
+        With INGEST_FIT ("letterbox" / "stretch") the items may also be utility.frames.FrameView descriptions (a crop, a fit or a placement,
+        a fill); the boxes come back in the source frames' normalised coordinates and the dict carries `affine` (numpy [B, 4])."""
+        ctx, affine = self.model.ctx, None
         if isinstance(frames, (list, tuple)):
-            frames = self.model.ctx.ingest_frames(frames, self.IMAGE_H, self.IMAGE_W, swap_rb=self.INGEST_SWAP_RB)
+            if self.INGEST_FIT is None:
+                frames = ctx.ingest_frames(frames, self.IMAGE_H, self.IMAGE_W, swap_rb=self.INGEST_SWAP_RB)
+            else:
+                frames, affine = ctx.ingest_views(frames, self.IMAGE_H, self.IMAGE_W, swap_rb=self.INGEST_SWAP_RB, fit=self.INGEST_FIT)
         netout = self.model.forward(frames)
-        return self.model.ctx.decode(netout, self.OBJ_THRESHOLD, self.NMS_THRESHOLD, self.ANCHORS,
-                                     len(self.LABELS))
+        r = ctx.decode(netout, self.OBJ_THRESHOLD, self.NMS_THRESHOLD, self.ANCHORS, len(self.LABELS))
+        if affine is not None:
+            ctx.boxes_map(r["boxes"], r["counts"], affine)
+            r["affine"] = affine
+        return r
 
     def predict(self, input_path, output_path):
         """KerasYOLO.py:522-537; additionally returns the box list."""

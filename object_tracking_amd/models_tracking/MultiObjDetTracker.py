@@ -146,6 +146,11 @@ class MultiObjDetTracker(object):
     MATCH_ANY_LABEL = False
     # build-defined frame ingest: track_stream on lists of device frames exchanges channels 0 and 2 while ingesting
     INGEST_SWAP_RB = False
+    # build-defined frame views: None = lists of frames are stretched (dt_ingest_frames).  "letterbox" / "stretch" = they
+    # go through dt_ingest_views (items may be utility.frames.FrameView; a plain frame is fitted whole by this rule) and the decoded boxes
+    # are mapped to the source frames' normalised coordinates BEFORE association: ids, the track table, velocities and the read-out rows
+    # live in source space, and the result carries `affine` [n, T, 4]
+    INGEST_FIT = None
 
     train_image_folder = 'data/MOT17/MOT17Det/train/'
     train_annot_folder = 'data/MOT17Ann/train/'
@@ -248,9 +253,9 @@ class MultiObjDetTracker(object):
         frames may also be a LIST of n streams, each a list of its next T device frames as decoders and crops hand them out -- uint8
         [H,W,3] tensors (row-pitched views allowed) and NV12 pairs (y, uv), every frame at its own size, equal T
         (mi355_dt.Context.ingest_frames): one ingest call converts and resizes them to IMAGE_H x IMAGE_W on the device."""
-        ctx = self.model.ctx
+        ctx, affine = self.model.ctx, None
         if isinstance(frames, (list, tuple)):
-            frames = self._ingest_streams(frames)
+            frames, affine = self._ingest_streams(frames)
         if cap is None:
             cap = getattr(self, "_stream_cap", None) or self.GRID_H * self.GRID_W * self.BOX
         trk = self.model.forward_stream(frames, slots, want_det=False)
@@ -259,24 +264,35 @@ class MultiObjDetTracker(object):
         r = ctx.decode(flat, self.OBJ_THRESHOLD, self.NMS_THRESHOLD, self.ANCHORS, len(self.LABELS), cap=cap)
         boxes = r["boxes"].reshape(n, T, cap, mi355_dt.DT_BOX_FLOATS)
         counts = r["counts"].reshape(n, T)
+        if affine is not None:
+            # to source coordinates before anything is matched; without views nothing is mapped (an identity map is not free of effect:
+            # -0.0 * 1 + 0 is +0.0)
+            ctx.boxes_map(boxes, counts, affine)
+            return dict(self._associate_stream(boxes, counts, slots), netout=trk, affine=affine.reshape(n, T, 4))
+        return dict(self._associate_stream(boxes, counts, slots), netout=trk)
+
+    def _associate_stream(self, boxes, counts, slots):
+        """the association entry the class attributes select, on a call's boxes: the result dict without `netout`"""
+        ctx = self.model.ctx
         match = self._match_policy()
         if self.MIN_HITS is not None or match:
             a = ctx.associate_stream_tracks(boxes, counts, self.ASSOC_THRESHOLD, slots, self.MAX_AGE,
                                             0.0 if self.MOTION_GAIN is None else self.MOTION_GAIN, self.MIN_HITS or 1, match=match,
                                             readout=self.MIN_HITS is not None)
-            return dict(a, boxes=boxes, counts=counts, netout=trk)
+            return dict(a, boxes=boxes, counts=counts)
         if self.MOTION_GAIN is not None:
             ids, nids, gaps = ctx.associate_stream(boxes, counts, self.ASSOC_THRESHOLD, slots, max_age=self.MAX_AGE, want_gaps=True,
                                                    motion_gain=self.MOTION_GAIN)
-            return dict(boxes=boxes, counts=counts, ids=ids, nids=nids, gaps=gaps, netout=trk)
+            return dict(boxes=boxes, counts=counts, ids=ids, nids=nids, gaps=gaps)
         if self.MAX_AGE > 0:
             ids, nids, gaps = ctx.associate_stream(boxes, counts, self.ASSOC_THRESHOLD, slots, max_age=self.MAX_AGE, want_gaps=True)
-            return dict(boxes=boxes, counts=counts, ids=ids, nids=nids, gaps=gaps, netout=trk)
+            return dict(boxes=boxes, counts=counts, ids=ids, nids=nids, gaps=gaps)
         ids, nids = ctx.associate_stream(boxes, counts, self.ASSOC_THRESHOLD, slots)
-        return dict(boxes=boxes, counts=counts, ids=ids, nids=nids, netout=trk)
+        return dict(boxes=boxes, counts=counts, ids=ids, nids=nids)
 
     def _ingest_streams(self, streams):
-        """a list (streams) of lists (T frames each) -> uint8 [n, T, IMAGE_H, IMAGE_W, 3] on the device, one dt_ingest_frames call"""
+        """a list (streams) of lists (T frames each) -> (uint8 [n, T, IMAGE_H, IMAGE_W, 3] on the device, affine): one dt_ingest_frames call
+        and None, or with INGEST_FIT one dt_ingest_views call and the box map [n * T, 4] of its views"""
         n = len(streams)
         if n == 0 or any(not isinstance(s, (list, tuple)) for s in streams):
             raise mi355_dt.NativeError("track_stream: frames must be a tensor or a list (streams) of lists (the frames of each)")
@@ -285,8 +301,11 @@ class MultiObjDetTracker(object):
             if len(s) != T or T == 0:
                 raise mi355_dt.NativeError("track_stream: stream %d has %d frames, stream 0 has %d (equal, and at least one)" % (i, len(s), T))
         flat = [f for s in streams for f in s]
-        out = self.model.ctx.ingest_frames(flat, self.IMAGE_H, self.IMAGE_W, swap_rb=self.INGEST_SWAP_RB)
-        return out.reshape(n, T, self.IMAGE_H, self.IMAGE_W, 3)
+        if self.INGEST_FIT is None:
+            out, affine = self.model.ctx.ingest_frames(flat, self.IMAGE_H, self.IMAGE_W, swap_rb=self.INGEST_SWAP_RB), None
+        else:
+            out, affine = self.model.ctx.ingest_views(flat, self.IMAGE_H, self.IMAGE_W, swap_rb=self.INGEST_SWAP_RB, fit=self.INGEST_FIT)
+        return out.reshape(n, T, self.IMAGE_H, self.IMAGE_W, 3), affine
 
     def decode_and_associate(self, trk, cap=None):
         """tracking grid [n_clips,T,G,G,BOX,5+C] (device) -> the track_clips result dict: one dt_decode over all frames

@@ -59,6 +59,30 @@ def ingest_frames(frames, image_h, image_w, ctx=None, swap_rb=False):
     return ctx.ingest_frames(frames, image_h, image_w, swap_rb=swap_rb)
 
 
+class FrameView(object):
+    """A host-side description of one VIEW of a frame (dt_ingest_views): which part of the frame goes where in the
+    network input, and what surrounds it.
+      frame  what ingest_frames takes as an item: a uint8 [H,W,3] device tensor (row-pitched views allowed) or an NV12 pair (y, uv)
+      crop   (x, y, w, h) in pixels of the frame, any parity; None: the whole frame
+      fit    "letterbox" (the largest centred rectangle of the crop's aspect ratio, mi355_dt.view_fit) or "stretch" (the whole input)
+      fill   three bytes for channels 0, 1, 2 of the pixels around the destination rectangle (written as they are, swap_rb or not)
+      dst    (x, y, w, h) in pixels of the network input: an explicit destination rectangle, instead of the fit"""
+    __slots__ = ("frame", "crop", "fit", "fill", "dst")
+
+    def __init__(self, frame, crop=None, fit="letterbox", fill=(128, 128, 128), dst=None):
+        self.frame, self.crop, self.fit, self.fill, self.dst = frame, crop, fit, fill, dst
+
+
+def ingest_views(views, image_h, image_w, ctx=None, swap_rb=False, fit="letterbox", fill=(128, 128, 128)):
+    """A list of FrameViews -- and plain frames of ingest_frames, taken whole with `fit` and `fill` -- -> (uint8 [n, image_h, image_w, 3]
+    on the device, affine float32 numpy [n, 4]): every crop converted, resized into its destination rectangle and surrounded by its fill
+    in one fused launch per 32 views (dt_ingest_views); Context.boxes_map(boxes, counts, affine) takes the decoded boxes back to the
+    source frames' normalised coordinates.  Boxes that lie in the fill are neither clipped nor dropped."""
+    import mi355_dt
+    ctx = ctx if ctx is not None else mi355_dt.default_context()
+    return ctx.ingest_views(views, image_h, image_w, swap_rb=swap_rb, fit=fit, fill=fill)
+
+
 def load_frame(path, image_h, image_w, ctx=None):
     """Returns (original BGR image, resized uint8 BGR frame)."""
     image = imread_bgr(path)
