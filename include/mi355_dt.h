@@ -47,6 +47,12 @@ extern "C" {
 #define DT_MATCH_BEST_FIRST 1   /* ... bit: the candidate pairs are taken best IoU first */
 #define DT_MATCH_ANY_LABEL 2    /* ... bit: labels are not compared */
 
+#define DT_SCORE_INTS 8       /* track scoring totals of a clip (dt_track_score): frames, gt boxes, hyp boxes, matches, switches, fragments, overflow, 0 */
+#define DT_SCORE_OBJ_INTS 8   /* ... a row of its object table: gt id, last track id (-1: never matched), present, matched, switches, fragments,
+                               *     last appearance matched (0/1), 0 */
+#define DT_SCORE_ANY_LABEL 1  /* ... flag bit: labels are not compared */
+#define DT_SCORE_RESUME 2     /* ... flag bit: d_totals, d_objs, d_nobjs are in-out and the call continues from them */
+
 typedef struct dt_ctx dt_ctx;
 
 /* ---- context ---------------------------------------------------------- */
@@ -62,6 +68,7 @@ DT_API int dt_set_stream(dt_ctx *ctx, void *hip_stream);
  * and the two track match policy entries dt_associate_tracks_match, dt_associate_stream_tracks_match
  * and the one frame-ingest entry dt_ingest_frames
  * and the four frame-view entries dt_view_fit, dt_view_affine, dt_ingest_views, dt_boxes_map
+ * and the one track scoring entry dt_track_score
  * -- additions only, the number stayed; 1.07: 1.06 + dt_gemm_split, dt_policy_set) */
 DT_API int dt_abi_version(void);
 
@@ -347,6 +354,52 @@ DT_API int dt_associate_tracks(dt_ctx *ctx, const float *d_boxes, const int *d_c
 DT_API int dt_associate_tracks_match(dt_ctx *ctx, const float *d_boxes, const int *d_counts,
                  int n_clips, int T, int cap, float assoc_threshold, int max_age, int tcap, float gain, int min_hits, int match,
                  int *d_ids, int *d_nids, int *d_gaps, int *d_hits, float *d_tracks, int *d_tinfo, int *d_tcounts);
+
+/* Track scoring (BUILD-DEFINED, DESIGN.md "Track scoring"): the CLEAR-MOT frame step (Bernardin & Stiefelhagen 2008) of a tracker's output
+ * against ground-truth tracks, with the optimal assignment replaced by this library's best-IoU-first order.  Clips are scored
+ * independently, one wavefront each, frames in sequence.
+ *   d_gt_boxes  [n_clips, T, gcap, DT_BOX_FLOATS]  floats 0..3 = x, y, w, h as dt_decode normalises them, float 5 = label, the rest ignored
+ *   d_gt_counts [n_clips, T] int32, d_gt_ids [n_clips, T, gcap] int32      rows g < min(count, gcap) take part
+ *   d_hyp_boxes [n_clips, T, hcap, 8]   x, y, w, h in floats 0..3, the label in float hyp_label_at: 5 for dt_decode's boxes, 4 for read-out
+ *               rows (DT_TRACK_FLOATS); d_hyp_counts [n_clips, T]; rows i < min(count, hcap) take part
+ *   d_hyp_ids   the id of row i of frame t is word (t * hcap + i) * id_stride of the clip: id_stride = 1 with d_ids of dt_associate*,
+ *               id_stride = DT_TRACK_INTS with d_tinfo -- so the confirmed-track read-out is scored by the same entry, its coasting rows
+ *               as ordinary hypotheses
+ * The OBJECT TABLE of a clip has at most ocap rows of DT_SCORE_OBJ_INTS int32, one per distinct ground-truth id in order of first appearance.
+ * The step of a frame (every read of the table sees it as the previous frame left it; it is written behind the match):
+ *   valid pair (g, i): bbox_iou(gt box g, hyp box i) >= iou_threshold as float32 (dt_bbox_iou's bits), and equal labels as floats unless
+ *       DT_SCORE_ANY_LABEL is set;
+ *   carry-over: g ascending; if g's id has a row with last track id tau >= 0, the lowest unclaimed i whose id is tau is looked up, and if
+ *       (g, i) is valid g is matched to i (a correspondence is kept while it is valid, even where a closer hypothesis exists);
+ *   the rest: among the unmatched g and unclaimed i the valid pair of the largest IoU is taken repeatedly, compared as float32, ties to the
+ *       lowest g, then the lowest i (the order of DT_MATCH_BEST_FIRST);
+ *   counts: matches; switches = matched g whose row had tau >= 0 and tau != the matched hypothesis' id; fragments = matched g whose row
+ *       had matched > 0 and last appearance matched == 0;
+ *   update, in g order: an id without a row gets one appended; when the table is full the box has no memory (no carry-over, never a
+ *       switch or fragment, nothing recorded) and overflow is incremented per such box; an id < 0 has no memory either and is not counted
+ *       as overflow.  Otherwise present += 1; matched: matched += 1, switches / fragments as counted, last track id = the hypothesis' id,
+ *       last appearance matched = 1; unmatched: last appearance matched = 0 and the last track id is kept.  An id that occurs twice or more in
+ *       a frame is updated as this walk in g order leaves it: the counters add, its highest g decides last appearance matched, and the
+ *       last track id is that of its highest MATCHED g (an unmatched row keeps the id, also one a lower row of the frame has just set).
+ *   d_totals  [n_clips, DT_SCORE_INTS] int32      frames, gt boxes, hyp boxes, matches, switches, fragments, overflow, 0
+ *             (misses = gt - matches, false positives = hyp - matches)
+ *   d_objs    [n_clips, ocap, DT_SCORE_OBJ_INTS] int32, d_nobjs [n_clips] int32 the rows in use
+ *   d_fcounts [n_clips, T, 4] int32               gt, hyp, matches, switches of every frame; may be NULL
+ *   d_match   [n_clips, T, gcap] int32            the hypothesis row matched to g, -1 for unmatched and unused rows
+ *   d_miou    [n_clips, T, gcap] float32          the IoU of that match, 0 elsewhere; d_match and d_miou: both, or both NULL
+ * Without DT_SCORE_RESUME d_totals, d_objs, d_nobjs may arrive uninitialised and every word of them is written: the rows of d_objs from
+ * d_nobjs on are zero with -1 in the gt id and last track id fields.  With it the three are in-out and the call continues from them:
+ * chunks of any sizes along T give every output of the one call on the concatenation, bit for bit -- the contract of the stream entries,
+ * with the state owned by the caller (no slot table).  Asynchronous on the context's stream; n_clips = 0 is a no-op.
+ * Not done here: an optimal (Hungarian) assignment, IDF1 / HOTA, ignore regions and visibility weighting, dropping coasting rows,
+ * detector mAP.
+ * DT_ERR_ARG (nothing launched): a NULL required pointer, n_clips < 0, T, gcap, hcap or ocap <= 0, id_stride < 1, hyp_label_at outside
+ * 0..7, unknown flag bits, one of d_match / d_miou without the other, a threshold that is NaN or outside (0, 1], or a table and frame
+ * that do not fit the 160 KB of LDS: 8 * ocap + 11 * gcap + 7 * hcap words must not exceed 40960 (gcap = hcap = 128: ocap up to 4832). */
+DT_API int dt_track_score(dt_ctx *ctx, const float *d_gt_boxes, const int *d_gt_counts, const int *d_gt_ids, int gcap,
+                 const float *d_hyp_boxes, const int *d_hyp_counts, const int *d_hyp_ids, int hcap, int id_stride, int hyp_label_at,
+                 int n_clips, int T, float iou_threshold, int flags, int ocap,
+                 int *d_totals, int *d_objs, int *d_nobjs, int *d_fcounts, int *d_match, float *d_miou);
 
 /* ---- streaming: ConvLSTM state and track ids carried across calls (addition; the reference's predict() sees one window) ---- *
  * A live stream delivers a frame, or a few, at a time.  The context holds a table of STREAM SLOTS in device memory; per slot the ConvLSTM

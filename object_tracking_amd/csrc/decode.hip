@@ -26,34 +26,7 @@
 
 __device__ __forceinline__ float sigmoid_ref(float x) { return 1.0f / (1.0f + expf(-x)); }
 
-// utils.py:175-188
-__device__ __forceinline__ float interval_overlap_ref(float x1, float x2, float x3, float x4)
-{
-    if (x3 < x1) {
-        if (x4 < x1) return 0.0f;
-        return fminf(x2, x4) - x1;
-    } else {
-        if (x2 < x3) return 0.0f;
-        return fminf(x2, x4) - x3;
-    }
-}
-
-// utils.py:155-173 (centre-format boxes)
-__device__ __forceinline__ float bbox_iou_ref(float ax, float ay, float aw, float ah, float bx, float by, float bw,
-                                              float bh)
-{
-    const float x1_min = ax - aw / 2, x1_max = ax + aw / 2;
-    const float y1_min = ay - ah / 2, y1_max = ay + ah / 2;
-    const float x2_min = bx - bw / 2, x2_max = bx + bw / 2;
-    const float y2_min = by - bh / 2, y2_max = by + bh / 2;
-    const float iw = interval_overlap_ref(x1_min, x1_max, x2_min, x2_max);
-    const float ih = interval_overlap_ref(y1_min, y1_max, y2_min, y2_max);
-    const float inter = iw * ih;
-    const float a1 = aw * ah;
-    const float a2 = bw * bh;
-    const float uni = (a1 + a2) - inter;
-    return inter / uni;
-}
+// interval_overlap_ref / bbox_iou_ref (utils.py:175-188, :155-173) and wave_umax_dpp: dt_internal.h, shared with score.hip
 
 __device__ __forceinline__ float wave_max(float v)
 {
@@ -66,19 +39,6 @@ __device__ __forceinline__ float wave_min(float v)
 #pragma unroll
     for (int o = 32; o > 0; o >>= 1) v = fminf(v, __shfl_xor(v, o));
     return v;
-}
-
-// maximum of an unsigned value over the 64 lanes (wave-uniform result): four DPP row shifts leave each row's maximum in
-// its last lane (lanes shifted in from outside a row read 0), four lane reads and scalar max finish
-__device__ __forceinline__ unsigned wave_umax_dpp(unsigned v)
-{
-    v = max(v, (unsigned)__builtin_amdgcn_update_dpp(0, (int)v, 0x111, 0xf, 0xf, false));   // row_shr:1
-    v = max(v, (unsigned)__builtin_amdgcn_update_dpp(0, (int)v, 0x112, 0xf, 0xf, false));   // row_shr:2
-    v = max(v, (unsigned)__builtin_amdgcn_update_dpp(0, (int)v, 0x114, 0xf, 0xf, false));   // row_shr:4
-    v = max(v, (unsigned)__builtin_amdgcn_update_dpp(0, (int)v, 0x118, 0xf, 0xf, false));   // row_shr:8
-    const unsigned a = (unsigned)__builtin_amdgcn_readlane((int)v, 15), b = (unsigned)__builtin_amdgcn_readlane((int)v, 31);
-    const unsigned c = (unsigned)__builtin_amdgcn_readlane((int)v, 47), d = (unsigned)__builtin_amdgcn_readlane((int)v, 63);
-    return max(max(a, b), max(c, d));
 }
 
 __device__ __forceinline__ float readlane_f(float v, int l) { return __int_as_float(__builtin_amdgcn_readlane(__float_as_int(v), l)); }

@@ -361,6 +361,75 @@ int launch_associate_tracks(hipStream_t st, const float *boxes, const int *count
                             int max_age, int tcap, float gain, int min_hits, int match, int *ids, int *nids, int *gaps /*may be null*/,
                             const TrackReadout &out, const AssocCarry &carry);
 
+// The reference's box IoU, shared by decode.hip (NMS, association) and score.hip (track scoring): one definition, and both files are
+// compiled with -ffp-contract=off -- numpy's float32 arithmetic rounds after every multiply and add, so no FMA may be formed here;
+// the pragma in each body says so for any other file that comes to use them.
+// utils.py:175-188
+__device__ __forceinline__ float interval_overlap_ref(float x1, float x2, float x3, float x4)
+{
+#pragma clang fp contract(off)
+    if (x3 < x1) {
+        if (x4 < x1) return 0.0f;
+        return fminf(x2, x4) - x1;
+    } else {
+        if (x2 < x3) return 0.0f;
+        return fminf(x2, x4) - x3;
+    }
+}
+
+// utils.py:155-173 (centre-format boxes)
+__device__ __forceinline__ float bbox_iou_ref(float ax, float ay, float aw, float ah, float bx, float by, float bw,
+                                              float bh)
+{
+#pragma clang fp contract(off)
+    const float x1_min = ax - aw / 2, x1_max = ax + aw / 2;
+    const float y1_min = ay - ah / 2, y1_max = ay + ah / 2;
+    const float x2_min = bx - bw / 2, x2_max = bx + bw / 2;
+    const float y2_min = by - bh / 2, y2_max = by + bh / 2;
+    const float iw = interval_overlap_ref(x1_min, x1_max, x2_min, x2_max);
+    const float ih = interval_overlap_ref(y1_min, y1_max, y2_min, y2_max);
+    const float inter = iw * ih;
+    const float a1 = aw * ah;
+    const float a2 = bw * bh;
+    const float uni = (a1 + a2) - inter;
+    return inter / uni;
+}
+
+// maximum of an unsigned value over the 64 lanes (wave-uniform result): four DPP row shifts leave each row's maximum in
+// its last lane (lanes shifted in from outside a row read 0), four lane reads and scalar max finish
+__device__ __forceinline__ unsigned wave_umax_dpp(unsigned v)
+{
+    v = max(v, (unsigned)__builtin_amdgcn_update_dpp(0, (int)v, 0x111, 0xf, 0xf, false));   // row_shr:1
+    v = max(v, (unsigned)__builtin_amdgcn_update_dpp(0, (int)v, 0x112, 0xf, 0xf, false));   // row_shr:2
+    v = max(v, (unsigned)__builtin_amdgcn_update_dpp(0, (int)v, 0x114, 0xf, 0xf, false));   // row_shr:4
+    v = max(v, (unsigned)__builtin_amdgcn_update_dpp(0, (int)v, 0x118, 0xf, 0xf, false));   // row_shr:8
+    const unsigned a = (unsigned)__builtin_amdgcn_readlane((int)v, 15), b = (unsigned)__builtin_amdgcn_readlane((int)v, 31);
+    const unsigned c = (unsigned)__builtin_amdgcn_readlane((int)v, 47), d = (unsigned)__builtin_amdgcn_readlane((int)v, 63);
+    return max(max(a, b), max(c, d));
+}
+
+// track scoring (score.hip:track_score_kernel): CLEAR-MOT counts of hypotheses against ground-truth tracks, one wavefront per clip.
+// The object table, the frame's ground-truth rows and its hypotheses live in LDS: 8 * ocap + 11 * gcap + 7 * hcap words.
+struct ScoreArgs {
+    const float *gt_boxes;   // [n][T][gcap][DT_BOX_FLOATS]
+    const int *gt_counts;    // [n][T]
+    const int *gt_ids;       // [n][T][gcap]
+    const float *hyp_boxes;  // [n][T][hcap][8]
+    const int *hyp_counts;   // [n][T]
+    const int *hyp_ids;      // [n][T][hcap][id_stride], the id in word 0
+    int gcap, hcap, id_stride, label_at, T, ocap;
+    float thr;
+    int *totals;             // [n][DT_SCORE_INTS]
+    int *objs;               // [n][ocap][DT_SCORE_OBJ_INTS]
+    int *nobjs;              // [n]
+    int *fcounts;            // [n][T][4] or null
+    int *match;              // [n][T][gcap] or null
+    float *miou;             // [n][T][gcap], null exactly when match is
+};
+size_t track_score_lds_bytes(int gcap, int hcap, int ocap);      // dynamic LDS the launch needs; dt_track_score refuses more than 160 KB
+// 0: launched; 1: device error.  flags: DT_SCORE_* bits.  The arguments are dt_track_score's, validated there (n_clips > 0, the LDS fits).
+int launch_track_score(hipStream_t st, const ScoreArgs &a, int n_clips, int flags);
+
 // ---------------------------------------------------------------------------
 // stream slots: state that outlives a call (stream_state.hip)
 // ---------------------------------------------------------------------------

@@ -1901,6 +1901,31 @@ extern "C" int dt_associate_tracks(dt_ctx *ctx, const float *d_boxes, const int 
                                      d_gaps, d_hits, d_tracks, d_tinfo, d_tcounts);
 }
 
+// track scoring (DESIGN.md "Track scoring"): CLEAR-MOT counts of hypotheses against ground-truth tracks; the caller owns the state
+extern "C" int dt_track_score(dt_ctx *ctx, const float *d_gt_boxes, const int *d_gt_counts, const int *d_gt_ids, int gcap,
+                              const float *d_hyp_boxes, const int *d_hyp_counts, const int *d_hyp_ids, int hcap, int id_stride, int hyp_label_at,
+                              int n_clips, int T, float iou_threshold, int flags, int ocap, int *d_totals, int *d_objs, int *d_nobjs,
+                              int *d_fcounts, int *d_match, float *d_miou)
+{
+    if (!ctx || !d_gt_boxes || !d_gt_counts || !d_gt_ids || !d_hyp_boxes || !d_hyp_counts || !d_hyp_ids || !d_totals || !d_objs || !d_nobjs)
+        return dt_fail(ctx, DT_ERR_ARG, "null argument");
+    if (n_clips < 0 || T <= 0 || gcap <= 0 || hcap <= 0 || ocap <= 0) return dt_fail(ctx, DT_ERR_ARG, "n_clips must not be negative; T, gcap, hcap and ocap must be positive");
+    if (id_stride < 1) return dt_fail(ctx, DT_ERR_ARG, "id_stride must be at least 1");
+    if (hyp_label_at < 0 || hyp_label_at > 7) return dt_fail(ctx, DT_ERR_ARG, "hyp_label_at must be in 0..7");
+    if (flags & ~(DT_SCORE_ANY_LABEL | DT_SCORE_RESUME)) return dt_fail(ctx, DT_ERR_ARG, "flags must be a combination of DT_SCORE_ANY_LABEL and DT_SCORE_RESUME");
+    if ((d_match != nullptr) != (d_miou != nullptr)) return dt_fail(ctx, DT_ERR_ARG, "d_match and d_miou are given both or neither");
+    if (!(iou_threshold > 0.0f && iou_threshold <= 1.0f)) return dt_fail(ctx, DT_ERR_ARG, "the IoU threshold must be in (0, 1]");
+    if (track_score_lds_bytes(gcap, hcap, ocap) > (size_t)160 * 1024)
+        return dt_fail(ctx, DT_ERR_ARG, "8 * ocap + 11 * gcap + 7 * hcap words do not fit the 160 KB of LDS");
+    if (n_clips == 0) return DT_OK;
+    ProfScope ps(ctx, "associate", 0.0, 4.0 * n_clips * ((double)T * (gcap * 11.0 + hcap * (8.0 + id_stride)) + ocap * 8.0), "score");
+    ScoreArgs a{d_gt_boxes, d_gt_counts, d_gt_ids, d_hyp_boxes, d_hyp_counts, d_hyp_ids, gcap, hcap, id_stride, hyp_label_at, T, ocap,
+                iou_threshold, d_totals, d_objs, d_nobjs, d_fcounts, d_match, d_miou};
+    const int rc = launch_track_score(ctx->stream, a, n_clips, flags);
+    if (rc) return dt_fail(ctx, launch_code(rc), "track score launch failed");
+    return DT_OK;
+}
+
 // ---------------------------------------------------------------------------
 // tracker head (ConvLSTM2D + 1x1)
 // ---------------------------------------------------------------------------

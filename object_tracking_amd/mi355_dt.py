@@ -23,6 +23,10 @@ DT_TRACK_FLOATS = 8      # a track read-out row: x, y, w, h, label, vx, vy, 0
 DT_TRACK_INTS = 4        # ... and its integers: id, age, hits, box
 DT_MATCH_BEST_FIRST = 1  # track match policy bits (dt_associate_tracks_match): candidate pairs taken best IoU first
 DT_MATCH_ANY_LABEL = 2   # ... labels not compared
+DT_SCORE_INTS = 8        # track scoring totals (dt_track_score): frames, gt boxes, hyp boxes, matches, switches, fragments, overflow, 0
+DT_SCORE_OBJ_INTS = 8    # ... an object row: gt id, last track id, present, matched, switches, fragments, last appearance matched, 0
+DT_SCORE_ANY_LABEL = 1   # ... flag bits: labels not compared
+DT_SCORE_RESUME = 2      # ... totals / objs / nobjs are in-out, the call continues from them
 DT_PIX_RGB24 = 0         # pixel formats of dt_frame_desc (dt_ingest_frames): 3 interleaved bytes per pixel, as they lie
 DT_PIX_NV12 = 1          # ... plane0 = Y, plane1 = U,V interleaved, one pair per 2x2 pixels
 DT_PIX_SWAP_RB = 16      # ... flag: output channels 0 and 2 exchanged
@@ -48,6 +52,7 @@ SYMBOLS = [
     "dt_tiny_stream_open", "dt_tiny_stream_reset", "dt_tiny_stream_sequence", "dt_tiny_stream_forward",
     "dt_ingest_frames",
     "dt_view_fit", "dt_view_affine", "dt_ingest_views", "dt_boxes_map",
+    "dt_track_score",
 ]
 
 _lib = None
@@ -121,6 +126,7 @@ def load_library():
     L.dt_associate_stream_tracks.argtypes = [vp, vp, vp, ci, ci, ci, cf, ci, cf, ci, ctypes.POINTER(ci), vp, vp, vp, vp, vp, vp, vp]
     L.dt_associate_tracks_match.argtypes = [vp, vp, vp, ci, ci, ci, cf, ci, ci, cf, ci, ci, vp, vp, vp, vp, vp, vp, vp]
     L.dt_associate_stream_tracks_match.argtypes = [vp, vp, vp, ci, ci, ci, cf, ci, cf, ci, ci, ctypes.POINTER(ci), vp, vp, vp, vp, vp, vp, vp]
+    L.dt_track_score.argtypes = [vp, vp, vp, vp, ci, vp, vp, vp, ci, ci, ci, ci, ci, cf, ci, ci, vp, vp, vp, vp, vp, vp]
     L.dt_track_row_width.argtypes = [vp]
     L.dt_track_detect.argtypes = [vp, vp, ci, ci, vp]
     L.dt_track_recurrent.argtypes = [vp, vp, ci, ci, vp, vp]
@@ -560,6 +566,52 @@ class Context(object):
                                                  tcap, float(gain), int(min_hits), _dptr(r["ids"]), _dptr(r["nids"]), _dptr(r["gaps"]),
                                                  _dptr(r["hits"]), _dptr(r.get("tracks")), _dptr(r.get("track_info")), _dptr(r.get("track_counts"))),
                     "dt_associate_tracks")
+        return r
+
+    def track_score(self, gt_boxes, gt_counts, gt_ids, hyp_boxes, hyp_counts, hyp_ids, iou_threshold=0.5, any_label=False, obj_cap=None,
+                    state=None, per_box=True):
+        """CLEAR-MOT counts of a tracker's output against ground-truth tracks (dt_track_score; the rule: DESIGN.md "Track scoring").
+        gt_boxes [n,T,gcap,8] (x, y, w, h in floats 0..3, the label in float 5), gt_counts [n,T] int32, gt_ids [n,T,gcap] int32;
+        hyp_boxes [n,T,hcap,8] with hyp_counts [n,T] and hyp_ids either [n,T,hcap] int32 -- `boxes` / `counts` / `ids` of an association
+        result, the label in float 5 -- or a [n,T,hcap,4] `track_info` beside `tracks` / `track_counts`, the label in float 4.
+        -> dict: totals [n,8] (frames, gt, hyp, matches, switches, fragments, overflow, 0), objs [n,obj_cap,8] (gt id, last track id,
+        present, matched, switches, fragments, last appearance matched, 0), nobjs [n], frame_counts [n,T,4] (gt, hyp, matches, switches)
+        and, with per_box, match [n,T,gcap] (hypothesis row or -1) and miou [n,T,gcap] (else both None).
+        obj_cap: rows of the object table (None: the state's, or max(64, 2 * gcap)); ids beyond it are scored without memory and counted
+        in `overflow`.  state: a previous result whose totals / objs / nobjs this call continues (they are copied, not written): chunks
+        of any sizes along T give the result of one call on the concatenation.  utility.evaluate.summarize turns it into MOTA etc."""
+        t = self.torch
+        i32 = lambda *shape: t.empty(shape, dtype=t.int32, device=self.device)
+        n, T, gcap, _ = gt_boxes.shape
+        hcap = hyp_boxes.shape[2]
+        assert hyp_boxes.shape[:2] == (n, T) and hyp_boxes.shape[3] == 8 and gt_boxes.shape[3] == DT_BOX_FLOATS
+        if hyp_ids.dim() == 4:
+            stride, label_at = int(hyp_ids.shape[3]), 4
+        else:
+            stride, label_at = 1, 5
+        assert tuple(hyp_ids.shape[:3]) == (n, T, hcap) and tuple(gt_ids.shape) == (n, T, gcap)
+        assert tuple(gt_counts.shape) == (n, T) and tuple(hyp_counts.shape) == (n, T)
+        for x, dt in ((gt_boxes, t.float32), (hyp_boxes, t.float32), (gt_counts, t.int32), (gt_ids, t.int32), (hyp_counts, t.int32),
+                      (hyp_ids, t.int32)):
+            assert x.is_cuda and x.is_contiguous() and x.dtype == dt
+        flags = DT_SCORE_ANY_LABEL if any_label else 0
+        if state is not None:
+            ocap = int(state["objs"].shape[1])
+            assert obj_cap is None or int(obj_cap) == ocap, "obj_cap differs from the state's"
+            assert int(state["objs"].shape[0]) == n
+            totals, objs, nobjs = state["totals"].clone(), state["objs"].clone(), state["nobjs"].clone()
+            flags |= DT_SCORE_RESUME
+        else:
+            ocap = max(64, 2 * gcap) if obj_cap is None else int(obj_cap)
+            totals, objs, nobjs = i32(n, DT_SCORE_INTS), i32(n, max(ocap, 0), DT_SCORE_OBJ_INTS), i32(n)
+        r = dict(totals=totals, objs=objs, nobjs=nobjs, frame_counts=i32(n, T, 4),
+                 match=i32(n, T, gcap) if per_box else None,
+                 miou=t.empty((n, T, gcap), dtype=t.float32, device=self.device) if per_box else None)
+        self._sync_stream()
+        self._check(self.lib.dt_track_score(self.h, _dptr(gt_boxes), _dptr(gt_counts), _dptr(gt_ids), gcap, _dptr(hyp_boxes), _dptr(hyp_counts),
+                                            _dptr(hyp_ids), hcap, stride, label_at, n, T, float(iou_threshold), flags, ocap, _dptr(totals),
+                                            _dptr(objs), _dptr(nobjs), _dptr(r["frame_counts"]), _dptr(r["match"]), _dptr(r["miou"])),
+                    "dt_track_score")
         return r
 
     def pack_detections(self, boxes, counts, ids, nids, n_rows):

@@ -352,6 +352,25 @@ class MultiObjDetTracker(object):
                        track_info=z((0, T, tcap, mi355_dt.DT_TRACK_INTS), torch.int32), track_counts=z((0, T), torch.int32))
         return res
 
+    def score(self, result, gt, confirmed=False, iou_threshold=0.5, any_label=False, obj_cap=None, state=None, per_box=True):
+        """Score a track_clips / track_stream result against ground-truth tracks on the device (mi355_dt.Context.track_score; the
+        rule: DESIGN.md "Track scoring").  gt = (gt_boxes [n,T,gcap,8], gt_counts [n,T], gt_ids [n,T,gcap]), numpy or device tensors
+        (utility.evaluate.gt_from_mot builds one sequence of them from MOT gt.txt).  The hypotheses are the result's boxes / counts /
+        ids, or with confirmed=True its read-out tracks / track_counts / track_info (MIN_HITS set; coasting tracks included).
+        state: the previous chunk's score, for results of track_stream.  utility.evaluate.summarize gives MOTA etc. of the return."""
+        import torch
+        ctx = self.model.ctx
+        dev = lambda a, dt: (a if torch.is_tensor(a) else torch.from_numpy(np.ascontiguousarray(a))).to(device=ctx.device, dtype=dt).contiguous()
+        gb, gc, gi = dev(gt[0], torch.float32), dev(gt[1], torch.int32), dev(gt[2], torch.int32)
+        if confirmed:
+            if result.get("tracks") is None:
+                raise mi355_dt.NativeError("score(confirmed=True) needs the track read-out in the result (MIN_HITS)")
+            hyp = (result["tracks"], result["track_counts"], result["track_info"])
+        else:
+            hyp = (result["boxes"], result["counts"], result["ids"])
+        return ctx.track_score(gb, gc, gi, hyp[0], hyp[1], hyp[2], iou_threshold=iou_threshold, any_label=any_label, obj_cap=obj_cap,
+                               state=state, per_box=per_box)
+
     @staticmethod
     def boxes_from_result(res, clip=0):
         """Host view of track_clips output for one clip: list over t of BoundBox lists."""
