@@ -1526,18 +1526,18 @@ def _conv_case(rs, B, H, W, Cin, Cout, heavy_tail=False):
     return x, w, b
 
 
-@pytest.mark.parametrize("B,H,W,Cin,Cout,pool", [
+SPLIT_CONV_SHAPES = [
     (2, 13, 13, 64, 128, 0),     # one ragged row tile, 128-wide column tile, K = 4 stages
     (6, 13, 13, 256, 256, 0),    # mosaic g = 2, 256-wide column tile
     (3, 26, 26, 128, 512, 2),    # pooled + full resolution outputs, two column tiles
     (1, 13, 13, 1280, 256, 0),   # conv_22's K = 1280 (80 stages)
     (40, 26, 26, 32, 128, 1),    # several row tiles (Mt > 256), the shortest K the kernel takes (2 stages), pooled
     (7, 12, 18, 96, 384, 0),     # K = 6 stages, N = 3 x 128
-])
-@pytest.mark.parametrize("half", ["0", "1"], ids=["tile256", "tile128x2"])
-def test_conv2d_split_bf16_gemm_vs_oracle(ctx, monkeypatch, B, H, W, Cin, Cout, pool, half):
-    """The split-operand GEMM (DT_S3=2: wherever the shape allows) against the oracle AND against the fp32 MFMA path of
-    the same layer: the two differ by no more than the fp32 path differs from the oracle."""
+]
+
+
+def _split_gemm_vs_oracle(ctx, monkeypatch, B, H, W, Cin, Cout, pool, half, h2):
+    monkeypatch.setenv("DT_S3_H2", h2)          # 1: two fp16 terms (the default); 0: three bf16 terms (what DT_PIN and short forwards run)
     monkeypatch.setenv("DT_WINO", "2")
     monkeypatch.setenv("DT_WINO_TILE", "6")
     monkeypatch.setenv("DT_S3_HALF", half)      # 1: the 128-row-tile / two-workgroups-per-CU form wherever N % 256 == 0
@@ -1554,6 +1554,8 @@ def test_conv2d_split_bf16_gemm_vs_oracle(ctx, monkeypatch, B, H, W, Cin, Cout, 
         assert ctx.profile_read("conv_igemm")["launches"] == (0 if s3 == "2" else 1)
         if s3 == "2":
             assert ctx.profile_read("s3_tile:128x2")["launches"] == (1 if (half == "1" and Cout % 256 == 0) else 0)
+            assert ctx.profile_read("s3_form:f16x2")["launches"] == (1 if h2 == "1" else 0)
+            assert ctx.profile_read("s3_form:bf16x3")["launches"] == (0 if h2 == "1" else 1)
         outs[s3] = [g.cpu().numpy() for g in (got if pool == 2 else (got,))]
     refs = {0: [ref], 1: [orc.maxpool2(ref)], 2: [ref, orc.maxpool2(ref)]}[pool]
     for a, f, r in zip(outs["2"], outs["0"], refs):
@@ -1561,6 +1563,21 @@ def test_conv2d_split_bf16_gemm_vs_oracle(ctx, monkeypatch, B, H, W, Cin, Cout, 
         assert e_s3 < 2e-4 and e_f32 < 2e-4                 # the F(6x6) tolerance of test_conv2d_winograd_vs_oracle
         assert e_s3 < 1.25 * e_f32 + 1e-6, (e_s3, e_f32)    # and the split form is as close to the oracle as fp32 MFMA is
         assert relerr(a, f) < 5e-5                          # ... the two forms differ by GEMM rounding (amplified by the output transform) only
+
+
+@pytest.mark.parametrize("B,H,W,Cin,Cout,pool", SPLIT_CONV_SHAPES)
+@pytest.mark.parametrize("half", ["0", "1"], ids=["tile256", "tile128x2"])
+def test_conv2d_split_bf16_gemm_vs_oracle(ctx, monkeypatch, B, H, W, Cin, Cout, pool, half):
+    """The split-operand GEMM (DT_S3=2: wherever the shape allows) against the oracle AND against the fp32 MFMA path of
+    the same layer: the two differ by no more than the fp32 path differs from the oracle.  The fp16 form (DT_S3_H2=1)."""
+    _split_gemm_vs_oracle(ctx, monkeypatch, B, H, W, Cin, Cout, pool, half, "1")
+
+
+@pytest.mark.parametrize("B,H,W,Cin,Cout,pool", SPLIT_CONV_SHAPES)
+@pytest.mark.parametrize("half", ["0", "1"], ids=["tile256", "tile128x2"])
+def test_conv2d_split_bf16_gemm_vs_oracle_bf16x3(ctx, monkeypatch, B, H, W, Cin, Cout, pool, half):
+    """the same in the three-term bf16 form (DT_S3_H2=0), at the same bars"""
+    _split_gemm_vs_oracle(ctx, monkeypatch, B, H, W, Cin, Cout, pool, half, "0")
 
 
 def test_split_bf16_gemm_error_against_float64(ctx, monkeypatch):
