@@ -69,6 +69,7 @@ DT_API int dt_set_stream(dt_ctx *ctx, void *hip_stream);
  * and the one frame-ingest entry dt_ingest_frames
  * and the four frame-view entries dt_view_fit, dt_view_affine, dt_ingest_views, dt_boxes_map
  * and the one track scoring entry dt_track_score
+ * and the two detection scoring entries dt_detect_match, dt_detect_rank
  * -- additions only, the number stayed; 1.07: 1.06 + dt_gemm_split, dt_policy_set) */
 DT_API int dt_abi_version(void);
 
@@ -391,8 +392,8 @@ DT_API int dt_associate_tracks_match(dt_ctx *ctx, const float *d_boxes, const in
  * d_nobjs on are zero with -1 in the gt id and last track id fields.  With it the three are in-out and the call continues from them:
  * chunks of any sizes along T give every output of the one call on the concatenation, bit for bit -- the contract of the stream entries,
  * with the state owned by the caller (no slot table).  Asynchronous on the context's stream; n_clips = 0 is a no-op.
- * Not done here: an optimal (Hungarian) assignment, IDF1 / HOTA, ignore regions and visibility weighting, dropping coasting rows,
- * detector mAP.
+ * Not done here: an optimal (Hungarian) assignment, IDF1 / HOTA, ignore regions and visibility weighting, dropping coasting rows.
+ * (Detector AP: dt_detect_match / dt_detect_rank below.)
  * DT_ERR_ARG (nothing launched): a NULL required pointer, n_clips < 0, T, gcap, hcap or ocap <= 0, id_stride < 1, hyp_label_at outside
  * 0..7, unknown flag bits, one of d_match / d_miou without the other, a threshold that is NaN or outside (0, 1], or a table and frame
  * that do not fit the 160 KB of LDS: 8 * ocap + 11 * gcap + 7 * hcap words must not exceed 40960 (gcap = hcap = 128: ocap up to 4832). */
@@ -400,6 +401,53 @@ DT_API int dt_track_score(dt_ctx *ctx, const float *d_gt_boxes, const int *d_gt_
                  const float *d_hyp_boxes, const int *d_hyp_counts, const int *d_hyp_ids, int hcap, int id_stride, int hyp_label_at,
                  int n_clips, int T, float iou_threshold, int flags, int ocap,
                  int *d_totals, int *d_objs, int *d_nobjs, int *d_fcounts, int *d_match, float *d_miou);
+
+/* Detection scoring (BUILD-DEFINED, DESIGN.md "Detection scoring"): per-class average precision of a detector's boxes against ground truth,
+ * by the VOC devkit's match.  Two entries: the match of every frame, then the position of every detection in its class's score order over
+ * the whole set.  Both give integers (and the IoU of the match); precision, recall and AP are taken from them on the host, in float64
+ * (Python: utility.evaluate.average_precision).  No float is summed on the device.
+ *   d_det_boxes [B, cap, DT_BOX_FLOATS]   x, y, w, h in floats 0..3, the label in float 5, the ranking score in float score_at (6: dt_decode's
+ *               score, 4: its conf); d_det_counts [B] int32; rows i < min(count, cap) take part (a negative count reads as 0)
+ *   d_gt_boxes  [B, gcap, DT_BOX_FLOATS]  x, y, w, h, the label in float 5; d_gt_counts [B]; rows g < min(count, gcap) take part
+ *   d_gt_flags  [B, gcap] int32, bit 0 = ignore (VOC "difficult", MOT distractors); NULL: no row is ignored
+ *   h_thresholds[n_thr] on the HOST, 1 <= n_thr <= 16, each in (0, 1]: one call gives COCO's .50:.05:.95
+ * A row takes part only if its label l is an integer value with 0 <= l < NC.  Boxes and scores must be finite (and so must the areas
+ * w * h).  Two boxes without area have the IoU 0 / 0 = NaN: the tests below are written as the kernel makes them, so a NaN is never the
+ * larger IoU and is below no threshold.
+ * MATCH, per frame, independent of other frames:
+ *   1. the candidates of detection i are all ground-truth rows of equal label (as floats), claimed and ignored rows too; best[i] is the
+ *      candidate of the largest bbox_iou(gt g, det i) as float32 (dt_bbox_iou's bits), ties to the lowest g, and iou[i] that IoU; without a
+ *      candidate best = -1 and iou = 0.  Neither depends on the threshold.
+ *   2. per threshold k the frame's detections are walked by descending score (float32, ties to the lower row):
+ *      best < 0 or iou < thr[k]: FP (state 0); else best is an ignore row: ignored (state 2), nothing is claimed; else best is unclaimed at
+ *      k: TP (state 1), and it is claimed; else FP (a duplicate -- no second-best row is looked for).
+ *   d_state [n_thr, B, cap] int32   1 TP, 0 FP, 2 ignored, -1 in rows that take no part (beyond the count, or a label outside 0..NC-1)
+ *   d_best  [B, cap] int32, d_iou [B, cap] float32   -1 and 0 in rows that take no part
+ * RANK, over all B frames, per threshold k and label c: the detections of label c with state 0 or 1 at k, by descending score, ties to
+ * the lower flat index b * cap + i.
+ *   d_rank  [n_thr, B, cap] int32   the detection's position in that order, from 0; -1 for ignored and unused rows
+ *   d_ctp   [n_thr, B, cap] int32   the TPs at positions <= its own; -1 likewise
+ *   d_ngt   [NC] int32              ground-truth rows of label c without the ignore bit
+ *   d_ndet, d_ntp [n_thr, NC] int32 the ranked detections, and the TPs among them
+ * Every word of every output is written; the buffers may arrive uninitialised.  Asynchronous on the context's stream.  B = 0 launches no
+ * match and the rank writes the totals as zeros; the per-frame arrays, which are empty then, are not looked at and may be NULL.
+ * CHUNK CONTRACT: the match is per frame, so the match outputs of chunks of frames, concatenated along B (d_state along its second axis),
+ * are the outputs of one call on the concatenation; the rank runs once over the concatenation (it needs every score of a class).
+ * The match runs one 64-lane workgroup per frame with the frame in LDS: 3 * cap + 6 * gcap words must not exceed 40960 (160 KB;
+ * cap = gcap = 1024 uses 9216).  The rank compacts the rows in use first (a prefix sum over min(count, cap)) and compares each with
+ * every other such row: its work grows with (rows in use)^2, not (B * cap)^2; it keeps 16 bytes per row of [B, cap] in a workspace.
+ * Not done here, on purpose: COCO's match (best UNCLAIMED row, crowd regions), area ranges and max-detections cuts, per-class score
+ * thresholds, label-free AP.
+ * DT_ERR_ARG (nothing launched, no output written): a NULL required pointer, B < 0, cap, gcap or NC <= 0, n_thr outside 1..16, a
+ * threshold that is NaN or outside (0, 1], score_at outside 0..7, B * cap or B * gcap >= 2^31, or (match) the LDS bound above. */
+DT_API int dt_detect_match(dt_ctx *ctx, const float *d_det_boxes, const int *d_det_counts, int cap, int score_at,
+                 const float *d_gt_boxes, const int *d_gt_counts, const int *d_gt_flags, int gcap,
+                 int B, int NC, const float *h_thresholds, int n_thr,
+                 int *d_state, int *d_best, float *d_iou);
+DT_API int dt_detect_rank(dt_ctx *ctx, const float *d_det_boxes, const int *d_det_counts, int cap, int score_at, const int *d_state,
+                 const float *d_gt_boxes, const int *d_gt_counts, const int *d_gt_flags, int gcap,
+                 int B, int NC, int n_thr,
+                 int *d_rank, int *d_ctp, int *d_ngt, int *d_ndet, int *d_ntp);
 
 /* ---- streaming: ConvLSTM state and track ids carried across calls (addition; the reference's predict() sees one window) ---- *
  * A live stream delivers a frame, or a few, at a time.  The context holds a table of STREAM SLOTS in device memory; per slot the ConvLSTM

@@ -430,6 +430,48 @@ size_t track_score_lds_bytes(int gcap, int hcap, int ocap);      // dynamic LDS 
 // 0: launched; 1: device error.  flags: DT_SCORE_* bits.  The arguments are dt_track_score's, validated there (n_clips > 0, the LDS fits).
 int launch_track_score(hipStream_t st, const ScoreArgs &a, int n_clips, int flags);
 
+// detection scoring (detscore.hip, DESIGN.md "Detection scoring"): the VOC match of detections against ground truth per frame, then the
+// position of every detection in its class's score order over all frames.  Integers out; the ratios are taken on the host.
+#define DT_DETSCORE_MAX_THR 16
+struct DetMatchArgs {
+    const float *det_boxes;  // [B][cap][DT_BOX_FLOATS]
+    const int *det_counts;   // [B]
+    const float *gt_boxes;   // [B][gcap][DT_BOX_FLOATS]
+    const int *gt_counts;    // [B]
+    const int *gt_flags;     // [B][gcap] or null (no row is ignored)
+    int cap, gcap, score_at, B, NC, n_thr;
+    float thr[DT_DETSCORE_MAX_THR];
+    int *state;              // [n_thr][B][cap]
+    int *best;               // [B][cap]
+    float *iou;              // [B][cap]
+};
+struct DetRankArgs {
+    const float *det_boxes;  // [B][cap][DT_BOX_FLOATS]
+    const int *det_counts;   // [B]
+    const int *state;        // [n_thr][B][cap]
+    const float *gt_boxes;   // [B][gcap][DT_BOX_FLOATS]
+    const int *gt_counts;    // [B]
+    const int *gt_flags;     // [B][gcap] or null
+    int cap, gcap, score_at, B, NC, n_thr;
+    int *rank, *ctp;         // [n_thr][B][cap] each
+    int *ngt;                // [NC]
+    int *ndet, *ntp;         // [n_thr][NC] each
+    // workspace of the call: offsets [B + 1] (rows in use before each frame; the last is their number N), then the rows in use in
+    // flat-index order, one array per field: score, label (-1: outside 0..NC-1), the states of all thresholds two bits each, flat index
+    int *offsets;
+    float *c_score;
+    int *c_label;
+    unsigned *c_state;
+    int *c_flat;
+};
+size_t detect_match_lds_bytes(int cap, int gcap);                // dynamic LDS of the match launch; dt_detect_match refuses more than 160 KB
+size_t detect_rank_ws_bytes(int B, int cap);                     // the workspace above, in bytes
+void detect_rank_ws_carve(DetRankArgs &a, void *ws);             // ... and its pointers
+// 0: launched; 1: device error.  The arguments are those of dt_detect_match / dt_detect_rank, validated there (the LDS fits; B may be 0
+// for the rank, which then only writes the totals)
+int launch_detect_match(hipStream_t st, const DetMatchArgs &a);
+int launch_detect_rank(hipStream_t st, const DetRankArgs &a);
+
 // ---------------------------------------------------------------------------
 // stream slots: state that outlives a call (stream_state.hip)
 // ---------------------------------------------------------------------------

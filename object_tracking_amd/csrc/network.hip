@@ -1926,6 +1926,57 @@ extern "C" int dt_track_score(dt_ctx *ctx, const float *d_gt_boxes, const int *d
     return DT_OK;
 }
 
+// detection scoring (DESIGN.md "Detection scoring"): the VOC match per frame, then every detection's position in its class's score order
+static const char *detect_score_args(const void *det_boxes, const void *det_counts, int cap, int score_at, const void *gt_boxes,
+                                     const void *gt_counts, int gcap, int B, int NC, int n_thr)
+{
+    if (B < 0 || cap <= 0 || gcap <= 0 || NC <= 0) return "B must not be negative; cap, gcap and NC must be positive";
+    if (B > 0 && (!det_boxes || !det_counts || !gt_boxes || !gt_counts)) return "null argument";      // (no frame: the per-frame arrays are not looked at)
+    if (n_thr < 1 || n_thr > DT_DETSCORE_MAX_THR) return "n_thr must be in 1..16";
+    if (score_at < 0 || score_at > 7) return "score_at must be in 0..7";
+    if ((long long)B * cap >= (1ll << 31) || (long long)B * gcap >= (1ll << 31)) return "B * cap and B * gcap must be below 2^31";
+    return nullptr;
+}
+
+extern "C" int dt_detect_match(dt_ctx *ctx, const float *d_det_boxes, const int *d_det_counts, int cap, int score_at,
+                               const float *d_gt_boxes, const int *d_gt_counts, const int *d_gt_flags, int gcap, int B, int NC,
+                               const float *h_thresholds, int n_thr, int *d_state, int *d_best, float *d_iou)
+{
+    if (!ctx) return DT_ERR_ARG;
+    if (!h_thresholds || (B > 0 && (!d_state || !d_best || !d_iou))) return dt_fail(ctx, DT_ERR_ARG, "null argument");
+    if (const char *why = detect_score_args(d_det_boxes, d_det_counts, cap, score_at, d_gt_boxes, d_gt_counts, gcap, B, NC, n_thr))
+        return dt_fail(ctx, DT_ERR_ARG, "%s", why);
+    DetMatchArgs a{d_det_boxes, d_det_counts, d_gt_boxes, d_gt_counts, d_gt_flags, cap, gcap, score_at, B, NC, n_thr, {}, d_state, d_best, d_iou};
+    for (int k = 0; k < n_thr; ++k) {
+        if (!(h_thresholds[k] > 0.0f && h_thresholds[k] <= 1.0f)) return dt_fail(ctx, DT_ERR_ARG, "every IoU threshold must be in (0, 1]");
+        a.thr[k] = h_thresholds[k];
+    }
+    if (detect_match_lds_bytes(cap, gcap) > (size_t)160 * 1024)
+        return dt_fail(ctx, DT_ERR_ARG, "3 * cap + 6 * gcap words do not fit the 160 KB of LDS");
+    if (B == 0) return DT_OK;
+    ProfScope ps(ctx, "score", 0.0, 4.0 * B * (cap * (8.0 + 2.0 + n_thr) + gcap * 9.0), "detect_match");
+    if (launch_detect_match(ctx->stream, a)) return dt_fail(ctx, DT_ERR_DEVICE, "detect match launch failed");
+    return DT_OK;
+}
+
+extern "C" int dt_detect_rank(dt_ctx *ctx, const float *d_det_boxes, const int *d_det_counts, int cap, int score_at, const int *d_state,
+                              const float *d_gt_boxes, const int *d_gt_counts, const int *d_gt_flags, int gcap, int B, int NC, int n_thr,
+                              int *d_rank, int *d_ctp, int *d_ngt, int *d_ndet, int *d_ntp)
+{
+    if (!ctx) return DT_ERR_ARG;
+    if ((B > 0 && (!d_state || !d_rank || !d_ctp)) || !d_ngt || !d_ndet || !d_ntp) return dt_fail(ctx, DT_ERR_ARG, "null argument");
+    if (const char *why = detect_score_args(d_det_boxes, d_det_counts, cap, score_at, d_gt_boxes, d_gt_counts, gcap, B, NC, n_thr))
+        return dt_fail(ctx, DT_ERR_ARG, "%s", why);
+    DetRankArgs a{d_det_boxes, d_det_counts, d_state, d_gt_boxes, d_gt_counts, d_gt_flags, cap, gcap, score_at, B, NC, n_thr,
+                  d_rank, d_ctp, d_ngt, d_ndet, d_ntp, nullptr, nullptr, nullptr, nullptr, nullptr};
+    void *ws = ws_get(ctx, "detect_rank", detect_rank_ws_bytes(B, cap));
+    if (!ws) return DT_ERR_DEVICE;
+    detect_rank_ws_carve(a, ws);
+    ProfScope ps(ctx, "score", 0.0, 4.0 * B * (cap * (2.0 + 3.0 * n_thr) + gcap * 2.0), "detect_rank");
+    if (launch_detect_rank(ctx->stream, a)) return dt_fail(ctx, DT_ERR_DEVICE, "detect rank launch failed");
+    return DT_OK;
+}
+
 // ---------------------------------------------------------------------------
 // tracker head (ConvLSTM2D + 1x1)
 // ---------------------------------------------------------------------------

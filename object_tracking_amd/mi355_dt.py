@@ -53,6 +53,7 @@ SYMBOLS = [
     "dt_ingest_frames",
     "dt_view_fit", "dt_view_affine", "dt_ingest_views", "dt_boxes_map",
     "dt_track_score",
+    "dt_detect_match", "dt_detect_rank",
 ]
 
 _lib = None
@@ -127,6 +128,8 @@ def load_library():
     L.dt_associate_tracks_match.argtypes = [vp, vp, vp, ci, ci, ci, cf, ci, ci, cf, ci, ci, vp, vp, vp, vp, vp, vp, vp]
     L.dt_associate_stream_tracks_match.argtypes = [vp, vp, vp, ci, ci, ci, cf, ci, cf, ci, ci, ctypes.POINTER(ci), vp, vp, vp, vp, vp, vp, vp]
     L.dt_track_score.argtypes = [vp, vp, vp, vp, ci, vp, vp, vp, ci, ci, ci, ci, ci, cf, ci, ci, vp, vp, vp, vp, vp, vp]
+    L.dt_detect_match.argtypes = [vp, vp, vp, ci, ci, vp, vp, vp, ci, ci, ci, vp, ci, vp, vp, vp]
+    L.dt_detect_rank.argtypes = [vp, vp, vp, ci, ci, vp, vp, vp, vp, ci, ci, ci, ci, vp, vp, vp, vp, vp]
     L.dt_track_row_width.argtypes = [vp]
     L.dt_track_detect.argtypes = [vp, vp, ci, ci, vp]
     L.dt_track_recurrent.argtypes = [vp, vp, ci, ci, vp, vp]
@@ -612,6 +615,64 @@ class Context(object):
                                             _dptr(hyp_ids), hcap, stride, label_at, n, T, float(iou_threshold), flags, ocap, _dptr(totals),
                                             _dptr(objs), _dptr(nobjs), _dptr(r["frame_counts"]), _dptr(r["match"]), _dptr(r["miou"])),
                     "dt_track_score")
+        return r
+
+    def _detect_score_inputs(self, det_boxes, det_counts, gt_boxes, gt_counts, gt_flags):
+        t = self.torch
+        B, cap, _ = det_boxes.shape
+        gcap = gt_boxes.shape[1]
+        assert det_boxes.shape[2] == DT_BOX_FLOATS and tuple(gt_boxes.shape) == (B, gcap, DT_BOX_FLOATS)
+        assert tuple(det_counts.shape) == (B,) and tuple(gt_counts.shape) == (B,)
+        assert gt_flags is None or tuple(gt_flags.shape) == (B, gcap)
+        for x, dt in ((det_boxes, t.float32), (gt_boxes, t.float32), (det_counts, t.int32), (gt_counts, t.int32), (gt_flags, t.int32)):
+            assert x is None or (x.is_cuda and x.is_contiguous() and x.dtype == dt)
+        return B, cap, gcap
+
+    def detect_match(self, det_boxes, det_counts, gt_boxes, gt_counts, nb_class, thresholds=(0.5,), gt_flags=None, score_at=6):
+        """The VOC match of detections against ground truth, per frame (dt_detect_match; the rule: DESIGN.md "Detection scoring").
+        det_boxes [B,cap,8] / det_counts [B] as KerasYOLO.detect leaves them (the label in float 5, the ranking score in float
+        score_at: 6 = score, 4 = conf); gt_boxes [B,gcap,8] (x, y, w, h, the label in float 5), gt_counts [B], gt_flags [B,gcap] int32
+        with bit 0 = ignore, or None; thresholds: 1..16 IoU thresholds in (0, 1].
+        -> dict of device tensors: state [n_thr,B,cap] int32 (1 TP, 0 FP, 2 ignored, -1 unused), best [B,cap] int32 (the ground-truth
+        row of the largest IoU among those of the detection's label, -1 without one), iou [B,cap] float32; and thresholds, nb_class.
+        Frames are matched independently: results of chunks of frames concatenate along B."""
+        t = self.torch
+        B, cap, gcap = self._detect_score_inputs(det_boxes, det_counts, gt_boxes, gt_counts, gt_flags)
+        thr = np.ascontiguousarray(np.asarray(thresholds, dtype=np.float32).reshape(-1))
+        r = dict(state=t.empty((len(thr), B, cap), dtype=t.int32, device=self.device),
+                 best=t.empty((B, cap), dtype=t.int32, device=self.device), iou=self._f32(B, cap),
+                 thresholds=thr.copy(), nb_class=int(nb_class))
+        self._sync_stream()
+        self._check(self.lib.dt_detect_match(self.h, _dptr(det_boxes), _dptr(det_counts), cap, int(score_at), _dptr(gt_boxes),
+                                             _dptr(gt_counts), _dptr(gt_flags), gcap, B, int(nb_class),
+                                             thr.ctypes.data_as(ctypes.c_void_p), len(thr), _dptr(r["state"]), _dptr(r["best"]),
+                                             _dptr(r["iou"])), "dt_detect_match")
+        return r
+
+    def detect_rank(self, det_boxes, det_counts, state, gt_boxes, gt_counts, nb_class, gt_flags=None, score_at=6):
+        """Every detection's position in its class's score order over all B frames (dt_detect_rank), from the `state` [n_thr,B,cap]
+        of detect_match on the same inputs (chunks concatenated along B).
+        -> dict of device tensors: rank, ctp [n_thr,B,cap] int32 (the position among the class's detections of state 0 / 1 by
+        descending score, ties to the lower flat index, and the TPs up to it; -1 for ignored and unused rows), ngt [nb_class],
+        ndet, ntp [n_thr,nb_class] int32.  utility.evaluate.average_precision turns them into AP."""
+        t = self.torch
+        B, cap, gcap = self._detect_score_inputs(det_boxes, det_counts, gt_boxes, gt_counts, gt_flags)
+        n_thr, C = int(state.shape[0]), int(nb_class)
+        assert tuple(state.shape) == (n_thr, B, cap) and state.is_cuda and state.is_contiguous() and state.dtype == t.int32
+        i32 = lambda *shape: t.empty(shape, dtype=t.int32, device=self.device)
+        r = dict(rank=i32(n_thr, B, cap), ctp=i32(n_thr, B, cap), ngt=i32(max(C, 0)), ndet=i32(n_thr, max(C, 0)), ntp=i32(n_thr, max(C, 0)))
+        self._sync_stream()
+        self._check(self.lib.dt_detect_rank(self.h, _dptr(det_boxes), _dptr(det_counts), cap, int(score_at), _dptr(state), _dptr(gt_boxes),
+                                            _dptr(gt_counts), _dptr(gt_flags), gcap, B, C, n_thr, _dptr(r["rank"]), _dptr(r["ctp"]),
+                                            _dptr(r["ngt"]), _dptr(r["ndet"]), _dptr(r["ntp"])), "dt_detect_rank")
+        return r
+
+    def detect_score(self, det_boxes, det_counts, gt_boxes, gt_counts, nb_class, thresholds=(0.5,), gt_flags=None, score_at=6):
+        """detect_match, then detect_rank on its states: the union of both dicts, plus `scores` and `labels` [B,cap] (floats score_at
+        and 5 of det_boxes, as views) -- what utility.evaluate.average_precision / precision_recall take."""
+        r = self.detect_match(det_boxes, det_counts, gt_boxes, gt_counts, nb_class, thresholds, gt_flags, score_at)
+        r.update(self.detect_rank(det_boxes, det_counts, r["state"], gt_boxes, gt_counts, nb_class, gt_flags, score_at))
+        r["scores"], r["labels"] = det_boxes[:, :, int(score_at)], det_boxes[:, :, 5]
         return r
 
     def pack_detections(self, boxes, counts, ids, nids, n_rows):

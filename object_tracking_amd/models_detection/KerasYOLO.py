@@ -236,6 +236,20 @@ class KerasYOLO(object):
             r["affine"] = affine
         return r
 
+    def score(self, result, gt, thresholds=(0.5,), score_at=6):
+        """Score a detect() result against ground truth on the device (mi355_dt.Context.detect_score; the rule: DESIGN.md "Detection
+        scoring").  gt = (gt_boxes [B,gcap,8], gt_counts [B][, gt_flags [B,gcap]]), numpy or device tensors
+        (utility.evaluate.gt_from_annotations builds them from parse_annotation records); flag bit 0 marks a row to ignore.
+        thresholds: 1..16 IoU thresholds (utility.evaluate.COCO_THRESHOLDS for .50:.05:.95); score_at: 6 ranks by the box's score,
+        4 by its conf.  utility.evaluate.average_precision gives AP / mAP of the return."""
+        import torch
+        ctx = self.model.ctx
+        dev = lambda a, dt: (a if torch.is_tensor(a) else torch.from_numpy(np.ascontiguousarray(a))).to(device=ctx.device, dtype=dt).contiguous()
+        gb, gc = dev(gt[0], torch.float32), dev(gt[1], torch.int32)
+        gf = dev(gt[2], torch.int32) if len(gt) > 2 and gt[2] is not None else None
+        return ctx.detect_score(result["boxes"], result["counts"], gb, gc, len(self.LABELS), thresholds=thresholds, gt_flags=gf,
+                                score_at=score_at)
+
     def predict(self, input_path, output_path):
         """KerasYOLO.py:522-537; additionally returns the box list."""
         image, frame = self._frame(input_path)

@@ -1,7 +1,9 @@
-"""Track scoring on the host side: MOT ground truth in, CLEAR-MOT figures out ("Track scoring").
+"""Scoring on the host side ("Track scoring" and "Detection scoring"): MOT ground truth in, CLEAR-MOT
+figures out; annotation records in, per-class average precision out.
 
-The counting itself runs on the device (mi355_dt.Context.track_score / dt_track_score).  This module only prepares its input
-from MOT `gt.txt` text and turns its integer output into the usual figures; nothing here touches the GPU.
+The counting itself runs on the device (mi355_dt.Context.track_score / dt_track_score; Context.detect_score / dt_detect_match,
+dt_detect_rank).  This module only prepares its input and turns its integer output into the usual figures, in float64; nothing
+here touches the GPU.
 """
 import numpy as np
 
@@ -91,3 +93,111 @@ def gt_from_mot(lines, width, height, T, gcap, classes=None):
         ids[t, k] = ident
         counts[t] = k + 1
     return boxes, counts, ids
+
+
+# ---------------------------------------------------------------------------------------------------------------- detection scoring
+COCO_THRESHOLDS = tuple(0.5 + 0.05 * i for i in range(10))      # .50:.05:.95
+AP_METHODS = ("area", "voc11", "coco101")
+
+
+def _curves(result):
+    """-> (rank, ctp [n_thr, M], class per flat row [M] with -1 where the label takes no part, ngt [NC], ndet [n_thr, NC])"""
+    rank, ctp = _host(result["rank"]), _host(result["ctp"])
+    n_thr = rank.shape[0]
+    ngt, ndet = _host(result["ngt"]).astype(np.int64), _host(result["ndet"]).astype(np.int64)
+    lab = _host(result["labels"]).astype(np.float64).reshape(-1)
+    ok = (lab >= 0) & (lab < ngt.shape[0]) & (lab == np.floor(lab))
+    cls = np.where(ok, lab, -1).astype(np.int64)
+    return rank.reshape(n_thr, -1), ctp.reshape(n_thr, -1), cls, ngt, ndet
+
+
+def _curve(rank_k, ctp_k, cls, c, n):
+    """the cumulative TP counts of class c in rank order"""
+    sel = (rank_k >= 0) & (cls == c)
+    out = np.zeros(n, dtype=np.float64)
+    out[rank_k[sel]] = ctp_k[sel]
+    return out, sel
+
+
+def _ap(ctp, ngt, method):
+    if ngt == 0:
+        return float("nan")
+    n = ctp.shape[0]
+    if n == 0:
+        return 0.0
+    p = ctp / np.arange(1, n + 1, dtype=np.float64)
+    r = ctp / float(ngt)
+    if method == "area":
+        env = np.maximum.accumulate(p[::-1])[::-1]
+        return float(np.sum((r - np.concatenate([[0.0], r[:-1]])) * env))
+    steps = {"voc11": 10, "coco101": 100}[method]
+    env = np.maximum.accumulate(p[::-1])[::-1]                 # r does not decrease along the curve: max{p_j : r_j >= t} = env at the first such j
+    t = np.arange(steps + 1, dtype=np.float64) / float(steps)
+    first = np.searchsorted(r, t, side="left")
+    vals = np.where(first < n, env[np.minimum(first, n - 1)], 0.0)
+    return float(np.sum(vals) / float(steps + 1))
+
+
+def average_precision(result, method="area"):
+    """A Context.detect_score result (device tensors or arrays: rank, ctp, ngt, ndet, ntp, labels, thresholds) -> dict:
+      ap          [n_thr, NC] float64: the AP of class c at threshold k; nan where the class has no ground truth (ngt = 0), 0 where
+                  it has ground truth and no ranked detection
+      map         [n_thr]: the mean over the classes with ground truth (nan without one);  map_all: the mean of map over the
+                  thresholds -- COCO's mAP when the thresholds are COCO_THRESHOLDS
+      ngt [NC], ndet, ntp [n_thr, NC], thresholds
+    For threshold k and class c the curve has n = ndet points, p_j = ctp_j / (j + 1), r_j = ctp_j / ngt, j in rank order.
+    method: "area" (VOC2010+): sum_j (r_j - r_{j-1}) * max_{j' >= j} p_j';  "voc11": the mean over t = i / 10, i = 0..10, of
+    max{p_j : r_j >= t} (0 where there is none);  "coco101": the same over t = i / 100, i = 0..100."""
+    if method not in AP_METHODS:
+        raise ValueError("method must be one of %s" % (AP_METHODS,))
+    rank, ctp, cls, ngt, ndet = _curves(result)
+    n_thr, NC = rank.shape[0], ngt.shape[0]
+    ap = np.full((n_thr, NC), np.nan, dtype=np.float64)
+    for k in range(n_thr):
+        for c in range(NC):
+            if ngt[c] > 0:
+                ap[k, c] = _ap(_curve(rank[k], ctp[k], cls, c, int(ndet[k, c]))[0], int(ngt[c]), method)
+    have = ngt > 0
+    m = ap[:, have].mean(axis=1) if have.any() else np.full(n_thr, np.nan)
+    return dict(ap=ap, map=m, map_all=float(m.mean()) if have.any() else float("nan"), ngt=ngt, ndet=ndet,
+                ntp=_host(result["ntp"]).astype(np.int64), thresholds=np.asarray(_host(result["thresholds"]), dtype=np.float64))
+
+
+def precision_recall(result, k, c):
+    """The curve of class c at threshold index k, in rank order -> dict(precision, recall [n] float64 (recall nan when the class has no
+    ground truth), scores [n] float32 (the ranking score of the detection at each rank), tp [n] int64 (cumulative))."""
+    rank, ctp, cls, ngt, ndet = _curves(result)
+    n = int(ndet[k, c])
+    cum, sel = _curve(rank[k], ctp[k], cls, c, n)
+    scores = np.zeros(n, dtype=np.float32)
+    scores[rank[k][sel]] = _host(result["scores"]).reshape(-1)[sel]
+    with np.errstate(divide="ignore", invalid="ignore"):
+        recall = cum / float(ngt[c]) if ngt[c] > 0 else np.full(n, np.nan)
+    return dict(precision=cum / np.arange(1, n + 1, dtype=np.float64), recall=recall, scores=scores, tp=cum.astype(np.int64))
+
+
+def gt_from_annotations(records, labels, gcap):
+    """utility.preprocessing.parse_annotation records -> (gt_boxes [B, gcap, 8] float32, gt_counts [B] int32, gt_flags [B, gcap] int32),
+    one frame per record, for Context.detect_score / KerasYOLO.score.
+    A record: dict(width, height, object=[dict(name, xmin, ymin, xmax, ymax[, difficult])]).  A box becomes x, y = its centre and
+    w, h, each divided by the record's width / height; float 4 is 1, float 5 the index of `name` in `labels`, float 6 is 1.
+    Objects whose name is not in `labels` are dropped; a true 'difficult' key sets bit 0 of the flag (the row is ignored in scoring).
+    More than gcap objects in a record is an error."""
+    B = len(records)
+    boxes = np.zeros((B, gcap, DT_BOX_FLOATS), dtype=np.float32)
+    counts = np.zeros(B, dtype=np.int32)
+    flags = np.zeros((B, gcap), dtype=np.int32)
+    index = {name: i for i, name in enumerate(labels)}
+    for b, rec in enumerate(records):
+        W, H = float(rec["width"]), float(rec["height"])
+        for o in rec["object"]:
+            if o["name"] not in index:
+                continue
+            k = int(counts[b])
+            if k >= gcap:
+                raise ValueError("record %d holds more than gcap = %d objects" % (b, gcap))
+            x0, y0, x1, y1 = float(o["xmin"]), float(o["ymin"]), float(o["xmax"]), float(o["ymax"])
+            boxes[b, k] = [(x0 + x1) / 2.0 / W, (y0 + y1) / 2.0 / H, (x1 - x0) / W, (y1 - y0) / H, 1.0, index[o["name"]], 1.0, 0.0]
+            flags[b, k] = 1 if int(o.get("difficult", 0)) else 0
+            counts[b] = k + 1
+    return boxes, counts, flags
