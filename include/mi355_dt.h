@@ -52,6 +52,8 @@ extern "C" {
                                *     last appearance matched (0/1), 0 */
 #define DT_SCORE_ANY_LABEL 1  /* ... flag bit: labels are not compared */
 #define DT_SCORE_RESUME 2     /* ... flag bit: d_totals, d_objs, d_nobjs are in-out and the call continues from them */
+#define DT_IDENT_INTS 8       /* identity scoring sizes of a clip (dt_identity_overlap): frames, gt boxes, hyp boxes, gt trajectories, hyp trajectories,
+                               *     gt overflow boxes, hyp overflow boxes, valid pairs */
 
 typedef struct dt_ctx dt_ctx;
 
@@ -70,6 +72,7 @@ DT_API int dt_set_stream(dt_ctx *ctx, void *hip_stream);
  * and the four frame-view entries dt_view_fit, dt_view_affine, dt_ingest_views, dt_boxes_map
  * and the one track scoring entry dt_track_score
  * and the two detection scoring entries dt_detect_match, dt_detect_rank
+ * and the two identity scoring entries dt_identity_overlap, dt_assign_max
  * -- additions only, the number stayed; 1.07: 1.06 + dt_gemm_split, dt_policy_set) */
 DT_API int dt_abi_version(void);
 
@@ -348,7 +351,7 @@ DT_API int dt_associate_tracks(dt_ctx *ctx, const float *d_boxes, const int *d_c
  * that does not depend on the order in which the frame's boxes arrive, ties apart.  Then the boxes that claimed nothing open new ids
  * in decode order; whenever both orders find the same pairs every output is the same bit for bit.  A box that claims an entry of another
  * label carries on its id, hits and velocity; the rebuilt entry has the box's label.
- * Not done here: an optimal (Hungarian) assignment, a cost other than IoU.
+ * Not done here: an optimal (Hungarian) assignment (dt_assign_max is one, not yet behind this match), a cost other than IoU.
  * DT_ERR_ARG: as dt_associate_tracks, and match outside 0..3.  With DT_MATCH_BEST_FIRST the LDS also holds three words per box (best
  * candidate key, its entry, claimed), 20 * tcap + 4 * cap words in all: tcap = cap fits up to 1706 (1950 without the bit); a table
  * with tcap <= 64 and T <= 64 runs in registers and keeps only the frame's keys, 256 * cap bytes, in the LDS. */
@@ -392,8 +395,8 @@ DT_API int dt_associate_tracks_match(dt_ctx *ctx, const float *d_boxes, const in
  * d_nobjs on are zero with -1 in the gt id and last track id fields.  With it the three are in-out and the call continues from them:
  * chunks of any sizes along T give every output of the one call on the concatenation, bit for bit -- the contract of the stream entries,
  * with the state owned by the caller (no slot table).  Asynchronous on the context's stream; n_clips = 0 is a no-op.
- * Not done here: an optimal (Hungarian) assignment, IDF1 / HOTA, ignore regions and visibility weighting, dropping coasting rows.
- * (Detector AP: dt_detect_match / dt_detect_rank below.)
+ * Not done here: an optimal (Hungarian) assignment in the frame step (dt_assign_max is one; IDF1: dt_identity_overlap below), HOTA,
+ * ignore regions and visibility weighting, dropping coasting rows.  (Detector AP: dt_detect_match / dt_detect_rank below.)
  * DT_ERR_ARG (nothing launched): a NULL required pointer, n_clips < 0, T, gcap, hcap or ocap <= 0, id_stride < 1, hyp_label_at outside
  * 0..7, unknown flag bits, one of d_match / d_miou without the other, a threshold that is NaN or outside (0, 1], or a table and frame
  * that do not fit the 160 KB of LDS: 8 * ocap + 11 * gcap + 7 * hcap words must not exceed 40960 (gcap = hcap = 128: ocap up to 4832). */
@@ -401,6 +404,57 @@ DT_API int dt_track_score(dt_ctx *ctx, const float *d_gt_boxes, const int *d_gt_
                  const float *d_hyp_boxes, const int *d_hyp_counts, const int *d_hyp_ids, int hcap, int id_stride, int hyp_label_at,
                  int n_clips, int T, float iou_threshold, int flags, int ocap,
                  int *d_totals, int *d_objs, int *d_nobjs, int *d_fcounts, int *d_match, float *d_miou);
+
+/* Identity scoring (BUILD-DEFINED, DESIGN.md "Identity scoring"): IDF1 (Ristani et al. 2016) of a tracker's output against ground-truth
+ * tracks.  Two entries: the overlap of ground-truth trajectories with hypothesis trajectories over a clip, then an exact one-to-one
+ * assignment of maximum weight on it, whose total is IDTP.  IDFN = gt boxes - IDTP, IDFP = hyp boxes - IDTP (the paper's minimum-cost
+ * formulation with its dummy nodes removed); IDP = IDTP / hyp, IDR = IDTP / gt, IDF1 = 2 IDTP / (gt + hyp) are taken on the host in float64
+ * (Python: utility.evaluate.identity).  No float is summed on the device.
+ *
+ * dt_identity_overlap: the input arguments, d_gt_boxes .. iou_threshold and flags, are dt_track_score's, bit for bit, DT_SCORE_ANY_LABEL and
+ * DT_SCORE_RESUME included -- so an association result and the confirmed-track read-out are scored by the same entry.  Clips are scored
+ * independently, one wavefront each, frames in sequence.
+ * TRAJECTORIES: a clip has a ground-truth table of at most acap rows, one per distinct ground-truth id >= 0 in order of first appearance
+ * (within a frame: row order), and a hypothesis table of at most bcap rows built the same way from the hypothesis ids >= 0; a row holds the
+ * id and its number of boxes.  A box whose id is < 0, or whose id finds its table full, has no trajectory: it counts in the box totals and,
+ * in the full-table case, in that side's overflow count, and takes no part in the overlap.
+ * OVERLAP: n[a][b] = the valid row pairs (g, i) over all frames with g of ground-truth trajectory a and i of hypothesis trajectory b; valid
+ * is dt_track_score's definition: bbox_iou(gt box g, hyp box i) >= iou_threshold as float32, and equal labels as floats unless
+ * DT_SCORE_ANY_LABEL.  Nothing is claimed and nothing is carried over: every valid pair of a frame counts (with distinct ids inside a
+ * frame at most one per frame and trajectory pair; repeated ids add).
+ *   d_sizes   [n_clips, DT_IDENT_INTS] int32   frames, gt boxes, hyp boxes, gt trajectories, hyp trajectories, gt overflow boxes, hyp overflow
+ *             boxes, valid pairs (those counted into d_overlap: its sum)
+ *   d_gt_tab  [n_clips, acap, 2] int32, d_hyp_tab [n_clips, bcap, 2] int32   id, boxes; unused rows are (-1, 0)
+ *   d_overlap [n_clips, acap, bcap] int32
+ * Without DT_SCORE_RESUME every word of the four is written and the buffers may arrive uninitialised.  With it they are in-out: chunks of
+ * any sizes along T give the outputs of one call on the concatenation, bit for bit.  Asynchronous on the context's stream; n_clips = 0 is
+ * a no-op.
+ * DT_ERR_ARG (nothing launched, nothing written): a NULL pointer, n_clips < 0, T, gcap, hcap, acap or bcap <= 0, id_stride < 1, hyp_label_at
+ * outside 0..7, unknown flag bits, a threshold that is NaN or outside (0, 1], n_clips * acap * bcap >= 2^31, or a frame and tables that
+ * do not fit the 160 KB of LDS: 2 * acap + 2 * bcap + 7 * gcap + 7 * hcap words must not exceed 40960 (gcap = hcap = 128: acap + bcap up
+ * to 19584).
+ *
+ * dt_assign_max: n independent problems, one wavefront each.  Problem k has rows = d_dims[k * stride + rows_at] and cols = d_dims[k * stride
+ * + cols_at], clamped to [0, rcap] and [0, ccap] (d_sizes of dt_identity_overlap is passed as it is, with stride DT_IDENT_INTS, rows_at 3,
+ * cols_at 4), and the weights d_w[k][r][c], r < rows, c < cols, of d_w [n, rcap, ccap] int32.  It finds a one-to-one assignment of rows to
+ * columns that maximises the sum of the chosen weights, by the shortest-augmenting-path Hungarian method with integer potentials (exact;
+ * no float), solved on the orientation whose row count is the smaller.
+ *   d_row_to_col [n, rcap] int32, d_col_to_row [n, ccap] int32   the partner, or -1: a pair whose weight is 0 is reported as unassigned, and
+ *             so are rows and columns beyond the counts
+ *   d_total      [n] int64                                        the sum of the chosen weights (IDTP on an overlap matrix)
+ * Every word of the three is written.  Weights must lie in [0, 2^24]; outside that the result is unspecified, but the call still
+ * terminates and stays in bounds.  Which of several optimal assignments is reported is fixed by the method as DESIGN.md states it step
+ * by step (ties to the lowest column); two runs give identical bits.  Asynchronous on the context's stream; n = 0 is a no-op.
+ * DT_ERR_ARG (nothing launched, nothing written): a NULL pointer, n < 0, rcap or ccap <= 0, rows_at or cols_at outside 0..stride-1,
+ * n * rcap * ccap >= 2^31, or work arrays that do not fit the 160 KB of LDS: 6 * (max(rcap, ccap) + 1) words must not exceed 40960
+ * (caps up to 6825).
+ * Not done here: HOTA, ignore regions, this solver behind the tracker's own match (dt_associate_tracks_match). */
+DT_API int dt_identity_overlap(dt_ctx *ctx, const float *d_gt_boxes, const int *d_gt_counts, const int *d_gt_ids, int gcap,
+                 const float *d_hyp_boxes, const int *d_hyp_counts, const int *d_hyp_ids, int hcap, int id_stride, int hyp_label_at,
+                 int n_clips, int T, float iou_threshold, int flags, int acap, int bcap,
+                 int *d_sizes, int *d_gt_tab, int *d_hyp_tab, int *d_overlap);
+DT_API int dt_assign_max(dt_ctx *ctx, const int *d_w, int rcap, int ccap, const int *d_dims, int stride, int rows_at, int cols_at, int n,
+                 int *d_row_to_col, int *d_col_to_row, int64_t *d_total);
 
 /* Detection scoring (BUILD-DEFINED, DESIGN.md "Detection scoring"): per-class average precision of a detector's boxes against ground truth,
  * by the VOC devkit's match.  Two entries: the match of every frame, then the position of every detection in its class's score order over

@@ -430,6 +430,36 @@ size_t track_score_lds_bytes(int gcap, int hcap, int ocap);      // dynamic LDS 
 // 0: launched; 1: device error.  flags: DT_SCORE_* bits.  The arguments are dt_track_score's, validated there (n_clips > 0, the LDS fits).
 int launch_track_score(hipStream_t st, const ScoreArgs &a, int n_clips, int flags);
 
+// identity scoring (identity.hip, DESIGN.md "Identity scoring"): the overlap of ground-truth trajectories with hypothesis trajectories,
+// one wavefront per clip, and an exact integer maximum-weight assignment, one wavefront per problem.  The inputs are ScoreArgs'.
+struct IdentArgs {
+    const float *gt_boxes;   // [n][T][gcap][DT_BOX_FLOATS]
+    const int *gt_counts;    // [n][T]
+    const int *gt_ids;       // [n][T][gcap]
+    const float *hyp_boxes;  // [n][T][hcap][8]
+    const int *hyp_counts;   // [n][T]
+    const int *hyp_ids;      // [n][T][hcap][id_stride], the id in word 0
+    int gcap, hcap, id_stride, label_at, T, acap, bcap;
+    float thr;
+    int *sizes;              // [n][DT_IDENT_INTS]
+    int *gt_tab;             // [n][acap][2]
+    int *hyp_tab;            // [n][bcap][2]
+    int *overlap;            // [n][acap][bcap]
+};
+size_t identity_overlap_lds_bytes(int gcap, int hcap, int acap, int bcap);      // dt_identity_overlap refuses more than 160 KB
+// 0: launched; 1: device error.  flags: DT_SCORE_* bits; without DT_SCORE_RESUME the overlap is zeroed on the stream first.
+int launch_identity_overlap(hipStream_t st, const IdentArgs &a, int n_clips, int flags);
+struct AssignArgs {
+    const int *w;            // [n][rcap][ccap]
+    const int *dims;         // [n][stride], rows in word rows_at, columns in word cols_at
+    int rcap, ccap, stride, rows_at, cols_at;
+    int *row_to_col;         // [n][rcap]
+    int *col_to_row;         // [n][ccap]
+    long long *total;        // [n]
+};
+size_t assign_max_lds_bytes(int rcap, int ccap);                                // dt_assign_max refuses more than 160 KB
+int launch_assign_max(hipStream_t st, const AssignArgs &a, int n);              // 0: launched; 1: device error
+
 // detection scoring (detscore.hip, DESIGN.md "Detection scoring"): the VOC match of detections against ground truth per frame, then the
 // position of every detection in its class's score order over all frames.  Integers out; the ratios are taken on the host.
 #define DT_DETSCORE_MAX_THR 16

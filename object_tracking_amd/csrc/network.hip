@@ -1926,6 +1926,49 @@ extern "C" int dt_track_score(dt_ctx *ctx, const float *d_gt_boxes, const int *d
     return DT_OK;
 }
 
+// identity scoring (DESIGN.md "Identity scoring"): the overlap of ground-truth with hypothesis trajectories; dt_assign_max on it gives IDTP
+extern "C" int dt_identity_overlap(dt_ctx *ctx, const float *d_gt_boxes, const int *d_gt_counts, const int *d_gt_ids, int gcap,
+                                   const float *d_hyp_boxes, const int *d_hyp_counts, const int *d_hyp_ids, int hcap, int id_stride,
+                                   int hyp_label_at, int n_clips, int T, float iou_threshold, int flags, int acap, int bcap, int *d_sizes,
+                                   int *d_gt_tab, int *d_hyp_tab, int *d_overlap)
+{
+    if (!ctx || !d_gt_boxes || !d_gt_counts || !d_gt_ids || !d_hyp_boxes || !d_hyp_counts || !d_hyp_ids || !d_sizes || !d_gt_tab || !d_hyp_tab ||
+        !d_overlap)
+        return dt_fail(ctx, DT_ERR_ARG, "null argument");
+    if (n_clips < 0 || T <= 0 || gcap <= 0 || hcap <= 0 || acap <= 0 || bcap <= 0)
+        return dt_fail(ctx, DT_ERR_ARG, "n_clips must not be negative; T, gcap, hcap, acap and bcap must be positive");
+    if (id_stride < 1) return dt_fail(ctx, DT_ERR_ARG, "id_stride must be at least 1");
+    if (hyp_label_at < 0 || hyp_label_at > 7) return dt_fail(ctx, DT_ERR_ARG, "hyp_label_at must be in 0..7");
+    if (flags & ~(DT_SCORE_ANY_LABEL | DT_SCORE_RESUME)) return dt_fail(ctx, DT_ERR_ARG, "flags must be a combination of DT_SCORE_ANY_LABEL and DT_SCORE_RESUME");
+    if (!(iou_threshold > 0.0f && iou_threshold <= 1.0f)) return dt_fail(ctx, DT_ERR_ARG, "the IoU threshold must be in (0, 1]");
+    if ((long long)n_clips * acap * bcap >= (1ll << 31)) return dt_fail(ctx, DT_ERR_ARG, "n_clips * acap * bcap must be below 2^31");
+    if (identity_overlap_lds_bytes(gcap, hcap, acap, bcap) > (size_t)160 * 1024)
+        return dt_fail(ctx, DT_ERR_ARG, "2 * acap + 2 * bcap + 7 * gcap + 7 * hcap words do not fit the 160 KB of LDS");
+    if (n_clips == 0) return DT_OK;
+    ProfScope ps(ctx, "associate", 0.0, 4.0 * n_clips * ((double)T * (gcap * 6.0 + hcap * (6.0 + id_stride)) + (acap + bcap) * 2.0 + (double)acap * bcap),
+                 "identity_overlap");
+    IdentArgs a{d_gt_boxes, d_gt_counts, d_gt_ids, d_hyp_boxes, d_hyp_counts, d_hyp_ids, gcap, hcap, id_stride, hyp_label_at, T, acap, bcap,
+                iou_threshold, d_sizes, d_gt_tab, d_hyp_tab, d_overlap};
+    if (launch_identity_overlap(ctx->stream, a, n_clips, flags)) return dt_fail(ctx, DT_ERR_DEVICE, "identity overlap launch failed");
+    return DT_OK;
+}
+
+extern "C" int dt_assign_max(dt_ctx *ctx, const int *d_w, int rcap, int ccap, const int *d_dims, int stride, int rows_at, int cols_at, int n,
+                             int *d_row_to_col, int *d_col_to_row, int64_t *d_total)
+{
+    if (!ctx || !d_w || !d_dims || !d_row_to_col || !d_col_to_row || !d_total) return dt_fail(ctx, DT_ERR_ARG, "null argument");
+    if (n < 0 || rcap <= 0 || ccap <= 0) return dt_fail(ctx, DT_ERR_ARG, "n must not be negative; rcap and ccap must be positive");
+    if (rows_at < 0 || rows_at >= stride || cols_at < 0 || cols_at >= stride) return dt_fail(ctx, DT_ERR_ARG, "rows_at and cols_at must lie inside the stride");
+    if ((long long)n * rcap * ccap >= (1ll << 31)) return dt_fail(ctx, DT_ERR_ARG, "n * rcap * ccap must be below 2^31");
+    if (assign_max_lds_bytes(rcap, ccap) > (size_t)160 * 1024)
+        return dt_fail(ctx, DT_ERR_ARG, "6 * (max(rcap, ccap) + 1) words do not fit the 160 KB of LDS");
+    if (n == 0) return DT_OK;
+    ProfScope ps(ctx, "associate", 0.0, 4.0 * n * ((double)rcap * ccap + rcap + ccap + 2.0), "assign_max");
+    AssignArgs a{d_w, d_dims, rcap, ccap, stride, rows_at, cols_at, d_row_to_col, d_col_to_row, reinterpret_cast<long long *>(d_total)};
+    if (launch_assign_max(ctx->stream, a, n)) return dt_fail(ctx, DT_ERR_DEVICE, "assign max launch failed");
+    return DT_OK;
+}
+
 // detection scoring (DESIGN.md "Detection scoring"): the VOC match per frame, then every detection's position in its class's score order
 static const char *detect_score_args(const void *det_boxes, const void *det_counts, int cap, int score_at, const void *gt_boxes,
                                      const void *gt_counts, int gcap, int B, int NC, int n_thr)

@@ -27,6 +27,7 @@ DT_SCORE_INTS = 8        # track scoring totals (dt_track_score): frames, gt box
 DT_SCORE_OBJ_INTS = 8    # ... an object row: gt id, last track id, present, matched, switches, fragments, last appearance matched, 0
 DT_SCORE_ANY_LABEL = 1   # ... flag bits: labels not compared
 DT_SCORE_RESUME = 2      # ... totals / objs / nobjs are in-out, the call continues from them
+DT_IDENT_INTS = 8        # identity scoring sizes (dt_identity_overlap): frames, gt boxes, hyp boxes, gt / hyp trajectories, gt / hyp overflow, valid pairs
 DT_PIX_RGB24 = 0         # pixel formats of dt_frame_desc (dt_ingest_frames): 3 interleaved bytes per pixel, as they lie
 DT_PIX_NV12 = 1          # ... plane0 = Y, plane1 = U,V interleaved, one pair per 2x2 pixels
 DT_PIX_SWAP_RB = 16      # ... flag: output channels 0 and 2 exchanged
@@ -54,6 +55,7 @@ SYMBOLS = [
     "dt_view_fit", "dt_view_affine", "dt_ingest_views", "dt_boxes_map",
     "dt_track_score",
     "dt_detect_match", "dt_detect_rank",
+    "dt_identity_overlap", "dt_assign_max",
 ]
 
 _lib = None
@@ -128,6 +130,8 @@ def load_library():
     L.dt_associate_tracks_match.argtypes = [vp, vp, vp, ci, ci, ci, cf, ci, ci, cf, ci, ci, vp, vp, vp, vp, vp, vp, vp]
     L.dt_associate_stream_tracks_match.argtypes = [vp, vp, vp, ci, ci, ci, cf, ci, cf, ci, ci, ctypes.POINTER(ci), vp, vp, vp, vp, vp, vp, vp]
     L.dt_track_score.argtypes = [vp, vp, vp, vp, ci, vp, vp, vp, ci, ci, ci, ci, ci, cf, ci, ci, vp, vp, vp, vp, vp, vp]
+    L.dt_identity_overlap.argtypes = [vp, vp, vp, vp, ci, vp, vp, vp, ci, ci, ci, ci, ci, cf, ci, ci, ci, vp, vp, vp, vp]
+    L.dt_assign_max.argtypes = [vp, vp, ci, ci, vp, ci, ci, ci, ci, vp, vp, vp]
     L.dt_detect_match.argtypes = [vp, vp, vp, ci, ci, vp, vp, vp, ci, ci, ci, vp, ci, vp, vp, vp]
     L.dt_detect_rank.argtypes = [vp, vp, vp, ci, ci, vp, vp, vp, vp, ci, ci, ci, ci, vp, vp, vp, vp, vp]
     L.dt_track_row_width.argtypes = [vp]
@@ -615,6 +619,79 @@ class Context(object):
                                             _dptr(hyp_ids), hcap, stride, label_at, n, T, float(iou_threshold), flags, ocap, _dptr(totals),
                                             _dptr(objs), _dptr(nobjs), _dptr(r["frame_counts"]), _dptr(r["match"]), _dptr(r["miou"])),
                     "dt_track_score")
+        return r
+
+    def identity_overlap(self, gt_boxes, gt_counts, gt_ids, hyp_boxes, hyp_counts, hyp_ids, iou_threshold=0.5, any_label=False, gt_cap=None,
+                         hyp_cap=None, state=None):
+        """The overlap of ground-truth trajectories with hypothesis trajectories (dt_identity_overlap; the rule: DESIGN.md "Identity
+        scoring").  The six inputs, iou_threshold and any_label are track_score's.
+        -> dict: sizes [n,8] (frames, gt boxes, hyp boxes, gt trajectories, hyp trajectories, gt overflow boxes, hyp overflow boxes,
+        valid pairs), gt_tab [n,gt_cap,2] and hyp_tab [n,hyp_cap,2] (id, boxes; unused rows -1, 0), overlap [n,gt_cap,hyp_cap] int32.
+        gt_cap / hyp_cap: rows of the two tables (None: the state's, or max(64, 2 * gcap) / max(64, 2 * hcap)); boxes of ids beyond
+        them are counted as overflow and take no part.  state: a previous result this call continues (copied, not written): chunks of
+        any sizes along T give the result of one call on the concatenation."""
+        t = self.torch
+        i32 = lambda *shape: t.empty(shape, dtype=t.int32, device=self.device)
+        n, T, gcap, _ = gt_boxes.shape
+        hcap = hyp_boxes.shape[2]
+        assert hyp_boxes.shape[:2] == (n, T) and hyp_boxes.shape[3] == 8 and gt_boxes.shape[3] == DT_BOX_FLOATS
+        if hyp_ids.dim() == 4:
+            stride, label_at = int(hyp_ids.shape[3]), 4
+        else:
+            stride, label_at = 1, 5
+        assert tuple(hyp_ids.shape[:3]) == (n, T, hcap) and tuple(gt_ids.shape) == (n, T, gcap)
+        assert tuple(gt_counts.shape) == (n, T) and tuple(hyp_counts.shape) == (n, T)
+        for x, dt in ((gt_boxes, t.float32), (hyp_boxes, t.float32), (gt_counts, t.int32), (gt_ids, t.int32), (hyp_counts, t.int32),
+                      (hyp_ids, t.int32)):
+            assert x.is_cuda and x.is_contiguous() and x.dtype == dt
+        flags = DT_SCORE_ANY_LABEL if any_label else 0
+        if state is not None:
+            acap, bcap = int(state["gt_tab"].shape[1]), int(state["hyp_tab"].shape[1])
+            assert gt_cap is None or int(gt_cap) == acap, "gt_cap differs from the state's"
+            assert hyp_cap is None or int(hyp_cap) == bcap, "hyp_cap differs from the state's"
+            assert int(state["sizes"].shape[0]) == n and tuple(state["overlap"].shape) == (n, acap, bcap)
+            r = {k: state[k].clone() for k in ("sizes", "gt_tab", "hyp_tab", "overlap")}
+            flags |= DT_SCORE_RESUME
+        else:
+            acap = max(64, 2 * gcap) if gt_cap is None else int(gt_cap)
+            bcap = max(64, 2 * hcap) if hyp_cap is None else int(hyp_cap)
+            r = dict(sizes=i32(n, DT_IDENT_INTS), gt_tab=i32(n, max(acap, 0), 2), hyp_tab=i32(n, max(bcap, 0), 2),
+                     overlap=i32(n, max(acap, 0), max(bcap, 0)))
+        self._sync_stream()
+        self._check(self.lib.dt_identity_overlap(self.h, _dptr(gt_boxes), _dptr(gt_counts), _dptr(gt_ids), gcap, _dptr(hyp_boxes),
+                                                 _dptr(hyp_counts), _dptr(hyp_ids), hcap, stride, label_at, n, T, float(iou_threshold), flags,
+                                                 acap, bcap, _dptr(r["sizes"]), _dptr(r["gt_tab"]), _dptr(r["hyp_tab"]), _dptr(r["overlap"])),
+                    "dt_identity_overlap")
+        return r
+
+    def assign_max(self, weights, dims=None, rows_at=0, cols_at=1):
+        """An exact one-to-one assignment of maximum total weight per problem (dt_assign_max; DESIGN.md "Identity scoring").
+        weights [n,rcap,ccap] int32 on the device, each in [0, 2^24]; dims [n,k] int32 with the rows and columns in use of problem i
+        in words rows_at and cols_at (None: every problem is rcap x ccap).
+        -> (row_to_col [n,rcap] int32, col_to_row [n,ccap] int32, total [n] int64): the partner or -1 -- a pair of weight 0 is
+        reported as unassigned -- and the sum of the chosen weights."""
+        t = self.torch
+        n, rcap, ccap = weights.shape
+        assert weights.is_cuda and weights.is_contiguous() and weights.dtype == t.int32
+        if dims is None:
+            dims = t.tensor([[rcap, ccap]], dtype=t.int32, device=self.device).repeat(n, 1).contiguous()
+            rows_at, cols_at = 0, 1
+        assert dims.dim() == 2 and int(dims.shape[0]) == n and dims.is_cuda and dims.is_contiguous() and dims.dtype == t.int32
+        r2c = t.empty((n, rcap), dtype=t.int32, device=self.device)
+        c2r = t.empty((n, ccap), dtype=t.int32, device=self.device)
+        total = t.empty((n,), dtype=t.int64, device=self.device)
+        self._sync_stream()
+        self._check(self.lib.dt_assign_max(self.h, _dptr(weights), rcap, ccap, _dptr(dims), int(dims.shape[1]), int(rows_at), int(cols_at), n,
+                                           _dptr(r2c), _dptr(c2r), _dptr(total)), "dt_assign_max")
+        return r2c, c2r, total
+
+    def identity_score(self, gt_boxes, gt_counts, gt_ids, hyp_boxes, hyp_counts, hyp_ids, iou_threshold=0.5, any_label=False, gt_cap=None,
+                       hyp_cap=None, state=None):
+        """identity_overlap, then assign_max on its overlap with the trajectory counts of `sizes`: the overlap's dict plus gt_to_hyp
+        [n,gt_cap], hyp_to_gt [n,hyp_cap] (rows of the other table, or -1) and idtp [n] int64.  utility.evaluate.identity turns it
+        into IDF1 etc.  `state` is a previous result (of either method); the assignment is solved anew on the accumulated overlap."""
+        r = self.identity_overlap(gt_boxes, gt_counts, gt_ids, hyp_boxes, hyp_counts, hyp_ids, iou_threshold, any_label, gt_cap, hyp_cap, state)
+        r["gt_to_hyp"], r["hyp_to_gt"], r["idtp"] = self.assign_max(r["overlap"], r["sizes"], 3, 4)
         return r
 
     def _detect_score_inputs(self, det_boxes, det_counts, gt_boxes, gt_counts, gt_flags):

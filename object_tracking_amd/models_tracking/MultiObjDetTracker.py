@@ -371,6 +371,22 @@ class MultiObjDetTracker(object):
         return ctx.track_score(gb, gc, gi, hyp[0], hyp[1], hyp[2], iou_threshold=iou_threshold, any_label=any_label, obj_cap=obj_cap,
                                state=state, per_box=per_box)
 
+    def identity(self, result, gt, confirmed=False, iou_threshold=0.5, any_label=False, state=None):
+        """Identity scoring of a track_clips / track_stream result against ground-truth tracks on the device
+        (mi355_dt.Context.identity_score; the rule: DESIGN.md "Identity scoring"): gt and the choice of hypotheses are score()'s.
+        state: the previous chunk's result, for results of track_stream.  utility.evaluate.identity gives IDF1 etc. of the return."""
+        import torch
+        ctx = self.model.ctx
+        dev = lambda a, dt: (a if torch.is_tensor(a) else torch.from_numpy(np.ascontiguousarray(a))).to(device=ctx.device, dtype=dt).contiguous()
+        gb, gc, gi = dev(gt[0], torch.float32), dev(gt[1], torch.int32), dev(gt[2], torch.int32)
+        if confirmed:
+            if result.get("tracks") is None:
+                raise mi355_dt.NativeError("identity(confirmed=True) needs the track read-out in the result (MIN_HITS)")
+            hyp = (result["tracks"], result["track_counts"], result["track_info"])
+        else:
+            hyp = (result["boxes"], result["counts"], result["ids"])
+        return ctx.identity_score(gb, gc, gi, hyp[0], hyp[1], hyp[2], iou_threshold=iou_threshold, any_label=any_label, state=state)
+
     @staticmethod
     def boxes_from_result(res, clip=0):
         """Host view of track_clips output for one clip: list over t of BoundBox lists."""

@@ -1,8 +1,8 @@
-"""Scoring on the host side ("Track scoring" and "Detection scoring"): MOT ground truth in, CLEAR-MOT
-figures out; annotation records in, per-class average precision out.
+"""Scoring on the host side ("Track scoring", "Identity scoring" and "Detection scoring"): MOT ground truth in,
+CLEAR-MOT and identity figures out; annotation records in, per-class average precision out.
 
-The counting itself runs on the device (mi355_dt.Context.track_score / dt_track_score; Context.detect_score / dt_detect_match,
-dt_detect_rank).  This module only prepares its input and turns its integer output into the usual figures, in float64; nothing
+The counting itself runs on the device (mi355_dt.Context.track_score / dt_track_score; Context.identity_score /
+dt_identity_overlap, dt_assign_max; Context.detect_score / dt_detect_match, dt_detect_rank).  This module only prepares its input and turns its integer output into the usual figures, in float64; nothing
 here touches the GPU.
 """
 import numpy as np
@@ -51,6 +51,27 @@ def summarize(result):
         rows += o
         clips.append(_figures(totals[k], float(sums[k]) if have_iou else None, o))
     pooled = _figures(totals.astype(np.int64).sum(axis=0) if n else np.zeros(8, dtype=np.int64), float(sums.sum()) if have_iou else None, rows)
+    return dict(clips=clips, pooled=pooled)
+
+
+def _identity_figures(idtp, gt, hyp, gt_tracks, hyp_tracks, overflow):
+    nan = float("nan")
+    return dict(idtp=idtp, idfn=gt - idtp, idfp=hyp - idtp, gt=gt, hyp=hyp, gt_tracks=gt_tracks, hyp_tracks=hyp_tracks, overflow=overflow,
+                idp=float(idtp) / float(hyp) if hyp > 0 else nan, idr=float(idtp) / float(gt) if gt > 0 else nan,
+                idf1=2.0 * float(idtp) / float(gt + hyp) if gt + hyp > 0 else nan)
+
+
+def identity(result):
+    """A Context.identity_score result (of a resumed run: its last one; a list's last entry is taken) -> dict(clips=[...], pooled=...).
+    Every entry has idtp, idfn = gt - idtp, idfp = hyp - idtp, gt, hyp (boxes), gt_tracks, hyp_tracks (trajectories), overflow (boxes
+    of either side whose id found its table full: they count in gt / hyp and can never be identity true positives) and
+      idp = idtp / hyp, idr = idtp / gt, idf1 = 2 idtp / (gt + hyp)       in float64; nan where the denominator is 0
+    `pooled` adds the counts of all clips before the ratios are taken."""
+    last = result[-1] if isinstance(result, (list, tuple)) else result
+    sizes, idtp = _host(last["sizes"]).astype(np.int64), _host(last["idtp"]).astype(np.int64)
+    clips = [_identity_figures(int(idtp[k]), int(s[1]), int(s[2]), int(s[3]), int(s[4]), int(s[5] + s[6])) for k, s in enumerate(sizes)]
+    tot = sizes.sum(axis=0) if len(sizes) else np.zeros(8, dtype=np.int64)
+    pooled = _identity_figures(int(idtp.sum()), int(tot[1]), int(tot[2]), int(tot[3]), int(tot[4]), int(tot[5] + tot[6]))
     return dict(clips=clips, pooled=pooled)
 
 
