@@ -334,34 +334,52 @@ struct AssocCarry {
     int *hstamp = nullptr;   // [n_slots] as vstamp, for `hits`: written by the track read-out call alone, so after any other association entry
                              // the two differ and every entry reads as hits = 1
 };
-// track memory (decode.hip:associate_mem_kernel): 2 = argument error, nothing launched (tcap < cap, max_age < 0, a table beyond the LDS, carry.tcap != tcap)
-size_t assoc_mem_lds_bytes(int T, int cap, int tcap);      // dynamic LDS the launch needs; above 160 KB the launcher refuses
-int launch_associate_mem(hipStream_t st, const float *boxes, const int *counts, int n_clips, int T, int cap, float thr,
-                         int max_age, int tcap, int *ids, int *nids, int *gaps /*may be null*/, const AssocCarry &carry);
 int launch_associate_stream(hipStream_t st, const float *boxes, const int *counts, int n_clips, int T, int cap,
                             float thr, int *ids, int *nids, const AssocCarry &carry);
-// track motion (decode.hip:associate_motion_kernel): the track-memory rule with every entry matched at its constant-velocity prediction.
-// 2 = argument error, nothing launched (those of launch_associate_mem, a gain outside [0, 1] or NaN, a stream launch without vel / vstamp)
-size_t assoc_motion_lds_bytes(int T, int cap, int tcap);   // dynamic LDS the launch needs; above 160 KB the launcher refuses
-int launch_associate_motion(hipStream_t st, const float *boxes, const int *counts, int n_clips, int T, int cap, float thr,
-                            int max_age, int tcap, float gain, int *ids, int *nids, int *gaps /*may be null*/, const AssocCarry &carry);
-// track read-out (decode.hip:associate_tracks_kernel): the track-motion rule with a hit count per entry, and the table's confirmed entries
-// (hits >= min_hits) written out once per frame.  tracks / tinfo / tcounts: all three or none.
-// 2 = argument error, nothing launched (those of launch_associate_motion, min_hits < 1, a partial read-out triple, a stream launch without hits / hstamp)
-struct TrackReadout {
+
+// The track table (associate.hip:associate_table_kernel): one kernel at three LEVELS, each of which holds what the one below it
+// holds and compiles none of what the ones above it add.
+//   ASSOC_MEMORY  entries with ages: a lost track keeps its id for up to max_age frames (dt_associate_mem)
+//   ASSOC_MOTION  + a velocity per entry, matched where it predicts the entry (dt_associate_motion); reads and writes vstamp
+//   ASSOC_TRACKS  + a hit count per entry, the read-out of the confirmed entries and the match policies (dt_associate_tracks[_match]);
+//                 reads and writes both stamps
+// (ASSOC_FRAME, the previous-frame rule of associate_kernel, is a level of the host entries only: network.hip:associate_entry.)
+enum { ASSOC_FRAME = 0, ASSOC_MEMORY = 1, ASSOC_MOTION = 2, ASSOC_TRACKS = 3 };
+struct TrackReadout {   // ASSOC_TRACKS only; tracks / tinfo / tcounts: all three or none
     int *hits;          // [n_clips][T][cap] hits of each box's track after its frame, -1 in unused entries; may be null
     float *tracks;      // [n_clips][T][tcap][DT_TRACK_FLOATS]
     int *tinfo;         // [n_clips][T][tcap][DT_TRACK_INTS]
     int *tcounts;       // [n_clips][T]
 };
-// match: the track match policy, DT_MATCH_* bits (0 = decode order within a label); outside 0..3 is an argument error too.  The
-// best-IoU-first order needs LDS of its own: the frame's keys [cap][64] in the register form, three more words per box in the general one.
-size_t assoc_tracks_lds_bytes(int T, int cap, int tcap, int match);   // dynamic LDS the launch needs; above 160 KB the launcher refuses
-int launch_associate_tracks(hipStream_t st, const float *boxes, const int *counts, int n_clips, int T, int cap, float thr,
-                            int max_age, int tcap, float gain, int min_hits, int match, int *ids, int *nids, int *gaps /*may be null*/,
-                            const TrackReadout &out, const AssocCarry &carry);
+struct AssocTableArgs {
+    const float *boxes; // [n_clips][T][cap][DT_BOX_FLOATS]
+    const int *counts;  // [n_clips][T]
+    int T, cap;
+    float thr;
+    int max_age, tcap;
+    float gain;         // from ASSOC_MOTION on
+    int min_hits;       // ASSOC_TRACKS
+    int *ids, *nids;    // [n_clips][T][cap], [n_clips]
+    int *gaps;          // [n_clips][T][cap]; may be null
+    TrackReadout out;
+    AssocCarry carry;   // slots == null: the stateless launch
+    // which instantiation the launcher picks; the kernel gets neither.  The launcher hands the members above to the kernel as its
+    // parameters, one by one: a struct parameter is fetched from the argument segment in other blocks than scalar parameters are, and
+    // at the tracks level (106 SGPRs, some kept in VGPR lanes) that changed where the spills fall.
+    int level;         // ASSOC_MEMORY .. ASSOC_TRACKS
+    int match;          // the track match policy, DT_MATCH_* bits (0 = decode order within a label); non-zero at ASSOC_TRACKS only
+};
+// dynamic LDS the launch needs: none in the register form (tcap <= 64, T <= 64) but the best-IoU-first order's keys [cap][64]; in the
+// general form two tables of 7 / 9 / 10 words per entry, the frame's gaps, and three more words per box for the best-IoU-first order
+size_t assoc_table_lds_bytes(int level, int T, int cap, int tcap, int match);
+// 0: launched (or, n_clips <= 0, nothing to launch); 1: device error; 2: argument error, nothing launched -- T or cap < 1, tcap < cap or
+// beyond the meta word's 16 bits, max_age < 0, a table beyond 160 KB of LDS, carry.tcap != tcap, a stream launch without the level's
+// slot arrays; from ASSOC_MOTION on a gain outside [0, 1] or NaN; at ASSOC_TRACKS min_hits < 1, a partial read-out triple, match outside 0..3
+int launch_associate_table(hipStream_t st, const AssocTableArgs &a, int n_clips);
 
-// The reference's box IoU, shared by decode.hip (NMS, association) and score.hip (track scoring): one definition, and both files are
+__device__ __forceinline__ float readlane_f(float v, int l) { return __int_as_float(__builtin_amdgcn_readlane(__float_as_int(v), l)); }
+
+// The reference's box IoU, shared by decode.hip (NMS), associate.hip and score.hip (track scoring): one definition, and these files are
 // compiled with -ffp-contract=off -- numpy's float32 arithmetic rounds after every multiply and add, so no FMA may be formed here;
 // the pragma in each body says so for any other file that comes to use them.
 // utils.py:175-188

@@ -1828,77 +1828,162 @@ extern "C" int dt_bbox_iou(dt_ctx *ctx, const float *d_pairs, int n, float *d_io
     return DT_OK;
 }
 
+// ---- track identity: the ten dt_associate* entries (DESIGN.md "Track identity") ---------------------------------------------------
+// One path.  A request is the launch's own argument struct: level = ASSOC_FRAME (associate_kernel, the previous-frame rule) or a level
+// of the table kernel.  An entry fills what its level has; associate_entry adds tcap and the carry of a stream call.
+static AssocTableArgs assoc_args(int level, const float *d_boxes, const int *d_counts, int T, int cap, float thr, int *d_ids, int *d_nids)
+{
+    AssocTableArgs a{};
+    a.level = level; a.boxes = d_boxes; a.counts = d_counts; a.T = T; a.cap = cap; a.thr = thr; a.ids = d_ids; a.nids = d_nids;
+    a.min_hits = 1;
+    return a;
+}
+
+// the parameters a level has; 0 or the message of the refusal, which names the argument
+static const char *assoc_params_refusal(const AssocTableArgs &a, bool stream)
+{
+    if (a.level >= ASSOC_MEMORY && a.max_age < 0) return "max_age must not be negative";
+    if (a.level >= ASSOC_MEMORY && !stream && a.tcap < a.cap) return "tcap must not be below cap";
+    if (a.level >= ASSOC_MOTION && !(a.gain >= 0.0f && a.gain <= 1.0f)) return "the motion gain must be in [0, 1]";
+    if (a.level < ASSOC_TRACKS) return nullptr;
+    if (a.min_hits < 1) return "min_hits must be at least 1";
+    const int given = (a.out.tracks != nullptr) + (a.out.tinfo != nullptr) + (a.out.tcounts != nullptr);
+    if (given != 0 && given != 3) return "d_tracks, d_tinfo and d_tcounts are given all three or none";
+    if (a.match < 0 || a.match > (DT_MATCH_BEST_FIRST | DT_MATCH_ANY_LABEL)) return "match must be a combination of DT_MATCH_BEST_FIRST and DT_MATCH_ANY_LABEL";
+    return nullptr;
+}
+
+// the slots' association state as a level's kernel sees it: the arrays of the levels above it stay null
+static AssocCarry assoc_carry(StreamTable &S, int level)
+{
+    AssocCarry c{S.list.get(), S.boxes.get(), S.ids.get(), S.ages.get(), S.meta.get(), S.tcap};
+    if (level >= ASSOC_MOTION) { c.vel = S.vel.get(); c.vstamp = S.vstamp.get(); }
+    if (level >= ASSOC_TRACKS) { c.hits = S.hits.get(); c.hstamp = S.hstamp.get(); }
+    return c;
+}
+
+// h_slots: a stream call (clip i continues slot h_slots[i], at the stream table's cap and tcap); null with stream = false: stateless
+static int associate_entry(dt_ctx *ctx, AssocTableArgs a, int n, bool stream, const int *h_slots)
+{
+    static const char *const level_tag[2][4] = {{nullptr, "memory", "motion", "tracks"}, {"stream", "stream_memory", "stream_motion", "stream_tracks"}};
+    static const double level_words[4] = {9.0, 10.0, 12.0, 13.0};      // moved per box: the profile's byte estimate
+    if (!ctx || !a.boxes || !a.counts || !a.ids || !a.nids) return dt_fail(ctx, DT_ERR_ARG, "null argument");
+    if (stream && (n <= 0 || a.T <= 0)) return dt_fail(ctx, DT_ERR_ARG, "n and T must be positive");
+    if (const char *why = assoc_params_refusal(a, stream)) return dt_fail(ctx, DT_ERR_ARG, "%s", why);
+    if (stream) {
+        const int rc = streams_check_list(ctx, h_slots, n);
+        if (rc) return rc;
+        StreamTable &S = ctx->streams;
+        if (a.cap != S.cap) return dt_fail(ctx, DT_ERR_ARG, "cap %d differs from the stream table's %d", a.cap, S.cap);
+        a.tcap = S.tcap;
+        // refused before the slot list is written, so that an error launches nothing
+        if (a.level >= ASSOC_MEMORY && assoc_table_lds_bytes(a.level, a.T, a.cap, a.tcap, a.match) > 160 * 1024)
+            return dt_fail(ctx, DT_ERR_ARG, "a track table of %d entries%s%s does not fit the LDS", a.tcap,
+                           a.level == ASSOC_MOTION ? " with velocities" : a.level == ASSOC_TRACKS ? " with velocities and hit counts" : "",
+                           (a.match & DT_MATCH_BEST_FIRST) ? " and the best-first order's words per box" : "");
+        if (launch_stream_slots(ctx->stream, h_slots, n, S.list.get(), nullptr)) return dt_fail(ctx, DT_ERR_DEVICE, "slot list launch failed");
+        a.carry = assoc_carry(S, a.level);
+    }
+    const double box_bytes = (double)(stream ? a.T + 2 : a.T) * a.cap * level_words[a.level];      // a stream call also reads and leaves the table
+    const double row_bytes = a.out.tracks ? (double)a.T * a.tcap * 12.0 : 0.0;
+    const char *tag = level_tag[stream][a.level];
+    if (a.match) tag = stream ? "stream_tracks_match" : "tracks_match";
+    ProfScope ps(ctx, "associate", 0.0, 4.0 * n * (box_bytes + row_bytes), tag);
+    int rc;
+    if (a.level != ASSOC_FRAME) rc = launch_associate_table(ctx->stream, a, n);
+    else if (stream) rc = launch_associate_stream(ctx->stream, a.boxes, a.counts, n, a.T, a.cap, a.thr, a.ids, a.nids, a.carry);
+    else rc = launch_associate(ctx->stream, a.boxes, a.counts, n, a.T, a.cap, a.thr, a.ids, a.nids);
+    if (rc) return dt_fail(ctx, launch_code(rc), "associate launch failed");
+    return DT_OK;
+}
+
 extern "C" int dt_associate(dt_ctx *ctx, const float *d_boxes, const int *d_counts, int n_clips, int T, int cap,
                             float assoc_threshold, int *d_ids, int *d_nids)
 {
-    if (!ctx || !d_boxes || !d_counts || !d_ids || !d_nids) return dt_fail(ctx, DT_ERR_ARG, "null argument");
-    ProfScope ps(ctx, "associate", 0.0, 4.0 * n_clips * (double)T * cap * 9.0);
-    const int rc = launch_associate(ctx->stream, d_boxes, d_counts, n_clips, T, cap, assoc_threshold, d_ids, d_nids);
-    if (rc) return dt_fail(ctx, launch_code(rc), "associate launch failed");
-    return DT_OK;
+    return associate_entry(ctx, assoc_args(ASSOC_FRAME, d_boxes, d_counts, T, cap, assoc_threshold, d_ids, d_nids), n_clips, false, nullptr);
+}
+
+extern "C" int dt_associate_stream(dt_ctx *ctx, const float *d_boxes, const int *d_counts, int n, int T, int cap,
+                                   float assoc_threshold, const int *h_slots, int *d_ids, int *d_nids)
+{
+    return associate_entry(ctx, assoc_args(ASSOC_FRAME, d_boxes, d_counts, T, cap, assoc_threshold, d_ids, d_nids), n, true, h_slots);
+}
+
+// the memory and motion entries, stateless (tcap given) and stream (the table's tcap)
+static int associate_aged(dt_ctx *ctx, int level, bool stream, const int *h_slots, const float *d_boxes, const int *d_counts, int n, int T, int cap,
+                          float thr, int max_age, int tcap, float gain, int *d_ids, int *d_nids, int *d_gaps)
+{
+    AssocTableArgs a = assoc_args(level, d_boxes, d_counts, T, cap, thr, d_ids, d_nids);
+    a.max_age = max_age; a.tcap = tcap; a.gain = gain; a.gaps = d_gaps;
+    return associate_entry(ctx, a, n, stream, h_slots);
 }
 
 extern "C" int dt_associate_mem(dt_ctx *ctx, const float *d_boxes, const int *d_counts, int n_clips, int T, int cap,
                                 float assoc_threshold, int max_age, int tcap, int *d_ids, int *d_nids, int *d_gaps)
 {
-    if (!ctx || !d_boxes || !d_counts || !d_ids || !d_nids) return dt_fail(ctx, DT_ERR_ARG, "null argument");
-    if (max_age < 0 || tcap < cap) return dt_fail(ctx, DT_ERR_ARG, "max_age must not be negative and tcap not below cap");
-    ProfScope ps(ctx, "associate", 0.0, 4.0 * n_clips * (double)T * cap * 10.0, "memory");
-    const int rc = launch_associate_mem(ctx->stream, d_boxes, d_counts, n_clips, T, cap, assoc_threshold, max_age, tcap, d_ids, d_nids,
-                                        d_gaps, AssocCarry{nullptr, nullptr, nullptr, nullptr, nullptr, 0});
-    if (rc) return dt_fail(ctx, launch_code(rc), "associate launch failed");
-    return DT_OK;
+    return associate_aged(ctx, ASSOC_MEMORY, false, nullptr, d_boxes, d_counts, n_clips, T, cap, assoc_threshold, max_age, tcap, 0.0f, d_ids, d_nids, d_gaps);
 }
 
 extern "C" int dt_associate_motion(dt_ctx *ctx, const float *d_boxes, const int *d_counts, int n_clips, int T, int cap,
                                    float assoc_threshold, int max_age, int tcap, float gain, int *d_ids, int *d_nids, int *d_gaps)
 {
-    if (!ctx || !d_boxes || !d_counts || !d_ids || !d_nids) return dt_fail(ctx, DT_ERR_ARG, "null argument");
-    if (max_age < 0 || tcap < cap) return dt_fail(ctx, DT_ERR_ARG, "max_age must not be negative and tcap not below cap");
-    if (!(gain >= 0.0f && gain <= 1.0f)) return dt_fail(ctx, DT_ERR_ARG, "the motion gain must be in [0, 1]");
-    ProfScope ps(ctx, "associate", 0.0, 4.0 * n_clips * (double)T * cap * 12.0, "motion");
-    const int rc = launch_associate_motion(ctx->stream, d_boxes, d_counts, n_clips, T, cap, assoc_threshold, max_age, tcap, gain, d_ids,
-                                           d_nids, d_gaps, AssocCarry{nullptr, nullptr, nullptr, nullptr, nullptr, 0});
-    if (rc) return dt_fail(ctx, launch_code(rc), "associate launch failed");
-    return DT_OK;
+    return associate_aged(ctx, ASSOC_MOTION, false, nullptr, d_boxes, d_counts, n_clips, T, cap, assoc_threshold, max_age, tcap, gain, d_ids, d_nids, d_gaps);
 }
 
-// the checks dt_associate_tracks and dt_associate_stream_tracks share; 0 or the message of the refusal
-static const char *tracks_args_refusal(int max_age, float gain, int min_hits, const float *d_tracks, const int *d_tinfo, const int *d_tcounts)
+extern "C" int dt_associate_stream_mem(dt_ctx *ctx, const float *d_boxes, const int *d_counts, int n, int T, int cap,
+                                       float assoc_threshold, int max_age, const int *h_slots, int *d_ids, int *d_nids, int *d_gaps)
 {
-    if (max_age < 0) return "max_age must not be negative";
-    if (!(gain >= 0.0f && gain <= 1.0f)) return "the motion gain must be in [0, 1]";
-    if (min_hits < 1) return "min_hits must be at least 1";
-    const int given = (d_tracks != nullptr) + (d_tinfo != nullptr) + (d_tcounts != nullptr);
-    if (given != 0 && given != 3) return "d_tracks, d_tinfo and d_tcounts are given all three or none";
-    return nullptr;
+    return associate_aged(ctx, ASSOC_MEMORY, true, h_slots, d_boxes, d_counts, n, T, cap, assoc_threshold, max_age, 0, 0.0f, d_ids, d_nids, d_gaps);
 }
 
-static bool match_valid(int match) { return match >= 0 && match <= (DT_MATCH_BEST_FIRST | DT_MATCH_ANY_LABEL); }
+extern "C" int dt_associate_stream_motion(dt_ctx *ctx, const float *d_boxes, const int *d_counts, int n, int T, int cap,
+                                          float assoc_threshold, int max_age, float gain, const int *h_slots, int *d_ids, int *d_nids,
+                                          int *d_gaps)
+{
+    return associate_aged(ctx, ASSOC_MOTION, true, h_slots, d_boxes, d_counts, n, T, cap, assoc_threshold, max_age, 0, gain, d_ids, d_nids, d_gaps);
+}
 
-// dt_associate_tracks with the track match policy of the call (DESIGN.md "Track match policy"); match = 0 is dt_associate_tracks itself
+// the tracks entries with the track match policy of the call (DESIGN.md "Track match policy"); match = 0 is dt_associate[_stream]_tracks
+// itself.  The policy leaves no trace in a slot: calls with different `match` may follow each other on one slot.
+static int associate_tracks(dt_ctx *ctx, bool stream, const int *h_slots, const float *d_boxes, const int *d_counts, int n, int T, int cap, float thr,
+                            int max_age, int tcap, float gain, int min_hits, int match, int *d_ids, int *d_nids, int *d_gaps, const TrackReadout &out)
+{
+    AssocTableArgs a = assoc_args(ASSOC_TRACKS, d_boxes, d_counts, T, cap, thr, d_ids, d_nids);
+    a.max_age = max_age; a.tcap = tcap; a.gain = gain; a.min_hits = min_hits; a.match = match; a.gaps = d_gaps; a.out = out;
+    return associate_entry(ctx, a, n, stream, h_slots);
+}
+
 extern "C" int dt_associate_tracks_match(dt_ctx *ctx, const float *d_boxes, const int *d_counts, int n_clips, int T, int cap,
                                          float assoc_threshold, int max_age, int tcap, float gain, int min_hits, int match, int *d_ids,
                                          int *d_nids, int *d_gaps, int *d_hits, float *d_tracks, int *d_tinfo, int *d_tcounts)
 {
-    if (!ctx || !d_boxes || !d_counts || !d_ids || !d_nids) return dt_fail(ctx, DT_ERR_ARG, "null argument");
-    if (tcap < cap) return dt_fail(ctx, DT_ERR_ARG, "tcap must not be below cap");
-    if (const char *why = tracks_args_refusal(max_age, gain, min_hits, d_tracks, d_tinfo, d_tcounts)) return dt_fail(ctx, DT_ERR_ARG, "%s", why);
-    if (!match_valid(match)) return dt_fail(ctx, DT_ERR_ARG, "match must be a combination of DT_MATCH_BEST_FIRST and DT_MATCH_ANY_LABEL");
-    ProfScope ps(ctx, "associate", 0.0, 4.0 * n_clips * (double)T * (cap * 13.0 + (d_tracks ? tcap * 12.0 : 0.0)), match ? "tracks_match" : "tracks");
-    const int rc = launch_associate_tracks(ctx->stream, d_boxes, d_counts, n_clips, T, cap, assoc_threshold, max_age, tcap, gain, min_hits,
-                                           match, d_ids, d_nids, d_gaps, TrackReadout{d_hits, d_tracks, d_tinfo, d_tcounts},
-                                           AssocCarry{nullptr, nullptr, nullptr, nullptr, nullptr, 0});
-    if (rc) return dt_fail(ctx, launch_code(rc), "associate launch failed");
-    return DT_OK;
+    return associate_tracks(ctx, false, nullptr, d_boxes, d_counts, n_clips, T, cap, assoc_threshold, max_age, tcap, gain, min_hits, match, d_ids, d_nids,
+                            d_gaps, TrackReadout{d_hits, d_tracks, d_tinfo, d_tcounts});
 }
 
 extern "C" int dt_associate_tracks(dt_ctx *ctx, const float *d_boxes, const int *d_counts, int n_clips, int T, int cap,
                                    float assoc_threshold, int max_age, int tcap, float gain, int min_hits, int *d_ids, int *d_nids,
                                    int *d_gaps, int *d_hits, float *d_tracks, int *d_tinfo, int *d_tcounts)
 {
-    return dt_associate_tracks_match(ctx, d_boxes, d_counts, n_clips, T, cap, assoc_threshold, max_age, tcap, gain, min_hits, 0, d_ids, d_nids,
-                                     d_gaps, d_hits, d_tracks, d_tinfo, d_tcounts);
+    return associate_tracks(ctx, false, nullptr, d_boxes, d_counts, n_clips, T, cap, assoc_threshold, max_age, tcap, gain, min_hits, 0, d_ids, d_nids,
+                            d_gaps, TrackReadout{d_hits, d_tracks, d_tinfo, d_tcounts});
+}
+
+extern "C" int dt_associate_stream_tracks_match(dt_ctx *ctx, const float *d_boxes, const int *d_counts, int n, int T, int cap,
+                                                float assoc_threshold, int max_age, float gain, int min_hits, int match, const int *h_slots,
+                                                int *d_ids, int *d_nids, int *d_gaps, int *d_hits, float *d_tracks, int *d_tinfo,
+                                                int *d_tcounts)
+{
+    return associate_tracks(ctx, true, h_slots, d_boxes, d_counts, n, T, cap, assoc_threshold, max_age, 0, gain, min_hits, match, d_ids, d_nids, d_gaps,
+                            TrackReadout{d_hits, d_tracks, d_tinfo, d_tcounts});
+}
+
+extern "C" int dt_associate_stream_tracks(dt_ctx *ctx, const float *d_boxes, const int *d_counts, int n, int T, int cap,
+                                          float assoc_threshold, int max_age, float gain, int min_hits, const int *h_slots, int *d_ids,
+                                          int *d_nids, int *d_gaps, int *d_hits, float *d_tracks, int *d_tinfo, int *d_tcounts)
+{
+    return associate_tracks(ctx, true, h_slots, d_boxes, d_counts, n, T, cap, assoc_threshold, max_age, 0, gain, min_hits, 0, d_ids, d_nids, d_gaps,
+                            TrackReadout{d_hits, d_tracks, d_tinfo, d_tcounts});
 }
 
 // track scoring (DESIGN.md "Track scoring"): CLEAR-MOT counts of hypotheses against ground-truth tracks; the caller owns the state
@@ -2279,108 +2364,6 @@ extern "C" int dt_track_stream_forward(dt_ctx *ctx, const void *d_frames, int fr
     if (rc) return rc;
     if (ctx->streams.row != (ctx->image_h / 32) * (ctx->image_w / 32) * ctx->trk_units) return dt_fail(ctx, DT_ERR_STATE, "the stream table was opened for another model");
     return track_forward_internal(ctx, d_frames, frames_dtype, n, T, h_slots, d_trk, d_det);
-}
-
-extern "C" int dt_associate_stream(dt_ctx *ctx, const float *d_boxes, const int *d_counts, int n, int T, int cap,
-                                   float assoc_threshold, const int *h_slots, int *d_ids, int *d_nids)
-{
-    if (!ctx || !d_boxes || !d_counts || !d_ids || !d_nids) return dt_fail(ctx, DT_ERR_ARG, "null argument");
-    if (n <= 0 || T <= 0) return dt_fail(ctx, DT_ERR_ARG, "n and T must be positive");
-    int rc = streams_check_list(ctx, h_slots, n);
-    if (rc) return rc;
-    StreamTable &S = ctx->streams;
-    if (cap != S.cap) return dt_fail(ctx, DT_ERR_ARG, "cap %d differs from the stream table's %d", cap, S.cap);
-    if (launch_stream_slots(ctx->stream, h_slots, n, S.list.get(), nullptr)) return dt_fail(ctx, DT_ERR_DEVICE, "slot list launch failed");
-    ProfScope ps(ctx, "associate", 0.0, 4.0 * n * (double)(T + 2) * cap * 9.0, "stream");
-    rc = launch_associate_stream(ctx->stream, d_boxes, d_counts, n, T, cap, assoc_threshold, d_ids, d_nids,
-                                 AssocCarry{S.list.get(), S.boxes.get(), S.ids.get(), S.ages.get(), S.meta.get(), S.tcap});
-    if (rc) return dt_fail(ctx, launch_code(rc), "associate launch failed");
-    return DT_OK;
-}
-
-extern "C" int dt_associate_stream_mem(dt_ctx *ctx, const float *d_boxes, const int *d_counts, int n, int T, int cap,
-                                       float assoc_threshold, int max_age, const int *h_slots, int *d_ids, int *d_nids, int *d_gaps)
-{
-    if (!ctx || !d_boxes || !d_counts || !d_ids || !d_nids) return dt_fail(ctx, DT_ERR_ARG, "null argument");
-    if (n <= 0 || T <= 0) return dt_fail(ctx, DT_ERR_ARG, "n and T must be positive");
-    if (max_age < 0) return dt_fail(ctx, DT_ERR_ARG, "max_age must not be negative");
-    int rc = streams_check_list(ctx, h_slots, n);
-    if (rc) return rc;
-    StreamTable &S = ctx->streams;
-    if (cap != S.cap) return dt_fail(ctx, DT_ERR_ARG, "cap %d differs from the stream table's %d", cap, S.cap);
-    // refused before the slot list is written, so that an error launches nothing
-    if (assoc_mem_lds_bytes(T, cap, S.tcap) > 160 * 1024) return dt_fail(ctx, DT_ERR_ARG, "a track table of %d entries does not fit the LDS", S.tcap);
-    if (launch_stream_slots(ctx->stream, h_slots, n, S.list.get(), nullptr)) return dt_fail(ctx, DT_ERR_DEVICE, "slot list launch failed");
-    ProfScope ps(ctx, "associate", 0.0, 4.0 * n * (double)(T + 2) * cap * 10.0, "stream_memory");
-    rc = launch_associate_mem(ctx->stream, d_boxes, d_counts, n, T, cap, assoc_threshold, max_age, S.tcap, d_ids, d_nids, d_gaps,
-                              AssocCarry{S.list.get(), S.boxes.get(), S.ids.get(), S.ages.get(), S.meta.get(), S.tcap});
-    if (rc) return dt_fail(ctx, launch_code(rc), "associate launch failed");
-    return DT_OK;
-}
-
-// dt_associate_stream_mem with the track-motion rule: the slot's velocities (StreamTable::vel) are the table's while the slot's stamp
-// says so, and this call's kernel leaves both.  The two older entries above advance the frame counter and not the stamp: after them the
-// table reads as at rest.
-extern "C" int dt_associate_stream_motion(dt_ctx *ctx, const float *d_boxes, const int *d_counts, int n, int T, int cap,
-                                          float assoc_threshold, int max_age, float gain, const int *h_slots, int *d_ids, int *d_nids,
-                                          int *d_gaps)
-{
-    if (!ctx || !d_boxes || !d_counts || !d_ids || !d_nids) return dt_fail(ctx, DT_ERR_ARG, "null argument");
-    if (n <= 0 || T <= 0) return dt_fail(ctx, DT_ERR_ARG, "n and T must be positive");
-    if (max_age < 0) return dt_fail(ctx, DT_ERR_ARG, "max_age must not be negative");
-    if (!(gain >= 0.0f && gain <= 1.0f)) return dt_fail(ctx, DT_ERR_ARG, "the motion gain must be in [0, 1]");
-    int rc = streams_check_list(ctx, h_slots, n);
-    if (rc) return rc;
-    StreamTable &S = ctx->streams;
-    if (cap != S.cap) return dt_fail(ctx, DT_ERR_ARG, "cap %d differs from the stream table's %d", cap, S.cap);
-    // refused before the slot list is written, so that an error launches nothing
-    if (assoc_motion_lds_bytes(T, cap, S.tcap) > 160 * 1024) return dt_fail(ctx, DT_ERR_ARG, "a track table of %d entries with velocities does not fit the LDS", S.tcap);
-    if (launch_stream_slots(ctx->stream, h_slots, n, S.list.get(), nullptr)) return dt_fail(ctx, DT_ERR_DEVICE, "slot list launch failed");
-    ProfScope ps(ctx, "associate", 0.0, 4.0 * n * (double)(T + 2) * cap * 12.0, "stream_motion");
-    rc = launch_associate_motion(ctx->stream, d_boxes, d_counts, n, T, cap, assoc_threshold, max_age, S.tcap, gain, d_ids, d_nids, d_gaps,
-                                 AssocCarry{S.list.get(), S.boxes.get(), S.ids.get(), S.ages.get(), S.meta.get(), S.tcap, S.vel.get(), S.vstamp.get()});
-    if (rc) return dt_fail(ctx, launch_code(rc), "associate launch failed");
-    return DT_OK;
-}
-
-// dt_associate_stream_motion with a hit count per entry and the read-out of the confirmed tracks: the slot's hit counts (StreamTable::hits)
-// are the table's while the slot's second stamp says so, and this call's kernel leaves both stamps.  dt_associate_stream_motion advances the
-// velocity stamp alone: after it every track reads as hits = 1; after the two older entries the velocities are forgotten too.
-// The match policy belongs to the call and leaves no trace in the slot: calls with different `match` may follow each other on one slot.
-extern "C" int dt_associate_stream_tracks_match(dt_ctx *ctx, const float *d_boxes, const int *d_counts, int n, int T, int cap,
-                                                float assoc_threshold, int max_age, float gain, int min_hits, int match, const int *h_slots,
-                                                int *d_ids, int *d_nids, int *d_gaps, int *d_hits, float *d_tracks, int *d_tinfo,
-                                                int *d_tcounts)
-{
-    if (!ctx || !d_boxes || !d_counts || !d_ids || !d_nids) return dt_fail(ctx, DT_ERR_ARG, "null argument");
-    if (n <= 0 || T <= 0) return dt_fail(ctx, DT_ERR_ARG, "n and T must be positive");
-    if (const char *why = tracks_args_refusal(max_age, gain, min_hits, d_tracks, d_tinfo, d_tcounts)) return dt_fail(ctx, DT_ERR_ARG, "%s", why);
-    if (!match_valid(match)) return dt_fail(ctx, DT_ERR_ARG, "match must be a combination of DT_MATCH_BEST_FIRST and DT_MATCH_ANY_LABEL");
-    int rc = streams_check_list(ctx, h_slots, n);
-    if (rc) return rc;
-    StreamTable &S = ctx->streams;
-    if (cap != S.cap) return dt_fail(ctx, DT_ERR_ARG, "cap %d differs from the stream table's %d", cap, S.cap);
-    // refused before the slot list is written, so that an error launches nothing
-    if (assoc_tracks_lds_bytes(T, cap, S.tcap, match) > 160 * 1024)
-        return dt_fail(ctx, DT_ERR_ARG, "a track table of %d entries with velocities and hit counts%s does not fit the LDS", S.tcap,
-                       (match & DT_MATCH_BEST_FIRST) ? " and the best-first order's words per box" : "");
-    if (launch_stream_slots(ctx->stream, h_slots, n, S.list.get(), nullptr)) return dt_fail(ctx, DT_ERR_DEVICE, "slot list launch failed");
-    ProfScope ps(ctx, "associate", 0.0, 4.0 * n * ((double)(T + 2) * cap * 13.0 + (d_tracks ? (double)T * S.tcap * 12.0 : 0.0)),
-                 match ? "stream_tracks_match" : "stream_tracks");
-    rc = launch_associate_tracks(ctx->stream, d_boxes, d_counts, n, T, cap, assoc_threshold, max_age, S.tcap, gain, min_hits, match, d_ids, d_nids, d_gaps,
-                                 TrackReadout{d_hits, d_tracks, d_tinfo, d_tcounts},
-                                 AssocCarry{S.list.get(), S.boxes.get(), S.ids.get(), S.ages.get(), S.meta.get(), S.tcap, S.vel.get(), S.vstamp.get(),
-                                            S.hits.get(), S.hstamp.get()});
-    if (rc) return dt_fail(ctx, launch_code(rc), "associate launch failed");
-    return DT_OK;
-}
-
-extern "C" int dt_associate_stream_tracks(dt_ctx *ctx, const float *d_boxes, const int *d_counts, int n, int T, int cap,
-                                          float assoc_threshold, int max_age, float gain, int min_hits, const int *h_slots, int *d_ids,
-                                          int *d_nids, int *d_gaps, int *d_hits, float *d_tracks, int *d_tinfo, int *d_tcounts)
-{
-    return dt_associate_stream_tracks_match(ctx, d_boxes, d_counts, n, T, cap, assoc_threshold, max_age, gain, min_hits, 0, h_slots, d_ids,
-                                            d_nids, d_gaps, d_hits, d_tracks, d_tinfo, d_tcounts);
 }
 
 // The two halves of dt_track_forward for a FRAME-sharded deployment (BASELINE.json configs[4]):

@@ -6,7 +6,7 @@
 //   1. carry-over: ground-truth row g, ascending, whose object was last matched to track id tau >= 0 takes the lowest unclaimed
 //      hypothesis of id tau if that pair is valid (IoU >= thr, equal labels unless ANY);
 //   2. the rest: among the unmatched rows and unclaimed hypotheses the valid pair of the largest IoU is taken repeatedly, ties to
-//      the lowest g, then the lowest i -- the best-IoU-first order of associate_tracks_kernel, in its LDS form;
+//      the lowest g, then the lowest i -- the best-IoU-first order of associate.hip:associate_table_kernel, in its LDS form;
 //   3. counts of the frame, then the table update with the result of a walk in g order.
 //
 // This translation unit is compiled with -ffp-contract=off: the IoU is bbox_iou_ref's float32 bits (dt_internal.h).
@@ -118,7 +118,7 @@ __global__ __launch_bounds__(64) void track_score_kernel(ScoreArgs p, int resume
                 todo &= todo - 1ull;
             }
         }
-        // ---- 2. the rest, best IoU first (associate_tracks_kernel's LDS form: cached best candidate per row, rounds) ----
+        // ---- 2. the rest, best IoU first (associate_table_kernel's LDS form: cached best candidate per row, rounds) ----
         auto scan = [&](int g) {
             const float ax = gx[g], ay = gy[g], aw = gw[g], ah = gh[g], al = gl[g];
             unsigned bestk = 0u;
