@@ -46,6 +46,7 @@ extern "C" {
 #define DT_MATCH_DECODE_ORDER 0 /* track match policy (dt_associate_tracks_match): boxes in decode order, entries of the box's label */
 #define DT_MATCH_BEST_FIRST 1   /* ... bit: the candidate pairs are taken best IoU first */
 #define DT_MATCH_ANY_LABEL 2    /* ... bit: labels are not compared */
+#define DT_ASSIGN_IOU_SCALE 1048576 /* track assignment (dt_associate_tracks_assign): a candidate weighs 1 + trunc(IoU * this), 2^20 */
 
 #define DT_SCORE_INTS 8       /* track scoring totals of a clip (dt_track_score): frames, gt boxes, hyp boxes, matches, switches, fragments, overflow, 0 */
 #define DT_SCORE_OBJ_INTS 8   /* ... a row of its object table: gt id, last track id (-1: never matched), present, matched, switches, fragments,
@@ -73,6 +74,7 @@ DT_API int dt_set_stream(dt_ctx *ctx, void *hip_stream);
  * and the one track scoring entry dt_track_score
  * and the two detection scoring entries dt_detect_match, dt_detect_rank
  * and the two identity scoring entries dt_identity_overlap, dt_assign_max
+ * and the two track assignment entries dt_associate_tracks_assign, dt_associate_stream_tracks_assign
  * -- additions only, the number stayed; 1.07: 1.06 + dt_gemm_split, dt_policy_set) */
 DT_API int dt_abi_version(void);
 
@@ -351,11 +353,40 @@ DT_API int dt_associate_tracks(dt_ctx *ctx, const float *d_boxes, const int *d_c
  * that does not depend on the order in which the frame's boxes arrive, ties apart.  Then the boxes that claimed nothing open new ids
  * in decode order; whenever both orders find the same pairs every output is the same bit for bit.  A box that claims an entry of another
  * label carries on its id, hits and velocity; the rebuilt entry has the box's label.
- * Not done here: an optimal (Hungarian) assignment (dt_assign_max is one, not yet behind this match), a cost other than IoU.
+ * Not done here: an optimal (Hungarian) assignment -- that is dt_associate_tracks_assign below, an entry of its own --, a cost other
+ * than IoU.
  * DT_ERR_ARG: as dt_associate_tracks, and match outside 0..3.  With DT_MATCH_BEST_FIRST the LDS also holds three words per box (best
  * candidate key, its entry, claimed), 20 * tcap + 4 * cap words in all: tcap = cap fits up to 1706 (1950 without the bit); a table
  * with tcap <= 64 and T <= 64 runs in registers and keeps only the frame's keys, 256 * cap bytes, in the LDS. */
 DT_API int dt_associate_tracks_match(dt_ctx *ctx, const float *d_boxes, const int *d_counts,
+                 int n_clips, int T, int cap, float assoc_threshold, int max_age, int tcap, float gain, int min_hits, int match,
+                 int *d_ids, int *d_nids, int *d_gaps, int *d_hits, float *d_tracks, int *d_tinfo, int *d_tcounts);
+/* Track assignment (BUILD-DEFINED, DESIGN.md "Track assignment"): dt_associate_tracks_match with the match of a frame replaced by an
+ * optimal one-to-one assignment, the step every association tracker of the SORT family takes (Hungarian method on the IoU matrix).
+ * Arguments and outputs are dt_associate_tracks_match's.  match is 0 or DT_MATCH_ANY_LABEL; DT_MATCH_BEST_FIRST is refused, for an
+ * order means nothing to an assignment.
+ * Candidates of a frame are exactly dt_associate_tracks_match's: pairs (box i in decode order, table entry j with age <= max_age), labels
+ * equal as floats unless DT_MATCH_ANY_LABEL is set, iou = bbox_iou(box i, predicted box of entry j) >= assoc_threshold as float32; a NaN
+ * is never a candidate.
+ * Weights: a matrix W[n][nt] of int32 over all n boxes and all nt table entries.  A candidate has W[i][j] = 1 + (int)(iou *
+ * 1048576.0f) (DT_ASSIGN_IOU_SCALE; the product is exact, the factor being a power of two, and the conversion truncates); every other
+ * pair has weight 0.  IoU differences below 2^-20 are therefore ties.
+ * Match: the claimed pairs are the row_to_col of dt_assign_max on W with rows = n and cols = nt -- the same method, the same
+ * orientation rule (solved on the side with fewer rows), the same tie rule (the lowest column), pairs of weight 0 reported as
+ * unassigned.  The result is an exact maximum of the summed quantised IoU over the one-to-one sets of candidates, and which optimum
+ * is chosen is fixed.  The set of the largest weight is not always the largest set: one pair of IoU 0.9 beats two of 0.3 each, and the
+ * box left over opens an id.
+ * Everything after the match is dt_associate_tracks_match's bit for bit: a claiming box inherits id, gap, hits + 1 and the velocity
+ * update on the entry's stored x, y; the other boxes open ids in decode order, at rest, with hits 1; rebuild, capacity cut and read-out
+ * are unchanged.  Boxes must be finite; non-finite boxes give unspecified ids, but the call still terminates and stays in bounds.
+ * Cost: up to min(n, nt)^2 solver steps per frame, each a pass over max(n, nt) entries 64 at a time; meant for frames of tens to a few
+ * hundred boxes.
+ * Not done here: a cost other than IoU, Kalman or w / h models, the optimal assignment inside dt_track_score's frame step.
+ * DT_ERR_ARG: as dt_associate_tracks_match, match other than 0 or DT_MATCH_ANY_LABEL, and a table that does not fit the 160 KB of LDS:
+ * beside the two tables and four words per box the LDS holds the solver's six work arrays of tcap + 1 words, so 26 * tcap + 4 * cap + 6
+ * words must not exceed 40960 (tcap = cap fits up to 1365).  A table with tcap <= 64 and T <= 64 runs in registers and keeps only the
+ * frame's weights and pairs, 260 * cap + 512 bytes, in the LDS. */
+DT_API int dt_associate_tracks_assign(dt_ctx *ctx, const float *d_boxes, const int *d_counts,
                  int n_clips, int T, int cap, float assoc_threshold, int max_age, int tcap, float gain, int min_hits, int match,
                  int *d_ids, int *d_nids, int *d_gaps, int *d_hits, float *d_tracks, int *d_tinfo, int *d_tcounts);
 
@@ -448,7 +479,7 @@ DT_API int dt_track_score(dt_ctx *ctx, const float *d_gt_boxes, const int *d_gt_
  * DT_ERR_ARG (nothing launched, nothing written): a NULL pointer, n < 0, rcap or ccap <= 0, rows_at or cols_at outside 0..stride-1,
  * n * rcap * ccap >= 2^31, or work arrays that do not fit the 160 KB of LDS: 6 * (max(rcap, ccap) + 1) words must not exceed 40960
  * (caps up to 6825).
- * Not done here: HOTA, ignore regions, this solver behind the tracker's own match (dt_associate_tracks_match). */
+ * Not done here: HOTA, ignore regions.  (This solver's method is also the tracker's own match in dt_associate_tracks_assign.) */
 DT_API int dt_identity_overlap(dt_ctx *ctx, const float *d_gt_boxes, const int *d_gt_counts, const int *d_gt_ids, int gcap,
                  const float *d_hyp_boxes, const int *d_hyp_counts, const int *d_hyp_ids, int hcap, int id_stride, int hyp_label_at,
                  int n_clips, int T, float iou_threshold, int flags, int acap, int bcap,
@@ -560,6 +591,15 @@ DT_API int dt_associate_stream_tracks(dt_ctx *ctx, const float *d_boxes, const i
  * chunk uses the same match.  Errors as dt_associate_stream_tracks, and DT_ERR_ARG for match outside 0..3 or, with DT_MATCH_BEST_FIRST,
  * a table that does not fit the LDS beside the order's three words per box; an error leaves the slots as they were. */
 DT_API int dt_associate_stream_tracks_match(dt_ctx *ctx, const float *d_boxes, const int *d_counts, int n, int T, int cap,
+                        float thr, int max_age, float gain, int min_hits, int match, const int *h_slots, int *d_ids, int *d_nids,
+                        int *d_gaps, int *d_hits, float *d_tracks, int *d_tinfo, int *d_tcounts);
+/* dt_associate_tracks_assign for streams: dt_associate_stream_tracks with the optimal assignment as the match of every frame; match is
+ * 0 or DT_MATCH_ANY_LABEL.  The policy leaves nothing in the slot and the slot layout is dt_associate_stream_tracks': calls of any
+ * association entry may follow each other on one slot, exactly as dt_associate_stream_tracks_match documents, and chunks of any sizes
+ * give what dt_associate_tracks_assign gives on the concatenation with tcap = the table's.  Errors as dt_associate_stream_tracks, and
+ * DT_ERR_ARG for any other match or a table beyond 26 * tcap + 4 * cap + 6 <= 40960 words (refused before the slot list is written);
+ * an error leaves the slots as they were. */
+DT_API int dt_associate_stream_tracks_assign(dt_ctx *ctx, const float *d_boxes, const int *d_counts, int n, int T, int cap,
                         float thr, int max_age, float gain, int min_hits, int match, const int *h_slots, int *d_ids, int *d_nids,
                         int *d_gaps, int *d_hits, float *d_tracks, int *d_tinfo, int *d_tcounts);
 

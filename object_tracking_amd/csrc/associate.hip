@@ -256,6 +256,11 @@ int launch_associate_stream(hipStream_t st, const float *boxes, const int *count
 // (box, entry) with the largest IoU key is taken repeatedly, ties to the lowest box, then the lowest entry; the boxes left over
 // open their ids in decode order afterwards.  Load, rebuild, hits, read-out and store are shared by all four.
 //
+// ASSOC_MATCH_ASSIGN (dt_associate_tracks_assign, ASSOC_TRACKS only, never with BEST_FIRST): a third match block in each form.  The
+// claimed pairs are an exact maximum-weight one-to-one assignment over the frame's candidates, weight = 1 + trunc(IoU * 2^20):
+// dt_assign_max's method, orientation and tie rule (identity.hip:assign_max_kernel), step for step.  What the boxes inherit and the
+// ids the others open are the best-first block's code behind the match.
+//
 // One wavefront per clip, two forms like associate_kernel, chosen from tcap and T alone.
 // ---------------------------------------------------------------------------
 __device__ __forceinline__ void track_row_store(float *tracks, int *tinfo, long long row, float x, float y, float w, float h, float l,
@@ -271,6 +276,9 @@ __device__ __forceinline__ void track_row_empty(float *tracks, int *tinfo, long 
     track_row_store(tracks, tinfo, row, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f, -1, -1, -1, -1);
 }
 
+// a candidate's weight in the optimal assignment: 1 + the IoU in units of 2^-20, truncated (the product is exact: a power of two)
+__device__ __forceinline__ int assign_weight(float iou) { return 1 + __float2int_rz(iou * (float)DT_ASSIGN_IOU_SCALE); }
+
 template <bool STREAM, int LEVEL, int MATCH>
 __global__ __launch_bounds__(64) void associate_table_kernel(const float *boxes, const int *counts, int T, int cap, float thr,
                                                              int max_age, int tcap, float gain, int min_hits, int *ids, int *nids,
@@ -279,6 +287,8 @@ __global__ __launch_bounds__(64) void associate_table_kernel(const float *boxes,
     static_assert(LEVEL >= ASSOC_MEMORY && LEVEL <= ASSOC_TRACKS && (MATCH == 0 || LEVEL == ASSOC_TRACKS), "the match policies belong to the tracks level");
     constexpr bool VEL = LEVEL >= ASSOC_MOTION, HITS = LEVEL >= ASSOC_TRACKS;
     constexpr bool BEST = (MATCH & DT_MATCH_BEST_FIRST) != 0, ANY = (MATCH & DT_MATCH_ANY_LABEL) != 0;
+    constexpr bool OPT = (MATCH & ASSOC_MATCH_ASSIGN) != 0;      // the optimal assignment; the launcher's bit, not a DT_MATCH_* one
+    static_assert(!(BEST && OPT), "an assignment has no order");
     constexpr int W = 7 + 2 * VEL + HITS;      // LDS words per entry of the general form: 5 box fields, id, age | vx, vy at 7, 8 | hits at 9
     extern __shared__ __attribute__((aligned(16))) float smem[];
     const int clip = blockIdx.x, lane = threadIdx.x;
@@ -391,7 +401,83 @@ __global__ __launch_bounds__(64) void associate_table_kernel(const float *boxes,
             }
             int cid = -1, cgap = -1, chits = -1;
             float cvx = 0.0f, cvy = 0.0f;
-            if constexpr (BEST) {
+            if constexpr (BEST || OPT) {
+                int tid0, cent;                         // the entries' ids before the claims mark them; lane = box: the entry it claimed
+                if constexpr (OPT) {
+                // optimal assignment (DESIGN.md "Track assignment"): dt_assign_max's method on the frame's weights, in registers.
+                // The weights are an [n][ASSIGN_TILE_STRIDE] tile of dynamic LDS, row = box, column = lane = entry; the odd stride
+                // spreads a column over the banks, for the transposed solve (nt < n) reads down one.  Solve rows and columns count
+                // from 1 (assign_max_kernel): lane j - 1 owns column j's v, minv, way, used and p, lane i - 1 owns row i's u, and
+                // the root column 0 is the wave-uniform j0 == 0 with p[0] = i.  `rin` marks the rows p[j] of the used columns
+                // (lane = row), which are the rows a step adds delta to.  The arithmetic is assign_max_kernel's unsigned words.
+                // Bounds: every loop below is counted (N rows, at most M + 1 steps, at most M + 1 flips), and every lane or tile
+                // index comes from a ballot below M, from `way` (a j0 of the same range) or from p (i or a copy of a p), never from
+                // a weight: non-finite boxes or a degenerate table may give unspecified ids, never an unbounded loop or an index
+                // outside the tile.
+                tid0 = tid; cent = -1;
+                volatile int *wm = reinterpret_cast<volatile int *>(smem);
+                volatile int *pent = wm + ASSIGN_TILE_STRIDE * cap, *pclm = pent + 64;   // the pairs: per box its entry, per entry whether claimed
+                const bool live = lane < nt && tid >= 0 && tage <= max_age;
+                for (int i = 0; i < n; ++i) {
+                    const float ax = readlane_f(cx, i), ay = readlane_f(cy, i), aw = readlane_f(cw, i), ah = readlane_f(ch, i);
+                    const float al = readlane_f(cl, i);
+                    const float iou = bbox_iou_ref(ax, ay, aw, ah, qx, qy, tbw, tbh);
+                    wm[i * ASSIGN_TILE_STRIDE + lane] = (live && (ANY || tbl == al) && iou >= thr) ? assign_weight(iou) : 0;
+                }
+                pent[lane] = -1; pclm[lane] = 0;
+                __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
+                __builtin_amdgcn_wave_barrier();
+                const bool tr = nt < n;                 // the solve's rows are the entries
+                const int N = tr ? nt : n, M = tr ? n : nt;
+                unsigned zu = 0u, zv = 0u;
+                int zp = 0, zway = 0;
+                for (int i = 1; i <= N; ++i) {
+                    unsigned minv = (unsigned)ASSIGN_INF;
+                    bool used = false, rin = false;
+                    int j0 = 0, i0 = i;
+                    bool reached = false;
+                    for (int step = 0; step <= M; ++step) {
+                        rin = rin || lane == i0 - 1;
+                        const unsigned ui = (unsigned)__builtin_amdgcn_readlane((int)zu, i0 - 1);
+                        const bool act = lane < M && !used;
+                        unsigned key = 0u;
+                        if (act) {
+                            const int wt = tr ? wm[lane * ASSIGN_TILE_STRIDE + (i0 - 1)] : wm[(i0 - 1) * ASSIGN_TILE_STRIDE + lane];
+                            const unsigned cur = 0u - (unsigned)wt - ui - zv;
+                            if ((int)cur < (int)minv) { minv = cur; zway = j0; }
+                            key = (unsigned)ASSIGN_INF - minv;
+                        }
+                        const unsigned top = wave_umax_dpp(key);
+                        const unsigned long long bal = __ballot(act && key == top);
+                        if (!bal) break;                // no unused column: cannot happen while N <= M
+                        const int j1 = __ffsll((long long)bal);
+                        const unsigned delta = (unsigned)ASSIGN_INF - top;
+                        if (rin) zu += delta;
+                        if (used) zv -= delta; else minv -= delta;
+                        j0 = j1;
+                        used = used || lane == j1 - 1;
+                        i0 = __builtin_amdgcn_readlane(zp, j1 - 1);
+                        if (i0 == 0) { reached = true; break; }
+                    }
+                    // flip the path back to the root
+                    for (int step = 0; reached && step <= M && j0 != 0; ++step) {
+                        const int jp = __builtin_amdgcn_readlane(zway, j0 - 1);
+                        const int pn = jp == 0 ? i : __builtin_amdgcn_readlane(zp, (jp - 1) & 63);
+                        zp = lane == j0 - 1 ? pn : zp;
+                        j0 = jp;
+                    }
+                }
+                // lane = column: its pair, unless the pair has no weight
+                if (lane < M && zp >= 1) {
+                    const int b = tr ? lane : zp - 1, e = tr ? zp - 1 : lane;
+                    if (wm[b * ASSIGN_TILE_STRIDE + e] != 0) { pent[b] = e; pclm[e] = 1; }
+                }
+                __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
+                __builtin_amdgcn_wave_barrier();
+                cent = pent[lane];
+                if (pclm[lane]) tid = -1;               // claimed
+                __builtin_amdgcn_wave_barrier();        // the next frame's tile stands behind these reads
+                } else {
                 // best-IoU-first order: the frame's keys are an [n][64] tile of dynamic LDS, column = lane = entry, and a lane
                 // reads and writes its own column only.  Each lane caches its column's best remaining (key, box), ties to the
                 // lowest box.  A round: the wave-wide largest cached key, among its lanes the lowest box, among those the
@@ -411,8 +497,7 @@ __global__ __launch_bounds__(64) void associate_table_kernel(const float *boxes,
                     if (key > bk) { bk = key; bb = i; }
                 }
                 unsigned long long taken = 0ull;        // boxes that have claimed an entry
-                const int tid0 = tid;                   // the entries' ids before the claims mark them
-                int cent = -1;                          // lane = box: the entry it claimed
+                cent = -1; tid0 = tid;
                 for (;;) {
                     const unsigned m = wave_umax_dpp(bk);
                     if (m == 0u) break;
@@ -437,6 +522,7 @@ __global__ __launch_bounds__(64) void associate_table_kernel(const float *boxes,
                             }
                         }
                     }
+                }
                 }
                 // what a box inherits from the entry it claimed (every lane takes part in the lane reads)
                 {
@@ -625,13 +711,115 @@ __global__ __launch_bounds__(64) void associate_table_kernel(const float *boxes,
             const float *q = cur + j * 8;
             B[j] = q[0]; B[tcap + j] = q[1]; B[2 * tcap + j] = q[2]; B[3 * tcap + j] = q[3]; B[4 * tcap + j] = q[5];
             bage[j] = 0;
-            if constexpr (BEST) bdone[j] = 0;
+            if constexpr (BEST || OPT) bdone[j] = 0;
         }
         __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
         __builtin_amdgcn_wave_barrier();
         if constexpr (HITS)
             if (tk && t > 0) readout(t - 1);              // table A is frame t-1's until the first claim below
-        if constexpr (BEST) {
+        if constexpr (BEST || OPT) {
+            if constexpr (OPT) {
+            // optimal assignment (DESIGN.md "Track assignment"): assign_max_kernel's loop with its six work arrays of tcap + 1 words
+            // behind the per-box words, on the frame's weights.  No n x nt matrix is held: a weight is recomputed from table A and the
+            // frame's boxes (in B) wherever the solver reads one -- a pure function of both, neither of which changes before the
+            // claims below, so its bits repeat.  Solve rows and columns count from 1 and column 0 is the root; the solve is
+            // transposed (rows = entries) when nt < n.  Bounds as in the register form: every loop is counted, and every index into
+            // the tables or the work arrays is a counter, a ballot position below M, a `way` (a j0) or a p (i or a copy of a p),
+            // never a weight: non-finite boxes or a degenerate table may give unspecified ids, never an unbounded loop or an index
+            // outside the LDS.
+            const int L = tcap + 1;
+            volatile unsigned *zu = reinterpret_cast<volatile unsigned *>(smem + 2 * TS + 4 * cap), *zv = zu + L, *zminv = zv + L;
+            volatile int *zway = reinterpret_cast<volatile int *>(zminv + L), *zp = zway + L, *zused = zp + L;
+            auto weight_of = [&](int b, int e) -> int {       // box b of the frame, entry e of table A
+                if (!(aage[e] <= max_age && (ANY || A[4 * tcap + e] == B[4 * tcap + b]))) return 0;
+                const float k = (float)(aage[e] + 1);
+                const float qx = A[e] + k * A[7 * tcap + e], qy = A[tcap + e] + k * A[8 * tcap + e];
+                const float iou = bbox_iou_ref(B[b], B[tcap + b], B[2 * tcap + b], B[3 * tcap + b], qx, qy, A[2 * tcap + e], A[3 * tcap + e]);
+                return iou >= thr ? assign_weight(iou) : 0;
+            };
+            const bool tr = nt < n;                     // the solve's rows are the entries
+            const int N = tr ? nt : n, M = tr ? n : nt;
+            auto weight = [&](int i, int j) { return tr ? weight_of(j - 1, i - 1) : weight_of(i - 1, j - 1); };
+            for (int j = lane; j <= M; j += 64) { zv[j] = 0u; zp[j] = 0; zway[j] = 0; }
+            for (int i = lane; i <= N; i += 64) zu[i] = 0u;
+            __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
+            __builtin_amdgcn_wave_barrier();
+            for (int i = 1; i <= N; ++i) {
+                for (int j = lane; j <= M; j += 64) { zminv[j] = (unsigned)ASSIGN_INF; zused[j] = 0; }
+                if (lane == 0) zp[0] = i;
+                __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
+                __builtin_amdgcn_wave_barrier();
+                int j0 = 0;
+                bool reached = false;
+                for (int step = 0; step <= M; ++step) {
+                    if (lane == 0) zused[j0] = 1;
+                    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
+                    __builtin_amdgcn_wave_barrier();
+                    const int i0 = min(max(zp[j0], 1), N);     // (in 1..N by construction; the clamp keeps the table index there whatever happens)
+                    const unsigned ui = zu[i0];
+                    unsigned bestk = 0u;
+                    int j1 = -1;
+                    for (int jb = 1; jb <= M; jb += 64) {
+                        const int j = jb + lane;
+                        const bool act = j <= M && zused[j] == 0;
+                        unsigned key = 0u;
+                        if (act) {
+                            const unsigned cur = 0u - (unsigned)weight(i0, j) - ui - zv[j];
+                            unsigned m = zminv[j];
+                            if ((int)cur < (int)m) { m = cur; zminv[j] = cur; zway[j] = j0; }
+                            key = (unsigned)ASSIGN_INF - m;
+                        }
+                        const unsigned top = wave_umax_dpp(key);
+                        if (top > bestk || j1 < 0) {
+                            const unsigned long long bal = __ballot(act && key == top);
+                            if (bal) {
+                                bestk = top;
+                                j1 = jb + __ffsll((long long)bal) - 1;
+                            }
+                        }
+                    }
+                    if (j1 < 0) break;                  // no unused column: cannot happen while N <= M
+                    const unsigned delta = (unsigned)ASSIGN_INF - bestk;
+                    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
+                    __builtin_amdgcn_wave_barrier();
+                    for (int j = lane; j <= M; j += 64) {
+                        if (zused[j]) {                 // p is one-to-one on the used columns
+                            const int pj = min(max(zp[j], 0), N);
+                            zu[pj] = zu[pj] + delta;
+                            zv[j] = zv[j] - delta;
+                        } else {
+                            zminv[j] = zminv[j] - delta;
+                        }
+                    }
+                    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
+                    __builtin_amdgcn_wave_barrier();
+                    j0 = j1;
+                    if (zp[j0] == 0) { reached = true; break; }
+                }
+                // flip the path back to the root
+                if (lane == 0 && reached) {
+                    int j = j0;
+                    for (int step = 0; step <= M && j != 0; ++step) {
+                        const int jp = min(max(zway[j], 0), M);
+                        zp[j] = zp[jp];
+                        j = jp;
+                    }
+                }
+                __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
+                __builtin_amdgcn_wave_barrier();
+            }
+            // the pairs that have a weight: the box notes its entry, the entry is marked like a best-first claim (complemented id)
+            for (int j = 1 + lane; j <= M; j += 64) {
+                const int i = zp[j];
+                if (i < 1 || i > N) continue;
+                const int b = tr ? j - 1 : i - 1, e = tr ? i - 1 : j - 1;
+                if (weight_of(b, e) == 0) continue;
+                bent[b] = e; bdone[b] = 1;
+                aid[e] = ~aid[e];
+            }
+            __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
+            __builtin_amdgcn_wave_barrier();
+            } else {
             // best-IoU-first order.  scan(i): box i's best candidate among the unclaimed entries, 64 entries per pass, ties to the
             // lowest entry -- the decode-order match's inner loop -- cached in bkey / bent.  A round: the largest cached key over
             // the boxes, 64 per pass, ties to the lowest box; that box claims its cached entry; the boxes still unmatched whose
@@ -690,6 +878,7 @@ __global__ __launch_bounds__(64) void associate_table_kernel(const float *boxes,
                     }
                 }
                 __builtin_amdgcn_wave_barrier();
+            }
             }
             // a box that claimed an entry inherits from it; the others open ids in decode order, at hits = 1 and at rest
             for (int i0 = 0; i0 < n; i0 += 64) {
@@ -810,10 +999,14 @@ __global__ __launch_bounds__(64) void associate_table_kernel(const float *boxes,
 
 size_t assoc_table_lds_bytes(int level, int T, int cap, int tcap, int match)
 {
-    const bool best = (match & DT_MATCH_BEST_FIRST) != 0;
-    if (tcap <= 64 && T <= 64) return best ? (size_t)64 * cap * sizeof(unsigned) : 0;      // the frame's keys, [cap][64]
+    const bool best = (match & DT_MATCH_BEST_FIRST) != 0, opt = (match & ASSOC_MATCH_ASSIGN) != 0;
+    if (tcap <= 64 && T <= 64) {
+        if (opt) return ((size_t)ASSIGN_TILE_STRIDE * cap + 128) * sizeof(int);            // the frame's weights, [cap][65], and the pairs
+        return best ? (size_t)64 * cap * sizeof(unsigned) : 0;                             // the frame's keys, [cap][64]
+    }
     const int words = 7 + 2 * (level >= ASSOC_MOTION) + (level >= ASSOC_TRACKS);           // per entry, as the kernel's W
-    return ((size_t)2 * words * tcap + (best ? 4 : 1) * cap) * sizeof(float);              // + key, entry, claimed per box
+    return ((size_t)2 * words * tcap + (best || opt ? 4 : 1) * cap                         // + key, entry, claimed per box
+            + (opt ? (size_t)6 * (tcap + 1) : 0)) * sizeof(float);                         // + the solver's u, v, minv, way, p, used
 }
 
 // one launch of associate_table_kernel<STREAM, LEVEL, MATCH>; the attribute is set once per device and instantiation
@@ -839,6 +1032,8 @@ int launch_associate_table(hipStream_t st, const AssocTableArgs &a, int n_clips)
     if (a.T <= 0 || a.cap <= 0 || a.tcap < a.cap || a.tcap > SM_COUNT_MASK || a.max_age < 0) return 2;
     if (a.level >= ASSOC_MOTION && !(a.gain >= 0.0f && a.gain <= 1.0f)) return 2;      // (NaN fails both comparisons)
     if (a.level < ASSOC_TRACKS ? a.match != 0 : (a.match < 0 || a.match > (DT_MATCH_BEST_FIRST | DT_MATCH_ANY_LABEL))) return 2;
+    if (a.assign && (a.level != ASSOC_TRACKS || (a.match & DT_MATCH_BEST_FIRST))) return 2;
+    const int match = assoc_kernel_match(a);
     if (a.level == ASSOC_TRACKS) {
         const TrackReadout &o = a.out;
         if (a.min_hits < 1) return 2;
@@ -849,18 +1044,20 @@ int launch_associate_table(hipStream_t st, const AssocTableArgs &a, int n_clips)
     if (stream && c.tcap != a.tcap) return 2;
     if (stream && a.level >= ASSOC_MOTION && (!c.vel || !c.vstamp)) return 2;
     if (stream && a.level >= ASSOC_TRACKS && (!c.hits || !c.hstamp)) return 2;
-    const size_t lds = assoc_table_lds_bytes(a.level, a.T, a.cap, a.tcap, a.match);
+    const size_t lds = assoc_table_lds_bytes(a.level, a.T, a.cap, a.tcap, match);
     if (lds > 160 * 1024) return 2;
     if (n_clips <= 0) return 0;
 #define DT_TABLE_LAUNCH(L, M) \
-    case (L) * 4 + (M): return stream ? launch_table_as<true, L, M>(st, lds, a, n_clips) : launch_table_as<false, L, M>(st, lds, a, n_clips);
-    switch (a.level * 4 + a.match) {
+    case (L) * 8 + (M): return stream ? launch_table_as<true, L, M>(st, lds, a, n_clips) : launch_table_as<false, L, M>(st, lds, a, n_clips);
+    switch (a.level * 8 + match) {
         DT_TABLE_LAUNCH(ASSOC_MEMORY, 0)
         DT_TABLE_LAUNCH(ASSOC_MOTION, 0)
         DT_TABLE_LAUNCH(ASSOC_TRACKS, 0)
         DT_TABLE_LAUNCH(ASSOC_TRACKS, 1)
         DT_TABLE_LAUNCH(ASSOC_TRACKS, 2)
         DT_TABLE_LAUNCH(ASSOC_TRACKS, 3)
+        DT_TABLE_LAUNCH(ASSOC_TRACKS, ASSOC_MATCH_ASSIGN)
+        DT_TABLE_LAUNCH(ASSOC_TRACKS, ASSOC_MATCH_ASSIGN | DT_MATCH_ANY_LABEL)
     }
 #undef DT_TABLE_LAUNCH
     return 2;

@@ -368,13 +368,23 @@ struct AssocTableArgs {
     // at the tracks level (106 SGPRs, some kept in VGPR lanes) that changed where the spills fall.
     int level;         // ASSOC_MEMORY .. ASSOC_TRACKS
     int match;          // the track match policy, DT_MATCH_* bits (0 = decode order within a label); non-zero at ASSOC_TRACKS only
+    bool assign;        // the optimal assignment (dt_associate_tracks_assign): ASSOC_TRACKS only, match 0 or DT_MATCH_ANY_LABEL
 };
-// dynamic LDS the launch needs: none in the register form (tcap <= 64, T <= 64) but the best-IoU-first order's keys [cap][64]; in the
-// general form two tables of 7 / 9 / 10 words per entry, the frame's gaps, and three more words per box for the best-IoU-first order
+// The kernel's MATCH template value: the call's DT_MATCH_* bits and, for the assignment entries, ASSOC_MATCH_ASSIGN -- a bit of the
+// launcher's own, never accepted from a public `match` argument (the match entries refuse 4 as they always did).
+#define ASSOC_MATCH_ASSIGN 4
+inline int assoc_kernel_match(const AssocTableArgs &a) { return a.match | (a.assign ? ASSOC_MATCH_ASSIGN : 0); }
+#define ASSIGN_TILE_STRIDE 65     // words per row of the register form's weight tile: odd, so a column's 64 words fall in 64 banks
+#define ASSIGN_INF 0x7fffffff     // assign_max_kernel's and the assignment match's "no reduced cost yet"
+// dynamic LDS the launch needs: none in the register form (tcap <= 64, T <= 64) but the best-IoU-first order's keys [cap][64] or the
+// assignment's weights [cap][65] and 128 words of pairs; in the general form two tables of 7 / 9 / 10 words per entry, the frame's
+// gaps, three more words per box for the best-IoU-first order and the assignment, and the assignment's 6 * (tcap + 1) solver words.
+// match: the kernel's MATCH value (assoc_kernel_match)
 size_t assoc_table_lds_bytes(int level, int T, int cap, int tcap, int match);
 // 0: launched (or, n_clips <= 0, nothing to launch); 1: device error; 2: argument error, nothing launched -- T or cap < 1, tcap < cap or
 // beyond the meta word's 16 bits, max_age < 0, a table beyond 160 KB of LDS, carry.tcap != tcap, a stream launch without the level's
-// slot arrays; from ASSOC_MOTION on a gain outside [0, 1] or NaN; at ASSOC_TRACKS min_hits < 1, a partial read-out triple, match outside 0..3
+// slot arrays; from ASSOC_MOTION on a gain outside [0, 1] or NaN; at ASSOC_TRACKS min_hits < 1, a partial read-out triple, match outside 0..3, assign below
+// ASSOC_TRACKS or with DT_MATCH_BEST_FIRST
 int launch_associate_table(hipStream_t st, const AssocTableArgs &a, int n_clips);
 
 __device__ __forceinline__ float readlane_f(float v, int l) { return __int_as_float(__builtin_amdgcn_readlane(__float_as_int(v), l)); }

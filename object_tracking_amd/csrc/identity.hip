@@ -196,7 +196,6 @@ int launch_identity_overlap(hipStream_t st, const IdentArgs &a, int n_clips, int
 }
 
 // ---------------------------------------------------------------------------------------------------------------- assignment
-#define ASSIGN_INF 0x7fffffff
 
 __global__ __launch_bounds__(64) void assign_max_kernel(AssignArgs a)
 {

@@ -1828,7 +1828,7 @@ extern "C" int dt_bbox_iou(dt_ctx *ctx, const float *d_pairs, int n, float *d_io
     return DT_OK;
 }
 
-// ---- track identity: the ten dt_associate* entries (DESIGN.md "Track identity") ---------------------------------------------------
+// ---- track identity: the twelve dt_associate* entries (DESIGN.md "Track identity") ---------------------------------------------------
 // One path.  A request is the launch's own argument struct: level = ASSOC_FRAME (associate_kernel, the previous-frame rule) or a level
 // of the table kernel.  An entry fills what its level has; associate_entry adds tcap and the carry of a stream call.
 static AssocTableArgs assoc_args(int level, const float *d_boxes, const int *d_counts, int T, int cap, float thr, int *d_ids, int *d_nids)
@@ -1849,6 +1849,7 @@ static const char *assoc_params_refusal(const AssocTableArgs &a, bool stream)
     if (a.min_hits < 1) return "min_hits must be at least 1";
     const int given = (a.out.tracks != nullptr) + (a.out.tinfo != nullptr) + (a.out.tcounts != nullptr);
     if (given != 0 && given != 3) return "d_tracks, d_tinfo and d_tcounts are given all three or none";
+    if (a.assign && a.match != 0 && a.match != DT_MATCH_ANY_LABEL) return "match must be 0 or DT_MATCH_ANY_LABEL: an order means nothing to an assignment";
     if (a.match < 0 || a.match > (DT_MATCH_BEST_FIRST | DT_MATCH_ANY_LABEL)) return "match must be a combination of DT_MATCH_BEST_FIRST and DT_MATCH_ANY_LABEL";
     return nullptr;
 }
@@ -1877,10 +1878,10 @@ static int associate_entry(dt_ctx *ctx, AssocTableArgs a, int n, bool stream, co
         if (a.cap != S.cap) return dt_fail(ctx, DT_ERR_ARG, "cap %d differs from the stream table's %d", a.cap, S.cap);
         a.tcap = S.tcap;
         // refused before the slot list is written, so that an error launches nothing
-        if (a.level >= ASSOC_MEMORY && assoc_table_lds_bytes(a.level, a.T, a.cap, a.tcap, a.match) > 160 * 1024)
+        if (a.level >= ASSOC_MEMORY && assoc_table_lds_bytes(a.level, a.T, a.cap, a.tcap, assoc_kernel_match(a)) > 160 * 1024)
             return dt_fail(ctx, DT_ERR_ARG, "a track table of %d entries%s%s does not fit the LDS", a.tcap,
                            a.level == ASSOC_MOTION ? " with velocities" : a.level == ASSOC_TRACKS ? " with velocities and hit counts" : "",
-                           (a.match & DT_MATCH_BEST_FIRST) ? " and the best-first order's words per box" : "");
+                           a.assign ? " and the assignment's words per box and per entry" : (a.match & DT_MATCH_BEST_FIRST) ? " and the best-first order's words per box" : "");
         if (launch_stream_slots(ctx->stream, h_slots, n, S.list.get(), nullptr)) return dt_fail(ctx, DT_ERR_DEVICE, "slot list launch failed");
         a.carry = assoc_carry(S, a.level);
     }
@@ -1888,8 +1889,11 @@ static int associate_entry(dt_ctx *ctx, AssocTableArgs a, int n, bool stream, co
     const double row_bytes = a.out.tracks ? (double)a.T * a.tcap * 12.0 : 0.0;
     const char *tag = level_tag[stream][a.level];
     if (a.match) tag = stream ? "stream_tracks_match" : "tracks_match";
+    if (a.assign) tag = stream ? "stream_tracks_assign" : "tracks_assign";
     ProfScope ps(ctx, "associate", 0.0, 4.0 * n * (box_bytes + row_bytes), tag);
     int rc;
+    if (!stream && a.assign && assoc_table_lds_bytes(a.level, a.T, a.cap, a.tcap, assoc_kernel_match(a)) > 160 * 1024)
+        return dt_fail(ctx, DT_ERR_ARG, "tcap: a track table of %d entries with the assignment's words per box and per entry does not fit the LDS", a.tcap);
     if (a.level != ASSOC_FRAME) rc = launch_associate_table(ctx->stream, a, n);
     else if (stream) rc = launch_associate_stream(ctx->stream, a.boxes, a.counts, n, a.T, a.cap, a.thr, a.ids, a.nids, a.carry);
     else rc = launch_associate(ctx->stream, a.boxes, a.counts, n, a.T, a.cap, a.thr, a.ids, a.nids);
@@ -1946,10 +1950,11 @@ extern "C" int dt_associate_stream_motion(dt_ctx *ctx, const float *d_boxes, con
 // the tracks entries with the track match policy of the call (DESIGN.md "Track match policy"); match = 0 is dt_associate[_stream]_tracks
 // itself.  The policy leaves no trace in a slot: calls with different `match` may follow each other on one slot.
 static int associate_tracks(dt_ctx *ctx, bool stream, const int *h_slots, const float *d_boxes, const int *d_counts, int n, int T, int cap, float thr,
-                            int max_age, int tcap, float gain, int min_hits, int match, int *d_ids, int *d_nids, int *d_gaps, const TrackReadout &out)
+                            int max_age, int tcap, float gain, int min_hits, int match, int *d_ids, int *d_nids, int *d_gaps, const TrackReadout &out,
+                            bool assign = false)
 {
     AssocTableArgs a = assoc_args(ASSOC_TRACKS, d_boxes, d_counts, T, cap, thr, d_ids, d_nids);
-    a.max_age = max_age; a.tcap = tcap; a.gain = gain; a.min_hits = min_hits; a.match = match; a.gaps = d_gaps; a.out = out;
+    a.max_age = max_age; a.tcap = tcap; a.gain = gain; a.min_hits = min_hits; a.match = match; a.gaps = d_gaps; a.out = out; a.assign = assign;
     return associate_entry(ctx, a, n, stream, h_slots);
 }
 
@@ -1984,6 +1989,24 @@ extern "C" int dt_associate_stream_tracks(dt_ctx *ctx, const float *d_boxes, con
 {
     return associate_tracks(ctx, true, h_slots, d_boxes, d_counts, n, T, cap, assoc_threshold, max_age, 0, gain, min_hits, 0, d_ids, d_nids, d_gaps,
                             TrackReadout{d_hits, d_tracks, d_tinfo, d_tcounts});
+}
+
+// the tracks entries with the optimal assignment as the match (DESIGN.md "Track assignment"); match: 0 or DT_MATCH_ANY_LABEL
+extern "C" int dt_associate_tracks_assign(dt_ctx *ctx, const float *d_boxes, const int *d_counts, int n_clips, int T, int cap,
+                                          float assoc_threshold, int max_age, int tcap, float gain, int min_hits, int match, int *d_ids,
+                                          int *d_nids, int *d_gaps, int *d_hits, float *d_tracks, int *d_tinfo, int *d_tcounts)
+{
+    return associate_tracks(ctx, false, nullptr, d_boxes, d_counts, n_clips, T, cap, assoc_threshold, max_age, tcap, gain, min_hits, match, d_ids, d_nids,
+                            d_gaps, TrackReadout{d_hits, d_tracks, d_tinfo, d_tcounts}, true);
+}
+
+extern "C" int dt_associate_stream_tracks_assign(dt_ctx *ctx, const float *d_boxes, const int *d_counts, int n, int T, int cap,
+                                                 float assoc_threshold, int max_age, float gain, int min_hits, int match, const int *h_slots,
+                                                 int *d_ids, int *d_nids, int *d_gaps, int *d_hits, float *d_tracks, int *d_tinfo,
+                                                 int *d_tcounts)
+{
+    return associate_tracks(ctx, true, h_slots, d_boxes, d_counts, n, T, cap, assoc_threshold, max_age, 0, gain, min_hits, match, d_ids, d_nids, d_gaps,
+                            TrackReadout{d_hits, d_tracks, d_tinfo, d_tcounts}, true);
 }
 
 // track scoring (DESIGN.md "Track scoring"): CLEAR-MOT counts of hypotheses against ground-truth tracks; the caller owns the state

@@ -23,6 +23,7 @@ DT_TRACK_FLOATS = 8      # a track read-out row: x, y, w, h, label, vx, vy, 0
 DT_TRACK_INTS = 4        # ... and its integers: id, age, hits, box
 DT_MATCH_BEST_FIRST = 1  # track match policy bits (dt_associate_tracks_match): candidate pairs taken best IoU first
 DT_MATCH_ANY_LABEL = 2   # ... labels not compared
+DT_ASSIGN_IOU_SCALE = 1048576  # track assignment (dt_associate_tracks_assign): a candidate weighs 1 + trunc(IoU * this)
 DT_SCORE_INTS = 8        # track scoring totals (dt_track_score): frames, gt boxes, hyp boxes, matches, switches, fragments, overflow, 0
 DT_SCORE_OBJ_INTS = 8    # ... an object row: gt id, last track id, present, matched, switches, fragments, last appearance matched, 0
 DT_SCORE_ANY_LABEL = 1   # ... flag bits: labels not compared
@@ -56,6 +57,7 @@ SYMBOLS = [
     "dt_track_score",
     "dt_detect_match", "dt_detect_rank",
     "dt_identity_overlap", "dt_assign_max",
+    "dt_associate_tracks_assign", "dt_associate_stream_tracks_assign",
 ]
 
 _lib = None
@@ -129,6 +131,8 @@ def load_library():
     L.dt_associate_stream_tracks.argtypes = [vp, vp, vp, ci, ci, ci, cf, ci, cf, ci, ctypes.POINTER(ci), vp, vp, vp, vp, vp, vp, vp]
     L.dt_associate_tracks_match.argtypes = [vp, vp, vp, ci, ci, ci, cf, ci, ci, cf, ci, ci, vp, vp, vp, vp, vp, vp, vp]
     L.dt_associate_stream_tracks_match.argtypes = [vp, vp, vp, ci, ci, ci, cf, ci, cf, ci, ci, ctypes.POINTER(ci), vp, vp, vp, vp, vp, vp, vp]
+    L.dt_associate_tracks_assign.argtypes = L.dt_associate_tracks_match.argtypes
+    L.dt_associate_stream_tracks_assign.argtypes = L.dt_associate_stream_tracks_match.argtypes
     L.dt_track_score.argtypes = [vp, vp, vp, vp, ci, vp, vp, vp, ci, ci, ci, ci, ci, cf, ci, ci, vp, vp, vp, vp, vp, vp]
     L.dt_identity_overlap.argtypes = [vp, vp, vp, vp, ci, vp, vp, vp, ci, ci, ci, ci, ci, cf, ci, ci, ci, vp, vp, vp, vp]
     L.dt_assign_max.argtypes = [vp, vp, ci, ci, vp, ci, ci, ci, ci, vp, vp, vp]
@@ -548,7 +552,7 @@ class Context(object):
                     tracks=t.empty((n, T, tcap, DT_TRACK_FLOATS), dtype=t.float32, device=self.device),
                     track_info=i32(n, T, tcap, DT_TRACK_INTS), track_counts=i32(n, T))
 
-    def associate_tracks(self, boxes, counts, assoc_threshold, max_age, gain, min_hits, track_cap=None, match=0, readout=True):
+    def associate_tracks(self, boxes, counts, assoc_threshold, max_age, gain, min_hits, track_cap=None, match=0, readout=True, assign=False):
         """The track-motion rule with a hit count per track and the read-out of the confirmed tracks (dt_associate_tracks).
         boxes [n_clips,T,cap,8], counts [n_clips,T] int32 -> dict: ids, gaps, hits [n_clips,T,cap], nids [n_clips] (ids, nids, gaps are
         associate(..., motion_gain=gain)'s; hits = frames in which the box's track has had a box), and per frame the tracks with
@@ -556,13 +560,21 @@ class Context(object):
         tracks [n_clips,T,tcap,8] (x, y, w, h, label, vx, vy, 0), track_info [n_clips,T,tcap,4] (id, age, hits, box; box = -1 for a
         coasting track), track_counts [n_clips,T]; rows from the count on are 0 / -1.  tcap = track_cap (None: cap).
         match: the track match policy, DT_MATCH_BEST_FIRST | DT_MATCH_ANY_LABEL bits (dt_associate_tracks_match); 0 = boxes in decode
-        order, entries of the box's label (dt_associate_tracks).  readout=False: no tracks / track_info / track_counts (the NULL triple)."""
+        order, entries of the box's label (dt_associate_tracks).  readout=False: no tracks / track_info / track_counts (the NULL triple).
+        assign=True: the match of a frame is the optimal (maximum summed IoU) one-to-one assignment (dt_associate_tracks_assign); match
+        may then be 0 or DT_MATCH_ANY_LABEL, and the library refuses DT_MATCH_BEST_FIRST."""
         t = self.torch
         assert boxes.is_cuda and boxes.is_contiguous() and counts.is_contiguous() and counts.dtype == t.int32
         n_clips, T, cap, _ = boxes.shape
         tcap = cap if track_cap is None else int(track_cap)
         r = self._tracks_outputs(n_clips, T, cap, max(tcap, 0), readout)
         self._sync_stream()
+        if assign:
+            self._check(self.lib.dt_associate_tracks_assign(self.h, _dptr(boxes), _dptr(counts), n_clips, T, cap, float(assoc_threshold),
+                                                            int(max_age), tcap, float(gain), int(min_hits), int(match), _dptr(r["ids"]),
+                                                            _dptr(r["nids"]), _dptr(r["gaps"]), _dptr(r["hits"]), _dptr(r.get("tracks")),
+                                                            _dptr(r.get("track_info")), _dptr(r.get("track_counts"))), "dt_associate_tracks_assign")
+            return r
         if match != 0:
             self._check(self.lib.dt_associate_tracks_match(self.h, _dptr(boxes), _dptr(counts), n_clips, T, cap, float(assoc_threshold),
                                                            int(max_age), tcap, float(gain), int(min_hits), int(match), _dptr(r["ids"]),
@@ -876,12 +888,13 @@ class Context(object):
                                                  arr, _dptr(ids), _dptr(nids)), "dt_associate_stream")
         return ids, nids
 
-    def associate_stream_tracks(self, boxes, counts, assoc_threshold, slots, max_age, gain, min_hits, match=0, readout=True):
+    def associate_stream_tracks(self, boxes, counts, assoc_threshold, slots, max_age, gain, min_hits, match=0, readout=True, assign=False):
         """associate_tracks for streams (dt_associate_stream_tracks): the slot's track table carries velocities and hit counts across
         calls; the read-out has the table's track_cap rows per frame.  The dict of associate_tracks.  After a call of associate_stream
         with a motion_gain the slot's tracks read as hits = 1; after one without, their velocities are forgotten too.
         match: the track match policy of this call (dt_associate_stream_tracks_match); it leaves nothing in the slot.
-        readout=False: no tracks / track_info / track_counts."""
+        readout=False: no tracks / track_info / track_counts.
+        assign=True: the optimal assignment as the match of this call (dt_associate_stream_tracks_assign); match 0 or DT_MATCH_ANY_LABEL."""
         t = self.torch
         assert boxes.is_cuda and boxes.is_contiguous() and counts.is_contiguous() and counts.dtype == t.int32
         n, T, cap, _ = boxes.shape
@@ -890,6 +903,13 @@ class Context(object):
             raise NativeError("dt_associate_stream_tracks failed (1): %d slots for %d streams" % (ns, n))
         r = self._tracks_outputs(n, T, cap, getattr(self, "_stream_tcap", None) or cap, readout)
         self._sync_stream()
+        if assign:
+            self._check(self.lib.dt_associate_stream_tracks_assign(self.h, _dptr(boxes), _dptr(counts), n, T, cap, float(assoc_threshold),
+                                                                   int(max_age), float(gain), int(min_hits), int(match), arr, _dptr(r["ids"]),
+                                                                   _dptr(r["nids"]), _dptr(r["gaps"]), _dptr(r["hits"]), _dptr(r.get("tracks")),
+                                                                   _dptr(r.get("track_info")), _dptr(r.get("track_counts"))),
+                        "dt_associate_stream_tracks_assign")
+            return r
         if match != 0:
             self._check(self.lib.dt_associate_stream_tracks_match(self.h, _dptr(boxes), _dptr(counts), n, T, cap, float(assoc_threshold),
                                                                   int(max_age), float(gain), int(min_hits), int(match), arr, _dptr(r["ids"]),

@@ -144,6 +144,10 @@ class MultiObjDetTracker(object):
     # itself still appears only with MIN_HITS)
     MATCH_BEST_FIRST = False
     MATCH_ANY_LABEL = False
+    # build-defined track assignment: the match of a frame is the optimal one-to-one assignment (the largest summed
+    # IoU, the Hungarian step of the SORT family) instead of a greedy pass; MATCH_ANY_LABEL still applies, MATCH_BEST_FIRST beside it is
+    # refused by the library.  The result carries `gaps` and `hits` as with a MATCH_* policy
+    MATCH_OPTIMAL = False
     # build-defined frame ingest: track_stream on lists of device frames exchanges channels 0 and 2 while ingesting
     INGEST_SWAP_RB = False
     # build-defined frame views: None = lists of frames are stretched (dt_ingest_frames).  "letterbox" / "stretch" = they
@@ -222,7 +226,7 @@ class MultiObjDetTracker(object):
           counts [n_clips,T]        boxes per frame
           ids    [n_clips,T,cap]    track ids (-1 in unused slots), per clip from 0
           nids   [n_clips]          ids opened per clip
-          gaps   [n_clips,T,cap]    only with MAX_AGE > 0, a MOTION_GAIN, MIN_HITS or a MATCH_* policy: frames the box's track had missed (0 unbroken, -1 new id / unused)
+          gaps   [n_clips,T,cap]    only with MAX_AGE > 0, a MOTION_GAIN, MIN_HITS or a MATCH_* policy (MATCH_OPTIMAL included): frames the box's track had missed (0 unbroken, -1 new id / unused)
         and only with MIN_HITS (the track read-out, mi355_dt.Context.associate_tracks):
           hits   [n_clips,T,cap]    frames in which the box's track has had a box (also with a MATCH_* policy alone)
           tracks [n_clips,T,tcap,8], track_info [n_clips,T,tcap,4], track_counts [n_clips,T]   the confirmed tracks of every frame
@@ -275,10 +279,10 @@ class MultiObjDetTracker(object):
         """the association entry the class attributes select, on a call's boxes: the result dict without `netout`"""
         ctx = self.model.ctx
         match = self._match_policy()
-        if self.MIN_HITS is not None or match:
+        if self.MIN_HITS is not None or match or self.MATCH_OPTIMAL:
             a = ctx.associate_stream_tracks(boxes, counts, self.ASSOC_THRESHOLD, slots, self.MAX_AGE,
                                             0.0 if self.MOTION_GAIN is None else self.MOTION_GAIN, self.MIN_HITS or 1, match=match,
-                                            readout=self.MIN_HITS is not None)
+                                            readout=self.MIN_HITS is not None, assign=bool(self.MATCH_OPTIMAL))
             return dict(a, boxes=boxes, counts=counts)
         if self.MOTION_GAIN is not None:
             ids, nids, gaps = ctx.associate_stream(boxes, counts, self.ASSOC_THRESHOLD, slots, max_age=self.MAX_AGE, want_gaps=True,
@@ -319,9 +323,10 @@ class MultiObjDetTracker(object):
         boxes = r["boxes"].reshape(n_clips, T, cap, mi355_dt.DT_BOX_FLOATS)
         counts = r["counts"].reshape(n_clips, T)
         match = self._match_policy()
-        if self.MIN_HITS is not None or match:
+        if self.MIN_HITS is not None or match or self.MATCH_OPTIMAL:
             a = ctx.associate_tracks(boxes, counts, self.ASSOC_THRESHOLD, self.MAX_AGE, 0.0 if self.MOTION_GAIN is None else self.MOTION_GAIN,
-                                     self.MIN_HITS or 1, track_cap=self.TRACK_CAP, match=match, readout=self.MIN_HITS is not None)
+                                     self.MIN_HITS or 1, track_cap=self.TRACK_CAP, match=match, readout=self.MIN_HITS is not None,
+                                     assign=bool(self.MATCH_OPTIMAL))
             return dict(a, boxes=boxes, counts=counts, netout=trk)
         if self.MOTION_GAIN is not None:
             ids, nids, gaps = ctx.associate(boxes, counts, self.ASSOC_THRESHOLD, max_age=self.MAX_AGE, track_cap=self.TRACK_CAP,
@@ -343,7 +348,7 @@ class MultiObjDetTracker(object):
         z = lambda shape, dt: torch.zeros(shape, dtype=dt, device=ctx.device)
         res = dict(boxes=z((0, T, cap, mi355_dt.DT_BOX_FLOATS), torch.float32), counts=z((0, T), torch.int32),
                    ids=z((0, T, cap), torch.int32), nids=z((0,), torch.int32), netout=None)
-        if self.MIN_HITS is None and self._match_policy():
+        if self.MIN_HITS is None and (self._match_policy() or self.MATCH_OPTIMAL):
             res.update(gaps=z((0, T, cap), torch.int32), hits=z((0, T, cap), torch.int32))
         if self.MIN_HITS is not None:
             tcap = cap if self.TRACK_CAP is None else self.TRACK_CAP
