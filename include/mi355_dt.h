@@ -75,6 +75,7 @@ DT_API int dt_set_stream(dt_ctx *ctx, void *hip_stream);
  * and the two detection scoring entries dt_detect_match, dt_detect_rank
  * and the two identity scoring entries dt_identity_overlap, dt_assign_max
  * and the two track assignment entries dt_associate_tracks_assign, dt_associate_stream_tracks_assign
+ * and the three Winograd transform test entries dt_wino_geometry, dt_wino_input, dt_wino_output
  * -- additions only, the number stayed; 1.07: 1.06 + dt_gemm_split, dt_policy_set) */
 DT_API int dt_abi_version(void);
 
@@ -740,6 +741,36 @@ DT_API int dt_gemm_split_bf16(dt_ctx *ctx, const float *d_v, const float *d_u, i
  * in the epilogue (P <= 64). */
 DT_API int dt_gemm_split(dt_ctx *ctx, const float *d_v, const float *d_u, int P, int Mt, int K, int N, int half, int nt,
                          float *d_m);
+
+/* The Winograd transforms ALONE (csrc/winograd.hip), without the GEMM between them: the production tile geometry (frame mosaics under
+ * the context's DT_WINO_MOSAIC policy included) and the production launchers on caller data.  ts = 2, 4 or 6.
+ * h_geom[DT_WINO_GEOM_INTS] receives g, ph, pw, th, tw, Mt, Mp (g x g frames per virtual image at pitch ph / pw, th x tw tiles of ts x ts
+ * outputs on it, Mt tiles in all, Mp = Mt rounded up to 256) and then WHICH KERNEL the launcher chose, with what grid: form (input:
+ * DT_WIN_*, output: DT_WOUT_*), workgroups, threads per workgroup.  dt_wino_geometry fills the first seven alone (pooled != 0: the
+ * geometry of a launch that pools -- an even pitch). */
+#define DT_WINO_GEOM_INTS 10
+enum { DT_WIN_TPI2 = 1, DT_WIN_TPI4, DT_WIN_TPI6, DT_WIN_TPI4_S3, DT_WIN_COOP6, DT_WIN_S3_6, DT_WIN_S3_4, DT_WIN_H2_6, DT_WIN_H2_4 };
+enum { DT_WOUT_TPI6 = 1, DT_WOUT_TPI4, DT_WOUT_TPI2, DT_WOUT_COOP6, DT_WOUT_GATES6, DT_WOUT_GATES4, DT_WOUT_GATES2 };
+DT_API int dt_wino_geometry(dt_ctx *ctx, int ts, int B, int H, int W, int pooled, int *h_geom);
+/* Input transform Bt d B of d_in [B][H][W][in_ld >= C] (frame stride in_bs floats) into d_v (v_bytes bytes), in the form nt:
+ *   0: float32 V [P][Mt][C], P = (ts+2)^2, position p = (ts+2) xi + nu;
+ *   3: three bf16 terms [P][3][C/16][Mp][16] (16-bit words; ts = 6: C % 32 == 0, ts = 4: C % 16 == 0);
+ *   2: two fp16 terms [P][2][C/16][Mp][16] of V[p] * 2^(14 - floor(log2 max|d_in|)) * rowfac[xi] * rowfac[nu] as the split GEMM reads them
+ *      (ts = 4 / 6, C % 32 == 0, dense frames); max |d_in| is measured into max-|x| slot 57.
+ * Rows Mt .. Mp-1 of the split layouts are not written.  force_form (fp32, ts = 6: 1 = one thread per item, 2 = lane-cooperative) and wg_cap
+ * (> 0: at most so many workgroups) are WinoArgs' test-only fields; 0 = what production launches.  DT_ERR_ARG for what the launcher refuses. */
+DT_API int dt_wino_input(dt_ctx *ctx, const float *d_in, int B, int H, int W, int C, int in_ld, long long in_bs, int ts, int pooled, int nt,
+                         int force_form, int wg_cap, void *d_v, long long v_bytes, int *h_geom);
+/* Output transform At m A of d_m [P][Mt][m_ld >= N] (m_floats floats) for the geometry of (B, H, W, ts, d_out2 != null):
+ *   plain form: + d_bias [N] (or null), + d_bias16 [16][N] border corrections (or null; slope 1, d_out only), LeakyReLU(slope), to
+ *     d_out [B][H][W][out_ld >= N] and / or its 2x2 max-pooled d_out2 [B][H/2][W/2][out2_ld >= N] (either may be null); publish != 0: max |x| of
+ *     the stored values (the pooled ones where d_out2 is set) into max-|x| slot 57, zeroed first (dt_amax_read);
+ *   gate form (d_cstate != null; N = 4 U, columns [j/32][gate][j%32], N % 128 == 0): z = transform + d_xproj [B][H][W][xp_ld >= N], the ConvLSTM2D
+ *     update of d_cstate [B][H][W][c_ld >= U] in place, h to d_out [B][H][W][out_ld >= U].
+ * force_form (ts = 6, plain form), wg_cap, h_geom and errors as for dt_wino_input. */
+DT_API int dt_wino_output(dt_ctx *ctx, const float *d_m, long long m_floats, int m_ld, int N, int B, int H, int W, int ts, const float *d_bias,
+                          const float *d_bias16, float slope, float *d_out, int out_ld, float *d_out2, int out2_ld, int publish,
+                          const float *d_xproj, int xp_ld, float *d_cstate, int c_ld, int force_form, int wg_cap, int *h_geom);
 
 /* ---- tuning / test knobs ------------------------------------------------- *
  * The DT_* environment variables of DESIGN.md's appendix are read in dt_create (no launch path calls getenv);

@@ -138,7 +138,33 @@ struct WinoArgs {
     float *cstate;
     long long c_bs;
     int c_ld;
+    // test only (dt_wino_input / dt_wino_output), both 0 in production -- like ConvArgs::force_cfg
+    int force_form;         // fp32 F(6x6), where two kernels exist for the same arguments: 1 = the thread-per-item kernel, 2 = the lane-cooperative one
+    int wg_cap;             // > 0: at most this many workgroups, on top of the launcher's own cap (the grid-stride loops at small shapes)
 };
+// Which kernel a transform launch takes and with what grid: decided by choose_wino_input / choose_wino_output (winograd.hip; pure: no launch), the one
+// place launch_wino_input / launch_wino_output switch on.  form 0 = the arguments are refused (the launchers return 2).
+enum { WIN_TPI2 = 1,     // wino_input_kernel<2,4>
+       WIN_TPI4,         // wino_input_kernel<4,4>
+       WIN_TPI6,         // wino_input_kernel<6,2>
+       WIN_TPI4_S3,      // wino_input_kernel<4,4,true>: three bf16 terms, C % 32 != 0
+       WIN_COOP6,        // wino_input_coop6_kernel
+       WIN_S3_6,         // wino_input_s3_kernel<6>
+       WIN_S3_4,         // wino_input_s3_kernel<4>
+       WIN_H2_6,         // wino_input_s3_kernel<6,2>
+       WIN_H2_4 };       // wino_input_s3_kernel<4,2>
+enum { WOUT_TPI6 = 1,    // wino_output_kernel<6,2>
+       WOUT_TPI4,        // wino_output_kernel<4,2>
+       WOUT_TPI2,        // wino_output_kernel<2,4>
+       WOUT_COOP6,       // wino_output_coop6_kernel
+       WOUT_GATES6,      // wino_output_gates_kernel<6,1>
+       WOUT_GATES4,      // wino_output_gates_kernel<4,1>
+       WOUT_GATES2 };    // wino_output_gates_kernel<2,4>
+static_assert(WIN_TPI2 == DT_WIN_TPI2 && WIN_H2_4 == DT_WIN_H2_4 && WOUT_TPI6 == DT_WOUT_TPI6 && WOUT_GATES2 == DT_WOUT_GATES2,
+              "the codes dt_wino_input / dt_wino_output report (mi355_dt.h)");
+struct WinoLaunch { int form; unsigned grid, threads; };
+WinoLaunch choose_wino_input(const WinoArgs &a);
+WinoLaunch choose_wino_output(const WinoArgs &a, int gates);
 // fused Winograd F(4x4,3x3) for the early layers (Cin 32 / 64 / 128 -> Cout 64 / 128 / 256: conv_2, conv_3, conv_5; conv_6 / conv_8 on request), wino4s_fused.hip
 struct Wino4FusedArgs {
     const float *in;     // NHWC, pixel stride in_ld, frame stride in_bs

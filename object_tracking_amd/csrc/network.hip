@@ -2913,6 +2913,103 @@ extern "C" int dt_gemm_split_bf16(dt_ctx *ctx, const float *d_v, const float *d_
     return dt_gemm_split(ctx, d_v, d_u, P, Mt, K, N, half, 3, d_m);
 }
 
+// winograd.hip's transforms ALONE on caller data (tests/test_gpu_wino_transform.py): the production geometry rule, the production launchers, nothing else.
+// h_geom[DT_WINO_GEOM_INTS] = g, ph, pw, th, tw, Mt, Mp, then what the launcher's choice function decided: form (WIN_* / WOUT_*), workgroups, threads.
+static void wino_test_geometry(dt_ctx *ctx, int ts, int B, int H, int W, bool pooled, WinoArgs &w, int *h_geom)
+{
+    const WinoGeom q = wino_geometry(ctx, ts, B, H, W, pooled);
+    w.B = B; w.H = H; w.W = W; w.ts = ts;
+    w.g = q.g; w.ph = q.ph; w.pw = q.pw; w.th = q.th; w.tw = q.tw; w.Mt = q.Mt;
+    w.Mp = (q.Mt + 255) / 256 * 256;
+    const int geom[7] = {q.g, q.ph, q.pw, q.th, q.tw, q.Mt, w.Mp};
+    memcpy(h_geom, geom, sizeof(geom));
+    h_geom[7] = h_geom[8] = h_geom[9] = 0;
+}
+static void wino_test_report(const WinoLaunch &l, int *h_geom) { h_geom[7] = l.form; h_geom[8] = (int)l.grid; h_geom[9] = (int)l.threads; }
+static bool wino_test_shape_ok(int ts, int B, int H, int W) { return (ts == 2 || ts == 4 || ts == 6) && B > 0 && H > 0 && W > 0 && (long long)B * H * W < (1ll << 24); }
+
+extern "C" int dt_wino_geometry(dt_ctx *ctx, int ts, int B, int H, int W, int pooled, int *h_geom)
+{
+    if (!ctx || !h_geom) return dt_fail(ctx, DT_ERR_ARG, "null argument");
+    if (!wino_test_shape_ok(ts, B, H, W)) return dt_fail(ctx, DT_ERR_ARG, "dt_wino_geometry: unsupported shape ts=%d B=%d H=%d W=%d", ts, B, H, W);
+    policy_refresh(ctx);   // test entry point (see dt_conv2d)
+    WinoArgs w{};
+    wino_test_geometry(ctx, ts, B, H, W, pooled != 0, w, h_geom);
+    return DT_OK;
+}
+
+extern "C" int dt_wino_input(dt_ctx *ctx, const float *d_in, int B, int H, int W, int C, int in_ld, long long in_bs, int ts, int pooled, int nt,
+                             int force_form, int wg_cap, void *d_v, long long v_bytes, int *h_geom)
+{
+    if (!ctx || !d_in || !d_v || !h_geom) return dt_fail(ctx, DT_ERR_ARG, "null argument");
+    call_begin(ctx, 0);
+    if (!wino_test_shape_ok(ts, B, H, W) || C <= 0 || in_ld < C || in_bs < (long long)H * W * in_ld || in_bs % 4 || (nt != 0 && nt != 2 && nt != 3) || force_form < 0 ||
+        force_form > 2 || wg_cap < 0)
+        return dt_fail(ctx, DT_ERR_ARG, "dt_wino_input: unsupported arguments ts=%d B=%d H=%d W=%d C=%d in_ld=%d in_bs=%lld nt=%d force_form=%d wg_cap=%d", ts, B, H, W,
+                       C, in_ld, in_bs, nt, force_form, wg_cap);
+    policy_refresh(ctx);   // test entry point (see dt_conv2d)
+    WinoArgs w{};
+    wino_test_geometry(ctx, ts, B, H, W, pooled != 0, w, h_geom);
+    const long long P = (ts + 2) * (ts + 2);
+    const long long need = nt ? P * nt * w.Mp * C * (long long)sizeof(unsigned short) : P * w.Mt * C * (long long)sizeof(float);
+    if (v_bytes < need) return dt_fail(ctx, DT_ERR_ARG, "dt_wino_input: V takes %lld bytes, the buffer has %lld", need, v_bytes);
+    w.in = d_in; w.in_bs = in_bs; w.in_ld = in_ld; w.C = C;
+    w.force_form = force_form; w.wg_cap = wg_cap;
+    if (nt) { w.v_s3 = static_cast<unsigned short *>(d_v); w.nt = nt; }
+    else w.v = static_cast<float *>(d_v);
+    if (nt == 2) {      // V's power of two comes from the input's max |x|, measured into the test slot as run_wino does it (dense frames: ONE tensor of rows)
+        if (in_bs != (long long)H * W * in_ld || C % 4) return dt_fail(ctx, DT_ERR_ARG, "dt_wino_input: the fp16 form measures B*H*W dense rows of C %% 4 == 0 channels");
+        w.amax = ensure_amax(ctx, d_in, (long long)B * H * W, C, in_ld, AMAX_TEST);
+        if (!w.amax) return DT_ERR_DEVICE;
+    }
+    const WinoLaunch l = choose_wino_input(w);
+    if (!l.form) return dt_fail(ctx, DT_ERR_ARG, "dt_wino_input: the launcher refuses ts=%d C=%d in_ld=%d nt=%d (C %% 4, the split forms' C %% 32 / C %% 16 and tile sizes)", ts, C, in_ld, nt);
+    wino_test_report(l, h_geom);
+    const int rc = launch_wino_input(ctx->stream, w);
+    if (rc) return dt_fail(ctx, launch_code(rc), "dt_wino_input: launch failed (rc=%d)", rc);
+    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+    return DT_OK;
+}
+
+extern "C" int dt_wino_output(dt_ctx *ctx, const float *d_m, long long m_floats, int m_ld, int N, int B, int H, int W, int ts, const float *d_bias,
+                              const float *d_bias16, float slope, float *d_out, int out_ld, float *d_out2, int out2_ld, int publish, const float *d_xproj, int xp_ld,
+                              float *d_cstate, int c_ld, int force_form, int wg_cap, int *h_geom)
+{
+    if (!ctx || !d_m || !h_geom || (!d_out && !d_out2)) return dt_fail(ctx, DT_ERR_ARG, "null argument");
+    call_begin(ctx, 0);
+    const bool gates = d_cstate != nullptr;
+    if (!wino_test_shape_ok(ts, B, H, W) || N <= 0 || m_ld < N || force_form < 0 || force_form > 2 || wg_cap < 0 || (d_out && out_ld < (gates ? N / 4 : N)) ||
+        (d_out2 && out2_ld < N))
+        return dt_fail(ctx, DT_ERR_ARG, "dt_wino_output: unsupported arguments ts=%d B=%d H=%d W=%d N=%d m_ld=%d out_ld=%d out2_ld=%d force_form=%d wg_cap=%d", ts, B, H, W,
+                       N, m_ld, out_ld, out2_ld, force_form, wg_cap);
+    if (gates && (!d_xproj || !d_out || d_out2 || d_bias || d_bias16 || publish || xp_ld < N || c_ld < N / 4))
+        return dt_fail(ctx, DT_ERR_ARG, "dt_wino_output: the gate form takes xproj [..][xp_ld >= N], cstate [..][c_ld >= N/4] and h (d_out) alone");
+    policy_refresh(ctx);   // test entry point (see dt_conv2d)
+    WinoArgs w{};
+    wino_test_geometry(ctx, ts, B, H, W, d_out2 != nullptr, w, h_geom);
+    const long long P = (ts + 2) * (ts + 2), need = P * w.Mt * m_ld;
+    if (m_floats < need) return dt_fail(ctx, DT_ERR_ARG, "dt_wino_output: M' takes %lld floats, the buffer has %lld", need, m_floats);
+    w.m = d_m; w.m_ld = m_ld; w.N = N; w.bias = d_bias; w.bias16 = d_bias16; w.slope = slope;
+    w.out = d_out; w.out_ld = out_ld; w.out_bs = (long long)H * W * out_ld; w.out2 = d_out2; w.out2_ld = out2_ld;
+    w.xproj = d_xproj; w.xp_ld = xp_ld; w.xp_bs = (long long)H * W * xp_ld;
+    w.cstate = d_cstate; w.c_ld = c_ld; w.c_bs = (long long)H * W * c_ld;
+    w.force_form = force_form; w.wg_cap = wg_cap;
+    if (publish) {
+        w.amax_out = amax_slot(ctx, AMAX_TEST);
+        if (!w.amax_out) return dt_fail(ctx, DT_ERR_STATE, "max-|x| slots not allocated");
+        HIP_TRY(ctx, hipMemsetAsync(w.amax_out, 0, DT_AMAX_WORDS * sizeof(unsigned), ctx->stream));
+    }
+    const WinoLaunch l = choose_wino_output(w, gates);
+    if (!l.form)
+        return dt_fail(ctx, DT_ERR_ARG, "dt_wino_output: the launcher refuses ts=%d N=%d m_ld=%d out_ld=%d out2_ld=%d slope=%g%s (N %% 4, N %% 128 for gates, row strides %% 4; "
+                       "bias16 needs slope 1, a full-resolution output and no pooling)", ts, N, m_ld, out_ld, out2_ld, (double)slope, d_bias16 ? " bias16" : "");
+    wino_test_report(l, h_geom);
+    const int rc = launch_wino_output(ctx->stream, w, gates);
+    if (rc) return dt_fail(ctx, launch_code(rc), "dt_wino_output: launch failed (rc=%d)", rc);
+    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+    return DT_OK;
+}
+
 // Re-reads the tuning / test knobs from the environment into the context (they are otherwise read in dt_create and by the
 // layer-level test entry points); the context's pin override stays.  Knobs that shape the uploaded weights (DT_WINO, DT_WINO_TILE)
 // take effect at the next weight load.

@@ -869,41 +869,68 @@ static inline bool wino_pitch_ok(const WinoArgs &a)
     return a.ph > a.H && a.pw > a.W && !(a.out2 && ((a.ph | a.pw) & 1));
 }
 
-int launch_wino_input(hipStream_t st, const WinoArgs &a)
+// ---- which kernel a launch takes: decided once, apart from launching (like network.hip:choose_conv / choose_wino) ---------------------
+static WinoLaunch wino_capped(int form, long long grid, unsigned threads, const WinoArgs &a)
 {
-    if (a.C % 4 || a.in_ld % 4 || a.Mt <= 0 || (a.ts != 2 && a.ts != 4 && a.ts != 6) || !wino_pitch_ok(a)) return 2;
+    if (a.wg_cap > 0 && grid > a.wg_cap) grid = a.wg_cap;      // (test only: WinoArgs::wg_cap)
+    return WinoLaunch{form, (unsigned)(grid < 1 ? 1 : grid), threads};
+}
+// one thread per item: 64 or 256 threads per workgroup, at most 8192 workgroups (wino_threads / wino_blocks)
+static WinoLaunch wino_tpi(int form, long long items, const WinoArgs &a) { return wino_capped(form, wino_blocks(items), wino_threads(items), a); }
+// eight lanes per (tile, 4 channels) item, 32 items per workgroup
+static WinoLaunch wino_coop(int form, long long items4, const WinoArgs &a)
+{
+    const long long wgs = (items4 + WINO_THREADS / 8 - 1) / (WINO_THREADS / 8);
+    return wino_capped(form, wgs < 65536 ? wgs : 65536, WINO_THREADS, a);
+}
+static const WinoLaunch WINO_REFUSED{0, 0, 0};
+
+WinoLaunch choose_wino_input(const WinoArgs &a)
+{
+    if (a.C % 4 || a.in_ld % 4 || a.Mt <= 0 || (a.ts != 2 && a.ts != 4 && a.ts != 6) || !wino_pitch_ok(a)) return WINO_REFUSED;
+    // the 8-channel split producers: 16 items per workgroup over Mt rounded up to whole groups of 4 tiles
+    const long long s3_wgs = ((long long)((a.Mt + 3) & ~3) * (a.C / 8) + WINO_S3IN_THREADS / 8 - 1) / (WINO_S3IN_THREADS / 8);
     if (a.v_s3 && a.nt == 2) {      // the fp16 form: the cooperative 8-channel producer only
-        if ((a.ts != 6 && a.ts != 4) || a.C % 32 || a.Mp < a.Mt || !a.amax) return 2;
-        const long long wgs = ((long long)((a.Mt + 3) & ~3) * (a.C / 8) + WINO_S3IN_THREADS / 8 - 1) / (WINO_S3IN_THREADS / 8);
+        if ((a.ts != 6 && a.ts != 4) || a.C % 32 || a.Mp < a.Mt || !a.amax) return WINO_REFUSED;
         // workgroup cap: 24576 (grid-stride beyond) instead of one workgroup per 16 items -- measured in the step on two boxes
         // (profiles/r06_experiments.txt section 9): 9.84-10.09 -> 9.34-9.45 ms per step for caps of 8192 .. 32768, back to 9.8 at 65536
         const long long cap = 24576;
-        const unsigned grid = (unsigned)(wgs < cap ? wgs : cap);
-        if (a.ts == 6) hipLaunchKernelGGL((wino_input_s3_kernel<6, 2>), dim3(grid), dim3(WINO_S3IN_THREADS), 0, st, a);
-        else hipLaunchKernelGGL((wino_input_s3_kernel<4, 2>), dim3(grid), dim3(WINO_S3IN_THREADS), 0, st, a);
-    } else if (a.v_s3 && a.ts == 4) {
-        if (a.C % 16 || a.Mp < a.Mt) return 2;
-        if (a.C % 32 == 0) {      // the cooperative 8-channel form (20 instead of 44 us per recurrent step at 48 clips)
-            const long long wgs = ((long long)((a.Mt + 3) & ~3) * (a.C / 8) + WINO_S3IN_THREADS / 8 - 1) / (WINO_S3IN_THREADS / 8);
-            hipLaunchKernelGGL(wino_input_s3_kernel<4>, dim3((unsigned)(wgs < 262144 ? wgs : 262144)), dim3(WINO_S3IN_THREADS), 0, st, a);
-        } else
-            hipLaunchKernelGGL((wino_input_kernel<4, 4, true>), dim3(wino_blocks((long long)a.Mt * (a.C / 4))), dim3(wino_threads((long long)a.Mt * (a.C / 4))), 0, st, a);
-    } else if (a.v_s3) {
-        if (a.ts != 6 || a.C % 32 || a.Mp < a.Mt) return 2;
-        const long long wgs = ((long long)((a.Mt + 3) & ~3) * (a.C / 8) + WINO_S3IN_THREADS / 8 - 1) / (WINO_S3IN_THREADS / 8);
-        hipLaunchKernelGGL(wino_input_s3_kernel<6>, dim3((unsigned)(wgs < 262144 ? wgs : 262144)), dim3(WINO_S3IN_THREADS), 0, st, a);
-    } else if (a.ts == 6 && wino_coop_wanted((long long)a.Mt * (a.C / 2))) {
-        const long long wgs = ((long long)a.Mt * (a.C / 4) + WINO_THREADS / 8 - 1) / (WINO_THREADS / 8);
-        hipLaunchKernelGGL(wino_input_coop6_kernel, dim3((unsigned)(wgs < 65536 ? wgs : 65536)), dim3(WINO_THREADS), 0, st, a);
-    } else if (a.ts == 6)
-        hipLaunchKernelGGL((wino_input_kernel<6, 2>), dim3(wino_blocks((long long)a.Mt * (a.C / 2))), dim3(wino_threads((long long)a.Mt * (a.C / 2))), 0,
-                           st, a);
-    else if (a.ts == 2)
-        hipLaunchKernelGGL((wino_input_kernel<2, 4>), dim3(wino_blocks((long long)a.Mt * (a.C / 4))), dim3(wino_threads((long long)a.Mt * (a.C / 4))), 0,
-                           st, a);
-    else   // 188 VGPRs, two waves per SIMD: still 7 % faster than <4,2> (1 KiB per wave per plane store)
-        hipLaunchKernelGGL((wino_input_kernel<4, 4>), dim3(wino_blocks((long long)a.Mt * (a.C / 4))), dim3(wino_threads((long long)a.Mt * (a.C / 4))), 0,
-                           st, a);
+        return wino_capped(a.ts == 6 ? WIN_H2_6 : WIN_H2_4, s3_wgs < cap ? s3_wgs : cap, WINO_S3IN_THREADS, a);
+    }
+    if (a.v_s3 && a.ts == 4) {
+        if (a.C % 16 || a.Mp < a.Mt) return WINO_REFUSED;
+        if (a.C % 32 == 0)      // the cooperative 8-channel form (20 instead of 44 us per recurrent step at 48 clips)
+            return wino_capped(WIN_S3_4, s3_wgs < 262144 ? s3_wgs : 262144, WINO_S3IN_THREADS, a);
+        return wino_tpi(WIN_TPI4_S3, (long long)a.Mt * (a.C / 4), a);
+    }
+    if (a.v_s3) {
+        if (a.ts != 6 || a.C % 32 || a.Mp < a.Mt) return WINO_REFUSED;
+        return wino_capped(WIN_S3_6, s3_wgs < 262144 ? s3_wgs : 262144, WINO_S3IN_THREADS, a);
+    }
+    if (a.ts == 6) {
+        const bool coop = a.force_form ? a.force_form == 2 : wino_coop_wanted((long long)a.Mt * (a.C / 2));
+        return coop ? wino_coop(WIN_COOP6, (long long)a.Mt * (a.C / 4), a) : wino_tpi(WIN_TPI6, (long long)a.Mt * (a.C / 2), a);
+    }
+    // F(4x4): 188 VGPRs, two waves per SIMD: still 7 % faster than <4,2> (1 KiB per wave per plane store)
+    return wino_tpi(a.ts == 2 ? WIN_TPI2 : WIN_TPI4, (long long)a.Mt * (a.C / 4), a);
+}
+
+int launch_wino_input(hipStream_t st, const WinoArgs &a)
+{
+    const WinoLaunch l = choose_wino_input(a);
+    const dim3 grid(l.grid), block(l.threads);
+    switch (l.form) {
+    case WIN_H2_6: hipLaunchKernelGGL((wino_input_s3_kernel<6, 2>), grid, block, 0, st, a); break;
+    case WIN_H2_4: hipLaunchKernelGGL((wino_input_s3_kernel<4, 2>), grid, block, 0, st, a); break;
+    case WIN_S3_6: hipLaunchKernelGGL(wino_input_s3_kernel<6>, grid, block, 0, st, a); break;
+    case WIN_S3_4: hipLaunchKernelGGL(wino_input_s3_kernel<4>, grid, block, 0, st, a); break;
+    case WIN_TPI4_S3: hipLaunchKernelGGL((wino_input_kernel<4, 4, true>), grid, block, 0, st, a); break;
+    case WIN_COOP6: hipLaunchKernelGGL(wino_input_coop6_kernel, grid, block, 0, st, a); break;
+    case WIN_TPI6: hipLaunchKernelGGL((wino_input_kernel<6, 2>), grid, block, 0, st, a); break;
+    case WIN_TPI2: hipLaunchKernelGGL((wino_input_kernel<2, 4>), grid, block, 0, st, a); break;
+    case WIN_TPI4: hipLaunchKernelGGL((wino_input_kernel<4, 4>), grid, block, 0, st, a); break;
+    default: return 2;
+    }
     return hipGetLastError() == hipSuccess ? 0 : 1;
 }
 
@@ -913,33 +940,38 @@ bool wino_output_fills_amax(const WinoArgs &a, int gates)
 {
     return !gates && a.amax_out != nullptr;
 }
+WinoLaunch choose_wino_output(const WinoArgs &a, int gates)
+{
+    if (a.m_ld % 4 || a.Mt <= 0 || (a.ts != 2 && a.ts != 4 && a.ts != 6) || !wino_pitch_ok(a)) return WINO_REFUSED;
+    if (gates) {
+        if (a.N % 128 || a.out_ld % 4 || a.c_ld % 4 || a.xp_ld % 4) return WINO_REFUSED;
+        if (a.ts == 6) return wino_tpi(WOUT_GATES6, (long long)a.Mt * (a.N / 4), a);
+        if (a.ts == 2) return wino_tpi(WOUT_GATES2, (long long)a.Mt * (a.N / 16), a);
+        return wino_tpi(WOUT_GATES4, (long long)a.Mt * (a.N / 4), a);
+    }
+    // vector stores need aligned rows; ragged N (conv_23-like heads) never takes this path
+    if (a.N % 4 || (a.out && a.out_ld % 4) || (a.out2 && a.out2_ld % 4)) return WINO_REFUSED;
+    if (a.bias16 && (a.slope != 1.0f || a.out2 || !a.out)) return WINO_REFUSED;      // the border corrections: linear, full-resolution epilogue only
+    if (a.ts == 6) {
+        const bool coop = a.force_form ? a.force_form == 2 : wino_coop_wanted((long long)a.Mt * (a.N / 2));
+        return coop ? wino_coop(WOUT_COOP6, (long long)a.Mt * (a.N / 4), a) : wino_tpi(WOUT_TPI6, (long long)a.Mt * (a.N / 2), a);
+    }
+    if (a.ts == 2) return wino_tpi(WOUT_TPI2, (long long)a.Mt * (a.N / 4), a);
+    return wino_tpi(WOUT_TPI4, (long long)a.Mt * (a.N / 2), a);      // <4,4> measured equal
+}
 int launch_wino_output(hipStream_t st, const WinoArgs &a, int gates)
 {
-    if (a.m_ld % 4 || a.Mt <= 0 || (a.ts != 2 && a.ts != 4 && a.ts != 6) || !wino_pitch_ok(a)) return 2;
-    if (gates) {
-        if (a.N % 128 || a.out_ld % 4 || a.c_ld % 4 || a.xp_ld % 4) return 2;
-        if (a.ts == 6)
-            hipLaunchKernelGGL((wino_output_gates_kernel<6, 1>), dim3(wino_blocks((long long)a.Mt * (a.N / 4))), dim3(wino_threads((long long)a.Mt * (a.N / 4))), 0, st, a);
-        else if (a.ts == 2)
-            hipLaunchKernelGGL((wino_output_gates_kernel<2, 4>), dim3(wino_blocks((long long)a.Mt * (a.N / 16))), dim3(wino_threads((long long)a.Mt * (a.N / 16))), 0, st, a);
-        else
-            hipLaunchKernelGGL((wino_output_gates_kernel<4, 1>), dim3(wino_blocks((long long)a.Mt * (a.N / 4))), dim3(wino_threads((long long)a.Mt * (a.N / 4))), 0, st, a);
-    } else {
-        // vector stores need aligned rows; ragged N (conv_23-like heads) never takes this path
-        if (a.N % 4 || (a.out && a.out_ld % 4) || (a.out2 && a.out2_ld % 4)) return 2;
-        if (a.bias16 && (a.slope != 1.0f || a.out2 || !a.out)) return 2;      // the border corrections: linear, full-resolution epilogue only
-        if (a.ts == 6 && wino_coop_wanted((long long)a.Mt * (a.N / 2))) {
-            const long long wgs = ((long long)a.Mt * (a.N / 4) + WINO_THREADS / 8 - 1) / (WINO_THREADS / 8);
-            hipLaunchKernelGGL(wino_output_coop6_kernel, dim3((unsigned)(wgs < 65536 ? wgs : 65536)), dim3(WINO_THREADS), 0, st, a);
-        } else if (a.ts == 6)
-            hipLaunchKernelGGL((wino_output_kernel<6, 2>), dim3(wino_blocks((long long)a.Mt * (a.N / 2))), dim3(wino_threads((long long)a.Mt * (a.N / 2))),
-                               0, st, a);
-        else if (a.ts == 2)
-            hipLaunchKernelGGL((wino_output_kernel<2, 4>), dim3(wino_blocks((long long)a.Mt * (a.N / 4))), dim3(wino_threads((long long)a.Mt * (a.N / 4))),
-                               0, st, a);
-        else   // <4,4> measured equal
-            hipLaunchKernelGGL((wino_output_kernel<4, 2>), dim3(wino_blocks((long long)a.Mt * (a.N / 2))), dim3(wino_threads((long long)a.Mt * (a.N / 2))),
-                               0, st, a);
+    const WinoLaunch l = choose_wino_output(a, gates);
+    const dim3 grid(l.grid), block(l.threads);
+    switch (l.form) {
+    case WOUT_GATES6: hipLaunchKernelGGL((wino_output_gates_kernel<6, 1>), grid, block, 0, st, a); break;
+    case WOUT_GATES2: hipLaunchKernelGGL((wino_output_gates_kernel<2, 4>), grid, block, 0, st, a); break;
+    case WOUT_GATES4: hipLaunchKernelGGL((wino_output_gates_kernel<4, 1>), grid, block, 0, st, a); break;
+    case WOUT_COOP6: hipLaunchKernelGGL(wino_output_coop6_kernel, grid, block, 0, st, a); break;
+    case WOUT_TPI6: hipLaunchKernelGGL((wino_output_kernel<6, 2>), grid, block, 0, st, a); break;
+    case WOUT_TPI2: hipLaunchKernelGGL((wino_output_kernel<2, 4>), grid, block, 0, st, a); break;
+    case WOUT_TPI4: hipLaunchKernelGGL((wino_output_kernel<4, 2>), grid, block, 0, st, a); break;
+    default: return 2;
     }
     return hipGetLastError() == hipSuccess ? 0 : 1;
 }

@@ -58,7 +58,13 @@ SYMBOLS = [
     "dt_detect_match", "dt_detect_rank",
     "dt_identity_overlap", "dt_assign_max",
     "dt_associate_tracks_assign", "dt_associate_stream_tracks_assign",
+    "dt_wino_geometry", "dt_wino_input", "dt_wino_output",
 ]
+# dt_wino_input / dt_wino_output (include/mi355_dt.h): what h_geom holds, and the codes of the kernel forms the launchers report
+DT_WINO_GEOM_INTS = 10
+WINO_GEOM_KEYS = ("g", "ph", "pw", "th", "tw", "Mt", "Mp", "form", "grid", "threads")
+WIN_FORMS = {"tpi2": 1, "tpi4": 2, "tpi6": 3, "tpi4_s3": 4, "coop6": 5, "s3_6": 6, "s3_4": 7, "h2_6": 8, "h2_4": 9}
+WOUT_FORMS = {"tpi6": 1, "tpi4": 2, "tpi2": 3, "coop6": 4, "gates6": 5, "gates4": 6, "gates2": 7}
 
 _lib = None
 
@@ -164,6 +170,10 @@ def load_library():
     L.dt_convlstm_step.argtypes = [vp, vp, ci, ci, ci, ci, vp, vp, ci, vp, vp, vp, vp, vp]
     L.dt_gemm_split_bf16.argtypes = [vp, vp, vp, ci, ci, ci, ci, ci, vp]
     L.dt_gemm_split.argtypes = [vp, vp, vp, ci, ci, ci, ci, ci, ci, vp]
+    cll, geom = ctypes.c_longlong, ctypes.POINTER(ci)
+    L.dt_wino_geometry.argtypes = [vp, ci, ci, ci, ci, ci, geom]
+    L.dt_wino_input.argtypes = [vp, vp, ci, ci, ci, ci, ci, cll, ci, ci, ci, ci, ci, vp, cll, geom]
+    L.dt_wino_output.argtypes = [vp, vp, cll, ci, ci, ci, ci, ci, ci, vp, vp, cf, vp, ci, vp, ci, ci, vp, ci, vp, ci, ci, ci, geom]
     L.dt_profile_enable.argtypes = [vp, ci]
     L.dt_graph_enable.argtypes = [vp, ci]
     L.dt_profile_reset.argtypes = [vp]
@@ -1156,6 +1166,57 @@ class Context(object):
 
     def gemm_split(self, v, u, half=0, nt=2):
         return self.gemm_split_bf16(v, u, half=half, nt=nt)
+
+    # ---- the Winograd transforms alone (csrc/winograd.hip) -------------
+    @staticmethod
+    def _wino_geom(g):
+        return dict(zip(WINO_GEOM_KEYS, [int(v) for v in g]))
+
+    def _nhwc_view(self, t, what):
+        """[B,H,W,C] float32 device view with dense channels, rows and frames of pixels `ld` floats apart -> (ld, frame stride)"""
+        assert t.is_cuda and t.dtype == self.torch.float32 and t.dim() == 4 and t.stride(3) == 1 and t.stride(1) == t.shape[2] * t.stride(2), what
+        return t.stride(2), t.stride(0)
+
+    def wino_geometry(self, ts, B, H, W, pooled=False):
+        """the tile geometry the library gives a Winograd launch (dt_wino_geometry): g, ph, pw, th, tw, Mt, Mp"""
+        g = (ctypes.c_int * DT_WINO_GEOM_INTS)()
+        self._check(self.lib.dt_wino_geometry(self.h, int(ts), int(B), int(H), int(W), int(bool(pooled)), g), "dt_wino_geometry")
+        return {k: v for k, v in self._wino_geom(g).items() if k not in ("form", "grid", "threads")}
+
+    def wino_input(self, x, v, ts, nt=0, pooled=False, force_form=0, wg_cap=0):
+        """Bt d B of the view x [B,H,W,C] (pixel stride >= C, any frame stride) into the caller's buffer v (dt_wino_input): nt=0 float32
+        [P,Mt,C], nt=3 / 2 the split layouts in 16-bit words.  Returns the geometry with the kernel form, grid and workgroup size taken."""
+        ld, bs = self._nhwc_view(x, "x")
+        assert v.is_cuda and v.is_contiguous()
+        B, H, W, C = x.shape
+        g = (ctypes.c_int * DT_WINO_GEOM_INTS)()
+        self._sync_stream()
+        self._check(self.lib.dt_wino_input(self.h, _dptr(x), B, H, W, C, ld, bs, int(ts), int(bool(pooled)), int(nt), int(force_form), int(wg_cap),
+                                           _dptr(v), v.numel() * v.element_size(), g), "dt_wino_input")
+        return self._wino_geom(g)
+
+    def wino_output(self, m, N, B, H, W, ts, bias=None, bias16=None, slope=1.0, out=None, out2=None, publish=False, xproj=None, cstate=None,
+                    force_form=0, wg_cap=0):
+        """At m A of m [P,Mt,m_ld] (dt_wino_output) into the caller's views out [B,H,W,N] and / or out2 [B,H//2,W//2,N] (pixel stride >= N), or,
+        with cstate, the ConvLSTM gate update: xproj [B,H,W,N] read, cstate [B,H,W,N//4] updated in place, h to out [B,H,W,N//4].  publish:
+        max |x| of what was stored goes to max-|x| slot 57 (amax_read).  Returns the geometry with the kernel form, grid and workgroup size."""
+        t = self.torch
+        assert m.is_cuda and m.is_contiguous() and m.dtype == t.float32 and m.dim() == 3
+        lds = {}
+        for name, a, shape in (("out", out, (B, H, W)), ("out2", out2, (B, H // 2, W // 2)), ("xproj", xproj, (B, H, W)), ("cstate", cstate, (B, H, W))):
+            lds[name] = 0
+            if a is not None:
+                assert tuple(a.shape[:3]) == shape, name
+                lds[name], bs = self._nhwc_view(a, name)
+                assert bs == shape[1] * shape[2] * lds[name], name + ": frames follow each other"
+        for a in (bias, bias16):
+            assert a is None or (a.is_cuda and a.is_contiguous() and a.dtype == t.float32)
+        g = (ctypes.c_int * DT_WINO_GEOM_INTS)()
+        self._sync_stream()
+        self._check(self.lib.dt_wino_output(self.h, _dptr(m), m.numel(), m.shape[2], int(N), int(B), int(H), int(W), int(ts), _dptr(bias), _dptr(bias16),
+                                            float(slope), _dptr(out), lds["out"], _dptr(out2), lds["out2"], int(bool(publish)), _dptr(xproj), lds["xproj"],
+                                            _dptr(cstate), lds["cstate"], int(force_form), int(wg_cap), g), "dt_wino_output")
+        return self._wino_geom(g)
 
     # ---- profiling ------------------------------------------------------
     def profile_enable(self, on=True):

@@ -10,7 +10,8 @@ the slot-dependence bar of DESIGN.md 4.3 (2e-5, relative to the output's largest
 Bit for bit: G of F(6x6) holds 2/9, 1/90, ... which are no float32 numbers, so no F(6x6) result is exact.  The exact one-hot check
 therefore runs the F(2x2) instance of the same output kernel template (halves and small integers only) on a forced 3x3 mosaic; the
 F(6x6) kernels -- lane-cooperative and thread-per-item -- hold the one-hot bar of test_conv2d_winograd_detects_transpose (integers
-up to 250, off by >= 1 wherever a tap, a separator or a pooling window is misplaced)."""
+up to 250, off by >= 1 wherever a tap, a separator or a pooling window is misplaced).  Each transform TAKEN ALONE is exact on small
+integers (Bt and At are dyadic): tests/test_gpu_wino_transform.py holds every transform kernel, F(6x6) included, to `array_equal`."""
 import functools
 
 import numpy as np
