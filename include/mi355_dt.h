@@ -55,6 +55,7 @@ extern "C" {
 #define DT_SCORE_RESUME 2     /* ... flag bit: d_totals, d_objs, d_nobjs are in-out and the call continues from them */
 #define DT_IDENT_INTS 8       /* identity scoring sizes of a clip (dt_identity_overlap): frames, gt boxes, hyp boxes, gt trajectories, hyp trajectories,
                                *     gt overflow boxes, hyp overflow boxes, valid pairs */
+#define DT_HOTA_MAX_THR 32    /* HOTA scoring (dt_hota_count): the most IoU thresholds of a call */
 
 typedef struct dt_ctx dt_ctx;
 
@@ -74,6 +75,7 @@ DT_API int dt_set_stream(dt_ctx *ctx, void *hip_stream);
  * and the one track scoring entry dt_track_score
  * and the two detection scoring entries dt_detect_match, dt_detect_rank
  * and the two identity scoring entries dt_identity_overlap, dt_assign_max
+ * and the three HOTA scoring entries dt_hota_align, dt_hota_weights, dt_hota_count
  * and the two track assignment entries dt_associate_tracks_assign, dt_associate_stream_tracks_assign
  * and the three Winograd transform test entries dt_wino_geometry, dt_wino_input, dt_wino_output
  * -- additions only, the number stayed; 1.07: 1.06 + dt_gemm_split, dt_policy_set) */
@@ -427,8 +429,8 @@ DT_API int dt_associate_tracks_assign(dt_ctx *ctx, const float *d_boxes, const i
  * d_nobjs on are zero with -1 in the gt id and last track id fields.  With it the three are in-out and the call continues from them:
  * chunks of any sizes along T give every output of the one call on the concatenation, bit for bit -- the contract of the stream entries,
  * with the state owned by the caller (no slot table).  Asynchronous on the context's stream; n_clips = 0 is a no-op.
- * Not done here: an optimal (Hungarian) assignment in the frame step (dt_assign_max is one; IDF1: dt_identity_overlap below), HOTA,
- * ignore regions and visibility weighting, dropping coasting rows.  (Detector AP: dt_detect_match / dt_detect_rank below.)
+ * Not done here: an optimal (Hungarian) assignment in the frame step (dt_assign_max is one; IDF1: dt_identity_overlap below; HOTA:
+ * dt_hota_align below), ignore regions and visibility weighting, dropping coasting rows.  (Detector AP: dt_detect_match / dt_detect_rank below.)
  * DT_ERR_ARG (nothing launched): a NULL required pointer, n_clips < 0, T, gcap, hcap or ocap <= 0, id_stride < 1, hyp_label_at outside
  * 0..7, unknown flag bits, one of d_match / d_miou without the other, a threshold that is NaN or outside (0, 1], or a table and frame
  * that do not fit the 160 KB of LDS: 8 * ocap + 11 * gcap + 7 * hcap words must not exceed 40960 (gcap = hcap = 128: ocap up to 4832). */
@@ -480,13 +482,77 @@ DT_API int dt_track_score(dt_ctx *ctx, const float *d_gt_boxes, const int *d_gt_
  * DT_ERR_ARG (nothing launched, nothing written): a NULL pointer, n < 0, rcap or ccap <= 0, rows_at or cols_at outside 0..stride-1,
  * n * rcap * ccap >= 2^31, or work arrays that do not fit the 160 KB of LDS: 6 * (max(rcap, ccap) + 1) words must not exceed 40960
  * (caps up to 6825).
- * Not done here: HOTA, ignore regions.  (This solver's method is also the tracker's own match in dt_associate_tracks_assign.) */
+ * Not done here: ignore regions.  (HOTA: dt_hota_align, dt_hota_weights, dt_hota_count below, which call this solver per frame; its method is
+ * also the tracker's own match in dt_associate_tracks_assign.) */
 DT_API int dt_identity_overlap(dt_ctx *ctx, const float *d_gt_boxes, const int *d_gt_counts, const int *d_gt_ids, int gcap,
                  const float *d_hyp_boxes, const int *d_hyp_counts, const int *d_hyp_ids, int hcap, int id_stride, int hyp_label_at,
                  int n_clips, int T, float iou_threshold, int flags, int acap, int bcap,
                  int *d_sizes, int *d_gt_tab, int *d_hyp_tab, int *d_overlap);
 DT_API int dt_assign_max(dt_ctx *ctx, const int *d_w, int rcap, int ccap, const int *d_dims, int stride, int rows_at, int cols_at, int n,
                  int *d_row_to_col, int *d_col_to_row, int64_t *d_total);
+
+/* HOTA scoring (BUILD-DEFINED, DESIGN.md "HOTA scoring"): HOTA (Luiten et al., IJCV 2021) of a tracker's output against ground-truth
+ * tracks, restated on the quantised similarity q = (int)(IoU * 2^20) so that the device sums integers only and every output is
+ * independent of the order of any sum.  Three entries, with dt_assign_max between the second and the third; DetA, AssA, HOTA, LocA
+ * and their siblings are ratios taken on the host in float64 (Python: utility.evaluate.hota).  S = DT_ASSIGN_IOU_SCALE = 2^20.
+ *
+ * The input arguments d_gt_boxes .. T of dt_hota_align and dt_hota_weights are dt_track_score's, name for name (there is no IoU threshold
+ * here); flags: DT_SCORE_ANY_LABEL, and for dt_hota_align DT_SCORE_RESUME.  Rows, trajectories, the two tables and the overflow counts are
+ * dt_identity_overlap's.
+ * SIMILARITY of a frame's row pair (g, i): q[g][i] = (int)(bbox_iou(gt box g, hyp box i) * 1048576.0f) (dt_bbox_iou's float32 bits; the
+ * product is exact, the conversion truncates), and q = 0 when the labels differ as floats (unless DT_SCORE_ANY_LABEL), when the IoU is
+ * NaN or <= 0, or when either row has no trajectory.  Boxes must have w, h >= 0 and be finite (then IoU <= 1, q <= S); a trajectory must
+ * have fewer than 2^22 boxes.  Outside that the results are unspecified, but every call terminates and stays in bounds.
+ *
+ * dt_hota_align (pass 1, one wavefront per clip, frames in sequence): per frame R[g] = sum_i q[g][i] and C[i] = sum_g q[g][i] in int64,
+ * and every pair with q > 0 adds c = (q << 20) / (R[g] + C[i] - q) (int64, integer division) to P[a][b] of its trajectories (a, b).  The
+ * c of a row, and of a column, add up to S at most, so P[a][b] <= S * min(n_a, n_b) with n the trajectories' box counts, repeated ids
+ * included.
+ *   d_sizes   [n_clips, DT_IDENT_INTS] int32   dt_identity_overlap's words, word 7 = the pairs with q > 0
+ *   d_gt_tab  [n_clips, acap, 2] int32, d_hyp_tab [n_clips, bcap, 2] int32   id, boxes; unused rows are (-1, 0)
+ *   d_align   [n_clips, acap, bcap] int64      P
+ * Without DT_SCORE_RESUME every word of the four is written.  With it they are in-out: chunks of any sizes along T give the outputs of
+ * one call on the concatenation, bit for bit.
+ *
+ * dt_hota_weights (pass 2, one wavefront per (clip, frame); frames are independent): from the FINISHED d_sizes, d_gt_tab, d_hyp_tab and
+ * d_align of the whole clip, W[g][i] = 1 + (P[a][b] * q) / (S * (n_a + n_b) - P[a][b]) (int64, integer division) where q > 0, else 0.
+ * The divisor is >= S * max(n_a, n_b) > 0 and W <= S + 1, inside dt_assign_max's [0, 2^24].
+ *   d_w       [n_clips, T, gcap, hcap] int32   every word written, 0 outside the frame's counts
+ *   d_dims    [n_clips, T, 2] int32            the frame's clamped row counts ng, nh
+ *   d_gt_ent  [n_clips, T, gcap] int32, d_hyp_ent [n_clips, T, hcap] int32   the row's trajectory (table row), or -1
+ * The frame's match is dt_assign_max's d_row_to_col on d_w as n_clips * T problems [gcap, hcap] with d_dims (stride 2, rows_at 0,
+ * cols_at 1): the solver is called unchanged, so its orientation and tie rules apply, and pairs of weight 0 are unassigned.
+ *
+ * dt_hota_count (one wavefront per (clip, frame)): h_thresholds [n_thr] on the HOST, 1 <= n_thr <= DT_HOTA_MAX_THR, each in (0, 1],
+ * strictly ascending.  A matched pair's level L is the number of k with IoU >= h_thresholds[k], compared as float32 (the IoU is the call
+ * whose product gave q).  A pair of level L >= 1 adds, in bucket L - 1: 1 to tp, q to loc, 1 to pairs[a][b].  A pair that passes
+ * threshold k passes every lower one: the figures at threshold k are the sums over the buckets k .. n_thr - 1, taken on the host.
+ *   d_tp      [n_clips, n_thr] int32, d_loc [n_clips, n_thr] int64, d_pairs [n_clips, n_thr, acap, bcap] int32
+ * flags: 0, or DT_SCORE_RESUME: the three are in-out and the call adds to them (the chunks of a clip, each with its own d_dims ..
+ * d_row_to_col); without it every word is written.  Rows whose d_row_to_col, d_gt_ent or d_hyp_ent lies outside its range are skipped.
+ *
+ * All three are asynchronous on the context's stream; n_clips = 0 is a no-op.  A clip fed in chunks takes two loops over the chunks:
+ * dt_hota_align with DT_SCORE_RESUME over all of them first, then dt_hota_weights, dt_assign_max and dt_hota_count (DT_SCORE_RESUME) per chunk.
+ * Not done here: ignore regions, visibility weighting, per-class breakdowns (the caller filters by label).
+ * DT_ERR_ARG (nothing launched, nothing written): a NULL pointer, n_clips < 0, T, gcap, hcap, acap or bcap <= 0, id_stride < 1, hyp_label_at
+ * outside 0..7, unknown flag bits, n_thr outside 1..32, a threshold that is NaN, outside (0, 1] or not above its predecessor,
+ * n_clips * acap * bcap (align, weights), n_clips * T * gcap * hcap (weights), n_clips * n_thr * acap * bcap, n_clips * T * gcap or
+ * n_clips * T * hcap (count) >= 2^31, or a frame and tables that do not fit the 160 KB of LDS: 2 * acap + 2 * bcap + 9 * gcap + 9 * hcap
+ * words (align; the int64 R and C beside dt_identity_overlap's rows) or 2 * acap + 2 * bcap + 7 * gcap + 7 * hcap words (weights) must not
+ * exceed 40960. */
+DT_API int dt_hota_align(dt_ctx *ctx, const float *d_gt_boxes, const int *d_gt_counts, const int *d_gt_ids, int gcap,
+                 const float *d_hyp_boxes, const int *d_hyp_counts, const int *d_hyp_ids, int hcap, int id_stride, int hyp_label_at,
+                 int n_clips, int T, int flags, int acap, int bcap,
+                 int *d_sizes, int *d_gt_tab, int *d_hyp_tab, int64_t *d_align);
+DT_API int dt_hota_weights(dt_ctx *ctx, const float *d_gt_boxes, const int *d_gt_counts, const int *d_gt_ids, int gcap,
+                 const float *d_hyp_boxes, const int *d_hyp_counts, const int *d_hyp_ids, int hcap, int id_stride, int hyp_label_at,
+                 int n_clips, int T, int flags, int acap, int bcap,
+                 const int *d_sizes, const int *d_gt_tab, const int *d_hyp_tab, const int64_t *d_align,
+                 int *d_w, int *d_dims, int *d_gt_ent, int *d_hyp_ent);
+DT_API int dt_hota_count(dt_ctx *ctx, const float *d_gt_boxes, int gcap, const float *d_hyp_boxes, int hcap, int n_clips, int T,
+                 const int *d_dims, const int *d_gt_ent, const int *d_hyp_ent, const int *d_row_to_col,
+                 const float *h_thresholds, int n_thr, int acap, int bcap, int flags,
+                 int *d_tp, int64_t *d_loc, int *d_pairs);
 
 /* Detection scoring (BUILD-DEFINED, DESIGN.md "Detection scoring"): per-class average precision of a detector's boxes against ground truth,
  * by the VOC devkit's match.  Two entries: the match of every frame, then the position of every detection in its class's score order over

@@ -15,7 +15,7 @@ CSRC = os.path.join(HERE, "csrc")
 LIB = os.path.join(HERE, "libmi355_dt.so")
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 
-# decode.hip / associate.hip / targets.hip / score.hip / identity.hip / detscore.hip restate numpy / Python float arithmetic op for op: no FMA contraction there.
+# decode.hip / associate.hip / targets.hip / score.hip / identity.hip / hota.hip / detscore.hip restate numpy / Python float arithmetic op for op: no FMA contraction there.
 SOURCES = {
     "conv_igemm.hip": [],
     "conv1.hip": [],
@@ -32,6 +32,7 @@ SOURCES = {
     "associate.hip": ["-ffp-contract=off"],
     "score.hip": ["-ffp-contract=off"],
     "identity.hip": ["-ffp-contract=off"],
+    "hota.hip": ["-ffp-contract=off"],
     "detscore.hip": ["-ffp-contract=off"],
     "targets.hip": ["-ffp-contract=off"],
     "recurrent.hip": [],

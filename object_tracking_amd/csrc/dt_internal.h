@@ -503,6 +503,60 @@ struct IdentArgs {
 size_t identity_overlap_lds_bytes(int gcap, int hcap, int acap, int bcap);      // dt_identity_overlap refuses more than 160 KB
 // 0: launched; 1: device error.  flags: DT_SCORE_* bits; without DT_SCORE_RESUME the overlap is zeroed on the stream first.
 int launch_identity_overlap(hipStream_t st, const IdentArgs &a, int n_clips, int flags);
+// (identity.hip and hota.hip) Rows [0, nr) of a frame, ids r_id: r_ent[r] becomes the table row of the id, opened if it is new and the table has room, else -1.
+// t_id / t_n [cap] are the table (ids distinct), nt its rows in use.  Returns the boxes whose id found the table full (wave-uniform).
+__device__ __forceinline__ int open_trajectories(volatile int *r_id, volatile int *r_ent, int nr, volatile int *t_id, volatile int *t_n,
+                                                 int &nt, int cap, int lane)
+{
+    const int nt0 = nt;                                       // the table as the previous frame left it
+    int over = 0;
+    for (int r = lane; r < nr; r += 64) {
+        const int id = r_id[r];
+        int e = -1;
+        if (id >= 0)
+            for (int k = 0; k < nt0; ++k) e = t_id[k] == id ? k : e;
+        r_ent[r] = e;
+    }
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
+    __builtin_amdgcn_wave_barrier();
+    for (int r0 = 0; r0 < nr; r0 += 64) {
+        const int r = r0 + lane;
+        unsigned long long fresh = __ballot(r < nr && r_ent[r] < 0 && r_id[r] >= 0);
+        while (fresh) {
+            const int rr = r0 + __ffsll((long long)fresh) - 1;
+            const int v = r_id[rr];
+            int found = -1;                                   // a lower row of this frame may have opened the trajectory
+            for (int k0 = nt0; k0 < nt; k0 += 64) {
+                const int k = k0 + lane;
+                const unsigned long long bal = __ballot(k < nt && t_id[k] == v);
+                if (bal) {
+                    found = k0 + __ffsll((long long)bal) - 1;
+                    break;
+                }
+            }
+            if (found < 0) {
+                if (nt < cap) {
+                    found = nt++;
+                    if (lane == 0) { t_id[found] = v; t_n[found] = 0; }
+                } else {
+                    ++over;
+                }
+            }
+            if (found >= 0 && lane == 0) r_ent[rr] = found;
+            __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
+            __builtin_amdgcn_wave_barrier();
+            fresh &= fresh - 1ull;
+        }
+    }
+    for (int r = lane; r < nr; r += 64) {
+        const int e = r_ent[r];
+        if (e >= 0) atomicAdd(const_cast<int *>(t_n + e), 1);
+    }
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
+    __builtin_amdgcn_wave_barrier();
+    return over;
+}
+
 struct AssignArgs {
     const int *w;            // [n][rcap][ccap]
     const int *dims;         // [n][stride], rows in word rows_at, columns in word cols_at
@@ -513,6 +567,47 @@ struct AssignArgs {
 };
 size_t assign_max_lds_bytes(int rcap, int ccap);                                // dt_assign_max refuses more than 160 KB
 int launch_assign_max(hipStream_t st, const AssignArgs &a, int n);              // 0: launched; 1: device error
+
+// HOTA scoring (hota.hip, DESIGN.md "HOTA scoring"): the alignment P of ground-truth with hypothesis trajectories over a clip (one
+// wavefront per clip), the weights W of every frame's match from the finished P (one wavefront per frame; dt_assign_max solves them), and
+// the counts per IoU level of the matched pairs (one wavefront per frame).  Integers only; the inputs are ScoreArgs'.
+struct HotaArgs {
+    const float *gt_boxes;   // [n][T][gcap][DT_BOX_FLOATS]
+    const int *gt_counts;    // [n][T]
+    const int *gt_ids;       // [n][T][gcap]
+    const float *hyp_boxes;  // [n][T][hcap][8]
+    const int *hyp_counts;   // [n][T]
+    const int *hyp_ids;      // [n][T][hcap][id_stride], the id in word 0
+    int gcap, hcap, id_stride, label_at, T, acap, bcap;
+    int *sizes;              // [n][DT_IDENT_INTS]            written by the alignment, read by the weights
+    int *gt_tab;             // [n][acap][2]                  likewise
+    int *hyp_tab;            // [n][bcap][2]                  likewise
+    long long *align;        // [n][acap][bcap]               likewise
+    int *w;                  // [n][T][gcap][hcap]            the weights' outputs from here on; null for the alignment
+    int *dims;               // [n][T][2]
+    int *gt_ent;             // [n][T][gcap]
+    int *hyp_ent;            // [n][T][hcap]
+};
+struct HotaCountArgs {
+    const float *gt_boxes;   // [n][T][gcap][DT_BOX_FLOATS]
+    const float *hyp_boxes;  // [n][T][hcap][8]
+    const int *dims;         // [n][T][2]
+    const int *gt_ent;       // [n][T][gcap]
+    const int *hyp_ent;      // [n][T][hcap]
+    const int *row_to_col;   // [n * T][gcap]
+    int gcap, hcap, T, acap, bcap, n_thr;
+    float thr[DT_HOTA_MAX_THR];
+    int *tp;                 // [n][n_thr]
+    long long *loc;          // [n][n_thr]
+    int *pairs;              // [n][n_thr][acap][bcap]
+};
+size_t hota_align_lds_bytes(int gcap, int hcap, int acap, int bcap);            // dt_hota_align refuses more than 160 KB
+size_t hota_weights_lds_bytes(int gcap, int hcap, int acap, int bcap);          // dt_hota_weights likewise
+// 0: launched; 1: device error.  The arguments are validated by the entries (network.hip).  flags: DT_SCORE_* bits; without
+// DT_SCORE_RESUME the alignment zeroes `align`, and the count zeroes tp, loc and pairs, on the stream first.
+int launch_hota_align(hipStream_t st, const HotaArgs &a, int n_clips, int flags);
+int launch_hota_weights(hipStream_t st, const HotaArgs &a, int n_clips, int flags);
+int launch_hota_count(hipStream_t st, const HotaCountArgs &a, int n_clips, int flags);
 
 // detection scoring (detscore.hip, DESIGN.md "Detection scoring"): the VOC match of detections against ground truth per frame, then the
 // position of every detection in its class's score order over all frames.  Integers out; the ratios are taken on the host.

@@ -21,60 +21,6 @@
 
 #define IDENT_LDS_LIMIT (160 * 1024)
 
-// Rows [0, nr) of a frame, ids r_id: r_ent[r] becomes the table row of the id, opened if it is new and the table has room, else -1.
-// t_id / t_n [cap] are the table (ids distinct), nt its rows in use.  Returns the boxes whose id found the table full (wave-uniform).
-__device__ __forceinline__ int open_trajectories(volatile int *r_id, volatile int *r_ent, int nr, volatile int *t_id, volatile int *t_n,
-                                                 int &nt, int cap, int lane)
-{
-    const int nt0 = nt;                                       // the table as the previous frame left it
-    int over = 0;
-    for (int r = lane; r < nr; r += 64) {
-        const int id = r_id[r];
-        int e = -1;
-        if (id >= 0)
-            for (int k = 0; k < nt0; ++k) e = t_id[k] == id ? k : e;
-        r_ent[r] = e;
-    }
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
-    __builtin_amdgcn_wave_barrier();
-    for (int r0 = 0; r0 < nr; r0 += 64) {
-        const int r = r0 + lane;
-        unsigned long long fresh = __ballot(r < nr && r_ent[r] < 0 && r_id[r] >= 0);
-        while (fresh) {
-            const int rr = r0 + __ffsll((long long)fresh) - 1;
-            const int v = r_id[rr];
-            int found = -1;                                   // a lower row of this frame may have opened the trajectory
-            for (int k0 = nt0; k0 < nt; k0 += 64) {
-                const int k = k0 + lane;
-                const unsigned long long bal = __ballot(k < nt && t_id[k] == v);
-                if (bal) {
-                    found = k0 + __ffsll((long long)bal) - 1;
-                    break;
-                }
-            }
-            if (found < 0) {
-                if (nt < cap) {
-                    found = nt++;
-                    if (lane == 0) { t_id[found] = v; t_n[found] = 0; }
-                } else {
-                    ++over;
-                }
-            }
-            if (found >= 0 && lane == 0) r_ent[rr] = found;
-            __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
-            __builtin_amdgcn_wave_barrier();
-            fresh &= fresh - 1ull;
-        }
-    }
-    for (int r = lane; r < nr; r += 64) {
-        const int e = r_ent[r];
-        if (e >= 0) atomicAdd(const_cast<int *>(t_n + e), 1);
-    }
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
-    __builtin_amdgcn_wave_barrier();
-    return over;
-}
-
 template <bool ANY>
 __global__ __launch_bounds__(64) void identity_overlap_kernel(IdentArgs p, int resume)
 {

@@ -2077,6 +2077,92 @@ extern "C" int dt_assign_max(dt_ctx *ctx, const int *d_w, int rcap, int ccap, co
     return DT_OK;
 }
 
+// HOTA scoring (DESIGN.md "HOTA scoring"): the alignment of a clip's trajectories, every frame's weights for dt_assign_max, and the
+// matched pairs counted per IoU level.  The first two share the checks of their input arguments.
+static const char *hota_input_args(const void *gt_boxes, const void *gt_counts, const void *gt_ids, int gcap, const void *hyp_boxes,
+                                   const void *hyp_counts, const void *hyp_ids, int hcap, int id_stride, int hyp_label_at, int n_clips, int T,
+                                   int acap, int bcap, const void *sizes, const void *gt_tab, const void *hyp_tab, const void *align)
+{
+    if (!gt_boxes || !gt_counts || !gt_ids || !hyp_boxes || !hyp_counts || !hyp_ids || !sizes || !gt_tab || !hyp_tab || !align) return "null argument";
+    if (n_clips < 0 || T <= 0 || gcap <= 0 || hcap <= 0 || acap <= 0 || bcap <= 0)
+        return "n_clips must not be negative; T, gcap, hcap, acap and bcap must be positive";
+    if (id_stride < 1) return "id_stride must be at least 1";
+    if (hyp_label_at < 0 || hyp_label_at > 7) return "hyp_label_at must be in 0..7";
+    if ((long long)n_clips * acap * bcap >= (1ll << 31)) return "n_clips * acap * bcap must be below 2^31";
+    return nullptr;
+}
+
+extern "C" int dt_hota_align(dt_ctx *ctx, const float *d_gt_boxes, const int *d_gt_counts, const int *d_gt_ids, int gcap,
+                             const float *d_hyp_boxes, const int *d_hyp_counts, const int *d_hyp_ids, int hcap, int id_stride, int hyp_label_at,
+                             int n_clips, int T, int flags, int acap, int bcap, int *d_sizes, int *d_gt_tab, int *d_hyp_tab, int64_t *d_align)
+{
+    if (!ctx) return DT_ERR_ARG;
+    if (const char *why = hota_input_args(d_gt_boxes, d_gt_counts, d_gt_ids, gcap, d_hyp_boxes, d_hyp_counts, d_hyp_ids, hcap, id_stride, hyp_label_at,
+                                          n_clips, T, acap, bcap, d_sizes, d_gt_tab, d_hyp_tab, d_align))
+        return dt_fail(ctx, DT_ERR_ARG, "%s", why);
+    if (flags & ~(DT_SCORE_ANY_LABEL | DT_SCORE_RESUME)) return dt_fail(ctx, DT_ERR_ARG, "flags must be a combination of DT_SCORE_ANY_LABEL and DT_SCORE_RESUME");
+    if (hota_align_lds_bytes(gcap, hcap, acap, bcap) > (size_t)160 * 1024)
+        return dt_fail(ctx, DT_ERR_ARG, "2 * acap + 2 * bcap + 9 * gcap + 9 * hcap words do not fit the 160 KB of LDS");
+    if (n_clips == 0) return DT_OK;
+    ProfScope ps(ctx, "score", 0.0, 4.0 * n_clips * ((double)T * (gcap * 6.0 + hcap * (6.0 + id_stride)) + (acap + bcap) * 2.0 + 2.0 * acap * bcap),
+                 "hota_align");
+    HotaArgs a{d_gt_boxes, d_gt_counts, d_gt_ids, d_hyp_boxes, d_hyp_counts, d_hyp_ids, gcap, hcap, id_stride, hyp_label_at, T, acap, bcap,
+               d_sizes, d_gt_tab, d_hyp_tab, reinterpret_cast<long long *>(d_align), nullptr, nullptr, nullptr, nullptr};
+    if (launch_hota_align(ctx->stream, a, n_clips, flags)) return dt_fail(ctx, DT_ERR_DEVICE, "hota align launch failed");
+    return DT_OK;
+}
+
+extern "C" int dt_hota_weights(dt_ctx *ctx, const float *d_gt_boxes, const int *d_gt_counts, const int *d_gt_ids, int gcap,
+                               const float *d_hyp_boxes, const int *d_hyp_counts, const int *d_hyp_ids, int hcap, int id_stride, int hyp_label_at,
+                               int n_clips, int T, int flags, int acap, int bcap, const int *d_sizes, const int *d_gt_tab,
+                               const int *d_hyp_tab, const int64_t *d_align, int *d_w, int *d_dims, int *d_gt_ent, int *d_hyp_ent)
+{
+    if (!ctx) return DT_ERR_ARG;
+    if (const char *why = hota_input_args(d_gt_boxes, d_gt_counts, d_gt_ids, gcap, d_hyp_boxes, d_hyp_counts, d_hyp_ids, hcap, id_stride, hyp_label_at,
+                                          n_clips, T, acap, bcap, d_sizes, d_gt_tab, d_hyp_tab, d_align))
+        return dt_fail(ctx, DT_ERR_ARG, "%s", why);
+    if (!d_w || !d_dims || !d_gt_ent || !d_hyp_ent) return dt_fail(ctx, DT_ERR_ARG, "null argument");
+    if (flags & ~DT_SCORE_ANY_LABEL) return dt_fail(ctx, DT_ERR_ARG, "flags must be 0 or DT_SCORE_ANY_LABEL");
+    if ((long long)n_clips * T * gcap * hcap >= (1ll << 31)) return dt_fail(ctx, DT_ERR_ARG, "n_clips * T * gcap * hcap must be below 2^31");
+    if (hota_weights_lds_bytes(gcap, hcap, acap, bcap) > (size_t)160 * 1024)
+        return dt_fail(ctx, DT_ERR_ARG, "2 * acap + 2 * bcap + 7 * gcap + 7 * hcap words do not fit the 160 KB of LDS");
+    if (n_clips == 0) return DT_OK;
+    ProfScope ps(ctx, "score", 0.0, 4.0 * n_clips * T * ((double)gcap * hcap + gcap * 7.0 + hcap * (7.0 + id_stride) + (acap + bcap) * 2.0 + 2.0), "hota_weights");
+    // the kernel only reads the four finished arrays: one argument block serves both kernels
+    HotaArgs a{d_gt_boxes, d_gt_counts, d_gt_ids, d_hyp_boxes, d_hyp_counts, d_hyp_ids, gcap, hcap, id_stride, hyp_label_at, T, acap, bcap,
+               const_cast<int *>(d_sizes), const_cast<int *>(d_gt_tab), const_cast<int *>(d_hyp_tab),
+               reinterpret_cast<long long *>(const_cast<int64_t *>(d_align)), d_w, d_dims, d_gt_ent, d_hyp_ent};
+    if (launch_hota_weights(ctx->stream, a, n_clips, flags)) return dt_fail(ctx, DT_ERR_DEVICE, "hota weights launch failed");
+    return DT_OK;
+}
+
+extern "C" int dt_hota_count(dt_ctx *ctx, const float *d_gt_boxes, int gcap, const float *d_hyp_boxes, int hcap, int n_clips, int T,
+                             const int *d_dims, const int *d_gt_ent, const int *d_hyp_ent, const int *d_row_to_col, const float *h_thresholds,
+                             int n_thr, int acap, int bcap, int flags, int *d_tp, int64_t *d_loc, int *d_pairs)
+{
+    if (!ctx) return DT_ERR_ARG;
+    if (!d_gt_boxes || !d_hyp_boxes || !d_dims || !d_gt_ent || !d_hyp_ent || !d_row_to_col || !h_thresholds || !d_tp || !d_loc || !d_pairs)
+        return dt_fail(ctx, DT_ERR_ARG, "null argument");
+    if (n_clips < 0 || T <= 0 || gcap <= 0 || hcap <= 0 || acap <= 0 || bcap <= 0)
+        return dt_fail(ctx, DT_ERR_ARG, "n_clips must not be negative; T, gcap, hcap, acap and bcap must be positive");
+    if (flags & ~DT_SCORE_RESUME) return dt_fail(ctx, DT_ERR_ARG, "flags must be 0 or DT_SCORE_RESUME");
+    if (n_thr < 1 || n_thr > DT_HOTA_MAX_THR) return dt_fail(ctx, DT_ERR_ARG, "n_thr must be in 1..32");
+    HotaCountArgs a{d_gt_boxes, d_hyp_boxes, d_dims, d_gt_ent, d_hyp_ent, d_row_to_col, gcap, hcap, T, acap, bcap, n_thr, {}, d_tp,
+                    reinterpret_cast<long long *>(d_loc), d_pairs};
+    for (int k = 0; k < n_thr; ++k) {
+        if (!(h_thresholds[k] > 0.0f && h_thresholds[k] <= 1.0f) || (k > 0 && !(h_thresholds[k] > h_thresholds[k - 1])))
+            return dt_fail(ctx, DT_ERR_ARG, "the IoU thresholds must be in (0, 1] and strictly ascending");
+        a.thr[k] = h_thresholds[k];
+    }
+    if ((long long)n_clips * n_thr * acap * bcap >= (1ll << 31)) return dt_fail(ctx, DT_ERR_ARG, "n_clips * n_thr * acap * bcap must be below 2^31");
+    if ((long long)n_clips * T * gcap >= (1ll << 31) || (long long)n_clips * T * hcap >= (1ll << 31))
+        return dt_fail(ctx, DT_ERR_ARG, "n_clips * T * gcap and n_clips * T * hcap must be below 2^31");
+    if (n_clips == 0) return DT_OK;
+    ProfScope ps(ctx, "score", 0.0, 4.0 * n_clips * ((double)T * (gcap * 19.0 + 2.0) + n_thr * (3.0 + (double)acap * bcap)), "hota_count");
+    if (launch_hota_count(ctx->stream, a, n_clips, flags)) return dt_fail(ctx, DT_ERR_DEVICE, "hota count launch failed");
+    return DT_OK;
+}
+
 // detection scoring (DESIGN.md "Detection scoring"): the VOC match per frame, then every detection's position in its class's score order
 static const char *detect_score_args(const void *det_boxes, const void *det_counts, int cap, int score_at, const void *gt_boxes,
                                      const void *gt_counts, int gcap, int B, int NC, int n_thr)

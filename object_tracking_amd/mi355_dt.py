@@ -29,6 +29,7 @@ DT_SCORE_OBJ_INTS = 8    # ... an object row: gt id, last track id, present, mat
 DT_SCORE_ANY_LABEL = 1   # ... flag bits: labels not compared
 DT_SCORE_RESUME = 2      # ... totals / objs / nobjs are in-out, the call continues from them
 DT_IDENT_INTS = 8        # identity scoring sizes (dt_identity_overlap): frames, gt boxes, hyp boxes, gt / hyp trajectories, gt / hyp overflow, valid pairs
+DT_HOTA_MAX_THR = 32     # HOTA scoring (dt_hota_count): the most IoU thresholds of a call
 DT_PIX_RGB24 = 0         # pixel formats of dt_frame_desc (dt_ingest_frames): 3 interleaved bytes per pixel, as they lie
 DT_PIX_NV12 = 1          # ... plane0 = Y, plane1 = U,V interleaved, one pair per 2x2 pixels
 DT_PIX_SWAP_RB = 16      # ... flag: output channels 0 and 2 exchanged
@@ -57,6 +58,7 @@ SYMBOLS = [
     "dt_track_score",
     "dt_detect_match", "dt_detect_rank",
     "dt_identity_overlap", "dt_assign_max",
+    "dt_hota_align", "dt_hota_weights", "dt_hota_count",
     "dt_associate_tracks_assign", "dt_associate_stream_tracks_assign",
     "dt_wino_geometry", "dt_wino_input", "dt_wino_output",
 ]
@@ -142,6 +144,9 @@ def load_library():
     L.dt_track_score.argtypes = [vp, vp, vp, vp, ci, vp, vp, vp, ci, ci, ci, ci, ci, cf, ci, ci, vp, vp, vp, vp, vp, vp]
     L.dt_identity_overlap.argtypes = [vp, vp, vp, vp, ci, vp, vp, vp, ci, ci, ci, ci, ci, cf, ci, ci, ci, vp, vp, vp, vp]
     L.dt_assign_max.argtypes = [vp, vp, ci, ci, vp, ci, ci, ci, ci, vp, vp, vp]
+    L.dt_hota_align.argtypes = [vp, vp, vp, vp, ci, vp, vp, vp, ci, ci, ci, ci, ci, ci, ci, ci, vp, vp, vp, vp]
+    L.dt_hota_weights.argtypes = [vp, vp, vp, vp, ci, vp, vp, vp, ci, ci, ci, ci, ci, ci, ci, ci, vp, vp, vp, vp, vp, vp, vp, vp]
+    L.dt_hota_count.argtypes = [vp, vp, ci, vp, ci, ci, ci, vp, vp, vp, vp, vp, ci, ci, ci, ci, vp, vp, vp]
     L.dt_detect_match.argtypes = [vp, vp, vp, ci, ci, vp, vp, vp, ci, ci, ci, vp, ci, vp, vp, vp]
     L.dt_detect_rank.argtypes = [vp, vp, vp, ci, ci, vp, vp, vp, vp, ci, ci, ci, ci, vp, vp, vp, vp, vp]
     L.dt_track_row_width.argtypes = [vp]
@@ -714,6 +719,130 @@ class Context(object):
         into IDF1 etc.  `state` is a previous result (of either method); the assignment is solved anew on the accumulated overlap."""
         r = self.identity_overlap(gt_boxes, gt_counts, gt_ids, hyp_boxes, hyp_counts, hyp_ids, iou_threshold, any_label, gt_cap, hyp_cap, state)
         r["gt_to_hyp"], r["hyp_to_gt"], r["idtp"] = self.assign_max(r["overlap"], r["sizes"], 3, 4)
+        return r
+
+    def _hota_inputs(self, gt_boxes, gt_counts, gt_ids, hyp_boxes, hyp_counts, hyp_ids):
+        """the checks of identity_overlap's six inputs -> (n, T, gcap, hcap, id_stride, label_at)"""
+        t = self.torch
+        n, T, gcap, _ = gt_boxes.shape
+        hcap = hyp_boxes.shape[2]
+        assert hyp_boxes.shape[:2] == (n, T) and hyp_boxes.shape[3] == 8 and gt_boxes.shape[3] == DT_BOX_FLOATS
+        if hyp_ids.dim() == 4:
+            stride, label_at = int(hyp_ids.shape[3]), 4
+        else:
+            stride, label_at = 1, 5
+        assert tuple(hyp_ids.shape[:3]) == (n, T, hcap) and tuple(gt_ids.shape) == (n, T, gcap)
+        assert tuple(gt_counts.shape) == (n, T) and tuple(hyp_counts.shape) == (n, T)
+        for x, dt in ((gt_boxes, t.float32), (hyp_boxes, t.float32), (gt_counts, t.int32), (gt_ids, t.int32), (hyp_counts, t.int32),
+                      (hyp_ids, t.int32)):
+            assert x.is_cuda and x.is_contiguous() and x.dtype == dt
+        return n, T, gcap, hcap, stride, label_at
+
+    def hota_align(self, gt_boxes, gt_counts, gt_ids, hyp_boxes, hyp_counts, hyp_ids, any_label=False, gt_cap=None, hyp_cap=None, state=None):
+        """Pass 1 of HOTA scoring (dt_hota_align; the rule: DESIGN.md "HOTA scoring"): the alignment of ground-truth trajectories with
+        hypothesis trajectories over a clip.  The six inputs, any_label, gt_cap / hyp_cap and state are identity_overlap's.
+        -> dict: sizes [n,8], gt_tab [n,gt_cap,2], hyp_tab [n,hyp_cap,2] as identity_overlap gives them (sizes word 7: the pairs of
+        similarity > 0), align [n,gt_cap,hyp_cap] int64, and any_label.  state: a previous result this call continues (copied, not
+        written): chunks of any sizes along T give the result of one call on the concatenation."""
+        t = self.torch
+        i32 = lambda *shape: t.empty(shape, dtype=t.int32, device=self.device)
+        n, T, gcap, hcap, stride, label_at = self._hota_inputs(gt_boxes, gt_counts, gt_ids, hyp_boxes, hyp_counts, hyp_ids)
+        flags = DT_SCORE_ANY_LABEL if any_label else 0
+        if state is not None:
+            acap, bcap = int(state["gt_tab"].shape[1]), int(state["hyp_tab"].shape[1])
+            assert gt_cap is None or int(gt_cap) == acap, "gt_cap differs from the state's"
+            assert hyp_cap is None or int(hyp_cap) == bcap, "hyp_cap differs from the state's"
+            assert int(state["sizes"].shape[0]) == n and tuple(state["align"].shape) == (n, acap, bcap)
+            assert bool(state["any_label"]) == bool(any_label), "any_label differs from the state's"
+            r = {k: state[k].clone() for k in ("sizes", "gt_tab", "hyp_tab", "align")}
+            flags |= DT_SCORE_RESUME
+        else:
+            acap = max(64, 2 * gcap) if gt_cap is None else int(gt_cap)
+            bcap = max(64, 2 * hcap) if hyp_cap is None else int(hyp_cap)
+            r = dict(sizes=i32(n, DT_IDENT_INTS), gt_tab=i32(n, max(acap, 0), 2), hyp_tab=i32(n, max(bcap, 0), 2),
+                     align=t.empty((n, max(acap, 0), max(bcap, 0)), dtype=t.int64, device=self.device))
+        r["any_label"] = bool(any_label)
+        self._sync_stream()
+        self._check(self.lib.dt_hota_align(self.h, _dptr(gt_boxes), _dptr(gt_counts), _dptr(gt_ids), gcap, _dptr(hyp_boxes), _dptr(hyp_counts),
+                                           _dptr(hyp_ids), hcap, stride, label_at, n, T, flags, acap, bcap, _dptr(r["sizes"]),
+                                           _dptr(r["gt_tab"]), _dptr(r["hyp_tab"]), _dptr(r["align"])), "dt_hota_align")
+        return r
+
+    def hota_weights(self, gt_boxes, gt_counts, gt_ids, hyp_boxes, hyp_counts, hyp_ids, align):
+        """Pass 2 of HOTA scoring (dt_hota_weights): the weights of every frame's match from a FINISHED hota_align result of the whole
+        clip (labels are compared as that result's any_label says).
+        -> dict: w [n,T,gcap,hcap] int32 (0 outside the frame's counts), dims [n,T,2] (the clamped row counts), gt_ent [n,T,gcap] and
+        hyp_ent [n,T,hcap] (the row's trajectory, or -1).  assign_max on w viewed as [n*T,gcap,hcap] with dims gives the match."""
+        t = self.torch
+        i32 = lambda *shape: t.empty(shape, dtype=t.int32, device=self.device)
+        n, T, gcap, hcap, stride, label_at = self._hota_inputs(gt_boxes, gt_counts, gt_ids, hyp_boxes, hyp_counts, hyp_ids)
+        acap, bcap = int(align["gt_tab"].shape[1]), int(align["hyp_tab"].shape[1])
+        assert tuple(align["sizes"].shape) == (n, DT_IDENT_INTS) and tuple(align["align"].shape) == (n, acap, bcap)
+        for k, dt in (("sizes", t.int32), ("gt_tab", t.int32), ("hyp_tab", t.int32), ("align", t.int64)):
+            assert align[k].is_cuda and align[k].is_contiguous() and align[k].dtype == dt
+        flags = DT_SCORE_ANY_LABEL if align["any_label"] else 0
+        r = dict(w=i32(n, T, gcap, hcap), dims=i32(n, T, 2), gt_ent=i32(n, T, gcap), hyp_ent=i32(n, T, hcap))
+        self._sync_stream()
+        self._check(self.lib.dt_hota_weights(self.h, _dptr(gt_boxes), _dptr(gt_counts), _dptr(gt_ids), gcap, _dptr(hyp_boxes), _dptr(hyp_counts),
+                                             _dptr(hyp_ids), hcap, stride, label_at, n, T, flags, acap, bcap, _dptr(align["sizes"]),
+                                             _dptr(align["gt_tab"]), _dptr(align["hyp_tab"]), _dptr(align["align"]), _dptr(r["w"]),
+                                             _dptr(r["dims"]), _dptr(r["gt_ent"]), _dptr(r["hyp_ent"])), "dt_hota_weights")
+        return r
+
+    def hota_count(self, gt_boxes, hyp_boxes, weights, row_to_col, thresholds, gt_cap, hyp_cap, state=None):
+        """The matched pairs of every frame counted per IoU level (dt_hota_count): weights is a hota_weights result on these boxes,
+        row_to_col [n*T,gcap] assign_max's match on it, thresholds 1..32 values in (0, 1], strictly ascending, gt_cap / hyp_cap the
+        rows of the two trajectory tables.
+        -> dict: tp [n,n_thr] int32, loc [n,n_thr] int64, pairs [n,n_thr,gt_cap,hyp_cap] int32 -- per BUCKET: a pair whose IoU reaches
+        L >= 1 thresholds is counted in bucket L - 1 only (utility.evaluate.hota takes the suffix sums) -- and thresholds.
+        state: a previous result (of the earlier chunks of these clips) that this call adds to (copied, not written)."""
+        t = self.torch
+        n, T, gcap, _ = gt_boxes.shape
+        hcap = hyp_boxes.shape[2]
+        acap, bcap = int(gt_cap), int(hyp_cap)
+        thr = np.ascontiguousarray(np.asarray(thresholds, dtype=np.float32).reshape(-1))
+        k = len(thr)
+        assert tuple(hyp_boxes.shape) == (n, T, hcap, 8) and gt_boxes.shape[3] == DT_BOX_FLOATS
+        assert tuple(weights["dims"].shape) == (n, T, 2) and tuple(weights["gt_ent"].shape) == (n, T, gcap)
+        assert tuple(weights["hyp_ent"].shape) == (n, T, hcap) and tuple(row_to_col.shape) == (n * T, gcap)
+        for x, dt in ((gt_boxes, t.float32), (hyp_boxes, t.float32), (weights["dims"], t.int32), (weights["gt_ent"], t.int32),
+                      (weights["hyp_ent"], t.int32), (row_to_col, t.int32)):
+            assert x.is_cuda and x.is_contiguous() and x.dtype == dt
+        flags = 0
+        if state is not None:
+            assert np.array_equal(np.asarray(state["thresholds"], dtype=np.float32), thr), "thresholds differ from the state's"
+            assert tuple(state["pairs"].shape) == (n, k, acap, bcap)
+            r = {key: state[key].clone() for key in ("tp", "loc", "pairs")}
+            flags = DT_SCORE_RESUME
+        else:
+            r = dict(tp=t.empty((n, k), dtype=t.int32, device=self.device), loc=t.empty((n, k), dtype=t.int64, device=self.device),
+                     pairs=t.empty((n, k, max(acap, 0), max(bcap, 0)), dtype=t.int32, device=self.device))
+        r["thresholds"] = thr.copy()
+        self._sync_stream()
+        self._check(self.lib.dt_hota_count(self.h, _dptr(gt_boxes), gcap, _dptr(hyp_boxes), hcap, n, T, _dptr(weights["dims"]),
+                                           _dptr(weights["gt_ent"]), _dptr(weights["hyp_ent"]), _dptr(row_to_col),
+                                           thr.ctypes.data_as(ctypes.c_void_p), k, acap, bcap, flags, _dptr(r["tp"]), _dptr(r["loc"]),
+                                           _dptr(r["pairs"])), "dt_hota_count")
+        return r
+
+    def hota_score(self, gt_boxes, gt_counts, gt_ids, hyp_boxes, hyp_counts, hyp_ids, thresholds=None, any_label=False, gt_cap=None,
+                   hyp_cap=None, align=None, state=None):
+        """HOTA scoring (DESIGN.md "HOTA scoring"): hota_align on these inputs (align=None), or a finished hota_align result of the whole
+        clip passed as `align` (any_label, gt_cap and hyp_cap are then that result's); then hota_weights, assign_max on every frame and
+        hota_count.  thresholds: None = utility.evaluate.HOTA_THRESHOLDS (0.05 .. 0.95).
+        -> dict: the alignment's sizes, gt_tab, hyp_tab and align; the count's tp, loc, pairs and thresholds; and the frames' w, dims,
+        gt_ent, hyp_ent and row_to_col [n*T,gcap].  utility.evaluate.hota turns it into HOTA, DetA, AssA, LocA etc.
+        state: the previous chunk's result, whose counts this call adds to.  A clip fed in chunks takes two loops over them: first
+        hota_align(..., state=previous) over all chunks, then hota_score(..., align=the last alignment, state=previous) per chunk."""
+        if thresholds is None:
+            from utility.evaluate import HOTA_THRESHOLDS as thresholds
+        if align is None:
+            align = self.hota_align(gt_boxes, gt_counts, gt_ids, hyp_boxes, hyp_counts, hyp_ids, any_label, gt_cap, hyp_cap)
+        w = self.hota_weights(gt_boxes, gt_counts, gt_ids, hyp_boxes, hyp_counts, hyp_ids, align)
+        n, T, gcap, hcap = w["w"].shape
+        r2c, _, _ = self.assign_max(w["w"].view(n * T, gcap, hcap), w["dims"].view(n * T, 2))
+        r = self.hota_count(gt_boxes, hyp_boxes, w, r2c, thresholds, align["gt_tab"].shape[1], align["hyp_tab"].shape[1], state)
+        r.update(w, row_to_col=r2c, **{k: align[k] for k in ("sizes", "gt_tab", "hyp_tab", "align", "any_label")})
         return r
 
     def _detect_score_inputs(self, det_boxes, det_counts, gt_boxes, gt_counts, gt_flags):

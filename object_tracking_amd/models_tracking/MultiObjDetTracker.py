@@ -392,6 +392,23 @@ class MultiObjDetTracker(object):
             hyp = (result["boxes"], result["counts"], result["ids"])
         return ctx.identity_score(gb, gc, gi, hyp[0], hyp[1], hyp[2], iou_threshold=iou_threshold, any_label=any_label, state=state)
 
+    def hota(self, result, gt, confirmed=False, any_label=False, thresholds=None, align=None, state=None):
+        """HOTA scoring of a track_clips / track_stream result against ground-truth tracks on the device
+        (mi355_dt.Context.hota_score; the rule: DESIGN.md "HOTA scoring"): gt and the choice of hypotheses are score()'s; thresholds:
+        None = utility.evaluate.HOTA_THRESHOLDS.  align / state: for results of track_stream -- a finished Context.hota_align result of
+        the whole run, and the previous chunk's return.  utility.evaluate.hota gives HOTA, DetA, AssA, LocA etc. of the return."""
+        import torch
+        ctx = self.model.ctx
+        dev = lambda a, dt: (a if torch.is_tensor(a) else torch.from_numpy(np.ascontiguousarray(a))).to(device=ctx.device, dtype=dt).contiguous()
+        gb, gc, gi = dev(gt[0], torch.float32), dev(gt[1], torch.int32), dev(gt[2], torch.int32)
+        if confirmed:
+            if result.get("tracks") is None:
+                raise mi355_dt.NativeError("hota(confirmed=True) needs the track read-out in the result (MIN_HITS)")
+            hyp = (result["tracks"], result["track_counts"], result["track_info"])
+        else:
+            hyp = (result["boxes"], result["counts"], result["ids"])
+        return ctx.hota_score(gb, gc, gi, hyp[0], hyp[1], hyp[2], thresholds=thresholds, any_label=any_label, align=align, state=state)
+
     @staticmethod
     def boxes_from_result(res, clip=0):
         """Host view of track_clips output for one clip: list over t of BoundBox lists."""

@@ -1,8 +1,8 @@
-"""Scoring on the host side ("Track scoring", "Identity scoring" and "Detection scoring"): MOT ground truth in,
-CLEAR-MOT and identity figures out; annotation records in, per-class average precision out.
+"""Scoring on the host side ("Track scoring", "Identity scoring", "HOTA scoring" and "Detection scoring"): MOT ground truth in,
+CLEAR-MOT, identity and HOTA figures out; annotation records in, per-class average precision out.
 
 The counting itself runs on the device (mi355_dt.Context.track_score / dt_track_score; Context.identity_score /
-dt_identity_overlap, dt_assign_max; Context.detect_score / dt_detect_match, dt_detect_rank).  This module only prepares its input and turns its integer output into the usual figures, in float64; nothing
+dt_identity_overlap, dt_assign_max; Context.hota_score / dt_hota_align, dt_hota_weights, dt_hota_count; Context.detect_score / dt_detect_match, dt_detect_rank).  This module only prepares its input and turns its integer output into the usual figures, in float64; nothing
 here touches the GPU.
 """
 import numpy as np
@@ -10,6 +10,9 @@ import numpy as np
 DT_BOX_FLOATS = 8
 TOTAL_FIELDS = ("frames", "gt", "hyp", "matches", "switches", "fragments", "overflow")
 MOSTLY_TRACKED, MOSTLY_LOST = 0.8, 0.2
+HOTA_THRESHOLDS = np.array([0.05 * k for k in range(1, 20)], dtype=np.float32)      # 0.05 .. 0.95, the measure's own
+HOTA_SCALE = 1048576                                                                # DT_ASSIGN_IOU_SCALE: loc sums trunc(IoU * 2^20)
+HOTA_ARRAYS = ("HOTA", "DetA", "AssA", "DetRe", "DetPr", "AssRe", "AssPr", "LocA")
 
 
 def _host(a):
@@ -73,6 +76,63 @@ def identity(result):
     tot = sizes.sum(axis=0) if len(sizes) else np.zeros(8, dtype=np.int64)
     pooled = _identity_figures(int(idtp.sum()), int(tot[1]), int(tot[2]), int(tot[3]), int(tot[4]), int(tot[5] + tot[6]))
     return dict(clips=clips, pooled=pooled)
+
+
+def _hota_sums(sizes, gt_tab, hyp_tab, tp, loc, pairs):
+    """one clip's buckets -> what pools over clips: per threshold TP, L, sum m A, sum m m / n_a, sum m m / n_b; and gt, hyp"""
+    n_a = gt_tab[:, 1].astype(np.float64)[None, :, None]
+    n_b = hyp_tab[:, 1].astype(np.float64)[None, None, :]
+    suffix = lambda x: np.cumsum(x[::-1], axis=0)[::-1]          # a pair that passes threshold k passes every lower one
+    TP, L, m = suffix(tp.astype(np.int64)), suffix(loc.astype(np.int64)), suffix(pairs.astype(np.int64)).astype(np.float64)
+    ass = (m * (m / np.maximum(1.0, n_a + n_b - m))).sum(axis=(1, 2))
+    re = (m * (m / np.maximum(1.0, n_a))).sum(axis=(1, 2))
+    pr = (m * (m / np.maximum(1.0, n_b))).sum(axis=(1, 2))
+    return dict(TP=TP, L=L, ass=ass, re=re, pr=pr, gt=int(sizes[1]), hyp=int(sizes[2]))
+
+
+def _hota_figures(s, gt_tracks, hyp_tracks, overflow):
+    TP = s["TP"].astype(np.float64)
+    FN, FP = s["gt"] - TP, s["hyp"] - TP
+    one = np.maximum(1.0, TP)
+    out = dict(TP=s["TP"].copy(), FN=s["gt"] - s["TP"], FP=s["hyp"] - s["TP"], gt=s["gt"], hyp=s["hyp"], gt_tracks=gt_tracks,
+               hyp_tracks=hyp_tracks, overflow=overflow)
+    out["DetA"], out["DetRe"], out["DetPr"] = TP / np.maximum(1.0, TP + FN + FP), TP / np.maximum(1.0, TP + FN), TP / np.maximum(1.0, TP + FP)
+    out["AssA"], out["AssRe"], out["AssPr"] = s["ass"] / one, s["re"] / one, s["pr"] / one
+    out["HOTA"] = np.sqrt(out["DetA"] * out["AssA"])
+    out["LocA"] = np.where(s["TP"] > 0, s["L"].astype(np.float64) / (float(HOTA_SCALE) * one), 1.0)
+    for k in HOTA_ARRAYS:
+        out[k.lower()] = float(out[k].mean())
+    out["hota0"], out["loca0"] = float(out["HOTA"][0]), float(out["LocA"][0])
+    return out
+
+
+def hota(result):
+    """A Context.hota_score result (of a resumed run: its last one; a list's last entry is taken) -> dict(clips=[...], pooled=...).
+    Every entry has, per threshold (arrays of len(thresholds), float64 but for the counts):
+      TP, FN = gt - TP, FP = hyp - TP         TP at threshold k: the matched pairs whose IoU reaches it (the buckets k and above)
+      DetA = TP / (TP + FN + FP), DetRe = TP / (TP + FN), DetPr = TP / (TP + FP)
+      AssA = sum m A / TP with A(a, b) = m / (n_a + n_b - m), m[a][b] the pairs of the trajectories a, b among the TP and n their boxes;
+      AssRe = sum m (m / n_a) / TP, AssPr = sum m (m / n_b) / TP
+      HOTA = sqrt(DetA AssA);  LocA = loc / (2^20 TP), the mean truncated IoU of the TP
+    their means over the thresholds (hota, deta, assa, detre, detpr, assre, asspr, loca), the first threshold's hota0 and loca0, and
+    gt, hyp (boxes), gt_tracks, hyp_tracks (trajectories), overflow (boxes whose id found its table full).
+    Every denominator is max(1, .) and LocA is 1.0 where TP = 0 -- TrackEval's conventions, so that figures compare with published ones
+    (summarize and identity return nan there instead).  `pooled` adds TP, gt, hyp, loc and the sums over m of all clips before the ratios
+    are taken (objects of different clips are different objects)."""
+    last = result[-1] if isinstance(result, (list, tuple)) else result
+    sizes, gt_tab, hyp_tab = _host(last["sizes"]).astype(np.int64), _host(last["gt_tab"]), _host(last["hyp_tab"])
+    tp, loc, pairs = _host(last["tp"]), _host(last["loc"]), _host(last["pairs"])
+    n_thr = tp.shape[1]
+    sums = [_hota_sums(sizes[k], gt_tab[k], hyp_tab[k], tp[k], loc[k], pairs[k]) for k in range(len(sizes))]
+    clips = [_hota_figures(s, int(sizes[k][3]), int(sizes[k][4]), int(sizes[k][5] + sizes[k][6])) for k, s in enumerate(sums)]
+    tot = sizes.sum(axis=0) if len(sizes) else np.zeros(8, dtype=np.int64)
+    pool = dict(TP=np.zeros(n_thr, dtype=np.int64), L=np.zeros(n_thr, dtype=np.int64), ass=np.zeros(n_thr), re=np.zeros(n_thr),
+                pr=np.zeros(n_thr), gt=0, hyp=0)
+    for s in sums:
+        for k in pool:
+            pool[k] = pool[k] + s[k]
+    return dict(clips=clips, pooled=_hota_figures(pool, int(tot[3]), int(tot[4]), int(tot[5] + tot[6])),
+                thresholds=np.asarray(last["thresholds"], dtype=np.float32).copy())
 
 
 def gt_from_mot(lines, width, height, T, gcap, classes=None):
