@@ -78,6 +78,7 @@ DT_API int dt_set_stream(dt_ctx *ctx, void *hip_stream);
  * and the three HOTA scoring entries dt_hota_align, dt_hota_weights, dt_hota_count
  * and the two track assignment entries dt_associate_tracks_assign, dt_associate_stream_tracks_assign
  * and the three Winograd transform test entries dt_wino_geometry, dt_wino_input, dt_wino_output
+ * and the one implicit-GEMM kernel test entry dt_conv_igemm
  * -- additions only, the number stayed; 1.07: 1.06 + dt_gemm_split, dt_policy_set) */
 DT_API int dt_abi_version(void);
 
@@ -837,6 +838,36 @@ DT_API int dt_wino_input(dt_ctx *ctx, const float *d_in, int B, int H, int W, in
 DT_API int dt_wino_output(dt_ctx *ctx, const float *d_m, long long m_floats, int m_ld, int N, int B, int H, int W, int ts, const float *d_bias,
                           const float *d_bias16, float slope, float *d_out, int out_ld, float *d_out2, int out2_ld, int publish,
                           const float *d_xproj, int xp_ld, float *d_cstate, int c_ld, int force_form, int wg_cap, int *h_geom);
+
+/* The fp32 implicit-GEMM kernel ALONE (csrc/conv_igemm.hip) on caller views with strides: no policy, no kernel-form choice, the tile
+ * configuration `cfg` handed straight to the production launcher (tests/test_gpu_conv_igemm_edges.py).
+ *   layer mode (P <= 1): d_in [B][H][W][in_ld >= Cin] with frames in_bs >= H*W*in_ld floats apart (1x1 plain / gates / split-K: dense frames,
+ *     as the launcher demands), h_kernel Keras HWIO [ks][ks][Cin][N] and h_bias [N] or null, packed and padded as a loaded layer's are
+ *     (npad = 0: N rounded up to 256; else the weight rows to allocate, a multiple of 128 >= N -- what the 256x256 fallback looks at);
+ *   batched-GEMM mode (P > 1, ks = 1, kind plain, H = 1, W = Mt): d_in [P][Mt][Cin] and d_wt [P][N][Cin] device operands, d_out [P][Mt][out_ld],
+ *     no bias -- the Winograd GEMMs' launch.
+ *   kind: DT_CONV_PLAIN  d_out [B*H*W][out_ld >= N];  DT_CONV_POOL  d_out [B*H/2*W/2][out_ld >= N] 2x2 max;  DT_CONV_POOL_BOTH (ks 3)  d_out
+ *     unpooled and d_out2 [..][out2_ld >= N] pooled;  DT_CONV_S2D (ks 1)  d_out [B*H/2*W/2][out_ld >= 4 N] tf.space_to_depth(2);
+ *     DT_CONV_GATES  N = 4 U Keras gate columns (i, f, c, o), no bias: z = conv + d_xproj [B*H*W][xp_ld >= N] in PACKED column order
+ *     [j/32][gate][j%32], d_cstate [B*H*W][c_ld >= U] updated in place, h to d_out [B*H*W][out_ld >= U];
+ *     DT_CONV_PARTIAL or ksplit > 1 (plain only): split-K partial sums over ksplit <= ks*ks*Cin/32 ranges into a slab, then the reduce kernel
+ *     (bias, LeakyReLU) into d_out.
+ *   slope: LeakyReLU slope (1 = linear); act: 1 = sigmoid instead; publish != 0: max |x| of the stored values (the pooled ones where the kind
+ *     pools) into max-|x| slot 57, zeroed first; wg_cap > 0: a persistent launch uses at most so many workgroups (ConvArgs' test-only field).
+ * h_info[DT_CONV_INFO_INTS] receives what ran: the resolved tile configuration (DT_CFG_*), BM, BN, threads per workgroup, 1 if the instance is
+ * the persistent one, grid x, grid y, tiles in all.  DT_ERR_ARG, and no launch, for what the launcher refuses. */
+#define DT_CONV_INFO_INTS 8
+enum { DT_CONV_PLAIN = 0, DT_CONV_POOL, DT_CONV_POOL_BOTH, DT_CONV_S2D, DT_CONV_GATES, DT_CONV_PARTIAL };
+enum { DT_CFG_128x128 = 0, DT_CFG_128x64, DT_CFG_256x128, DT_CFG_256x256, DT_CFG_64x128 };
+typedef struct dt_conv_igemm_desc {
+    int32_t ks, B, H, W, Cin, N, P, in_ld;
+    int64_t in_bs;
+    int32_t npad, kind, cfg, ksplit, act, publish, wg_cap;
+    float slope;
+    int32_t out_ld, out2_ld, xp_ld, c_ld;
+} dt_conv_igemm_desc;
+DT_API int dt_conv_igemm(dt_ctx *ctx, const dt_conv_igemm_desc *desc, const float *d_in, const float *h_kernel, const float *h_bias, const float *d_wt,
+                         float *d_out, float *d_out2, const float *d_xproj, float *d_cstate, int *h_info);
 
 /* ---- tuning / test knobs ------------------------------------------------- *
  * The DT_* environment variables of DESIGN.md's appendix are read in dt_create (no launch path calls getenv);

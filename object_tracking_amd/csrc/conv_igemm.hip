@@ -310,7 +310,8 @@ __global__ __launch_bounds__(64 * WGM * WGN, (WGM * WGN > 4 ? (WGM * WGN) / 4 : 
         }
         // Raw GEMM output (the batched Winograd GEMMs: no bias, linear): the epilogue of a 256x256 tile is VALU-issue
         // bound (6 us, from per-tile cycle stamps), so skip the activation arithmetic and walk the rows with one pointer
-        if (EPI == EPI_PLAIN && PERSIST && p.bias == nullptr && p.slope == 1.0f && p.act == 0) {
+        // (not when the launch publishes max |x|: this form keeps no maximum.  The condition is the same for every tile of a launch.)
+        if (EPI == EPI_PLAIN && PERSIST && p.bias == nullptr && p.slope == 1.0f && p.act == 0 && p.amax_out == nullptr) {
     #pragma unroll
             for (int i = 0; i < TM; ++i)
     #pragma unroll
@@ -514,10 +515,84 @@ __global__ __launch_bounds__(64 * WGM * WGN, (WGM * WGN > 4 ? (WGM * WGN) / 4 : 
     if ((EPI == EPI_PLAIN || EPI == EPI_POOL || EPI == EPI_POOL_BOTH || EPI == EPI_S2D) && p.amax_out) dt_amax_publish(p.amax_out, out_am);
 }
 
-template <int KS, int BM, int BN, int WGM, int WGN, int ORDER, int EPI, bool PERSIST = false>
-static int launch_one(hipStream_t st, const ConvArgs &a, int ksplit = 1)
+// ---- which instance runs, on what grid ----------------------------------------------------------------------------------
+// plan_conv_igemm is the ONE place that resolves a launch: what the launcher refuses, the tile configuration after the
+// caller's forced one and the 256x256 -> 256x128 fallback, the gate / split-K instances' own tiles, and the grid.
+// launch_conv_igemm dispatches on its result and launch_one launches its grid; the test entry dt_conv_igemm reports it.
+static int conv_cus()
 {
-    const int ntm = (a.M + BM - 1) / BM, ntn = (a.N + BN - 1) / BN;
+    static const int cus = [] {
+        int dev = 0, n = 0;
+        if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || n <= 0)
+            n = 256;
+        return n;
+    }();
+    return cus;
+}
+
+ConvPlan plan_conv_igemm(const ConvArgs &a, int ks, int order, int epi, int cfg)
+{
+    ConvPlan pl{};
+    pl.rc = 2;
+    // a caller-forced tile configuration (Policy::conv_cfg: A/B runs and the tests that exercise every
+    // configuration at small shapes) applies to the 128-wide-or-wider layers
+    if (a.force_cfg > 0 && cfg != CFG_128x64 && cfg != CFG_64x128 && epi != EPI_PARTIAL) cfg = a.force_cfg - 1;
+    if (cfg == CFG_256x256) {   // the column tile may only read weight rows that exist
+        const int have = a.npad ? a.npad : (a.N + 127) / 128 * 128;
+        if (have < (a.N + 255) / 256 * 256) cfg = CFG_256x128;
+    }
+    if (ks != 1 && ks != 3) return pl;
+    if (a.M <= 0 || a.N <= 0 || a.Cin <= 0 || a.Cin % KCH != 0 || a.K != ks * ks * a.Cin) return pl;
+    if (ks == 1 && order == ORD_LINEAR && a.in_bs != (long long)a.H * a.W * a.in_ld) return pl;   // flat row addressing
+    if (order == ORD_QUAD && ((a.H | a.W) & 1)) return pl;   // the quad epilogues store all four pixels of a 2x2 window
+    int wgm = 2, wgn = 2;
+    pl.bm = 128; pl.bn = 128; pl.grid_y = 1;
+    if (epi == EPI_GATES) {
+        if (order != ORD_LINEAR) return pl;
+        if (ks == 3 && cfg == CFG_256x256) { pl.cfg = CFG_256x256; pl.bm = 256; pl.bn = 256; wgm = 8; wgn = 2; }   // 16 waves
+        else { pl.cfg = CFG_128x128; wgm = 4; wgn = 1; }
+    } else if (epi == EPI_PARTIAL) {
+        if (order != ORD_LINEAR || a.ksplit < 1) return pl;
+        pl.cfg = CFG_128x128; pl.grid_y = a.ksplit;
+    } else {
+        if (order == ORD_LINEAR ? epi != EPI_PLAIN
+                                : !(epi == EPI_POOL || (epi == EPI_POOL_BOTH && ks == 3) || (epi == EPI_S2D && ks == 1)))
+            return pl;
+        pl.cfg = cfg;
+        switch (cfg) {
+        case CFG_128x64: pl.bm = 128; pl.bn = 64; wgm = 4; wgn = 1; break;
+        case CFG_64x128: pl.bm = 64; pl.bn = 128; break;                            // few rows (a handful of Winograd tiles)
+        case CFG_256x128: pl.bm = 256; pl.bn = 128; wgm = 4; wgn = 2; break;         // 8 waves, 1 workgroup per CU
+        case CFG_256x256: pl.bm = 256; pl.bn = 256; wgm = 4; wgn = 4; break;         // 16 waves, 1 workgroup per CU
+        default: pl.cfg = CFG_128x128; break;
+        }
+        // The GEMM-shaped launches (1x1 layers and the batched Winograd GEMMs: short K, many tiles) use the
+        // persistent form of the kernel; the 3x3 layers keep one tile per workgroup (long K per tile, and the
+        // extra live state of the tile loop costs them registers).
+        pl.persist = (ks == 1 && order == ORD_LINEAR && epi == EPI_PLAIN) ? 1 : 0;
+    }
+    pl.wgm = wgm; pl.wgn = wgn;
+    pl.threads = 64 * wgm * wgn;
+    const long long total = (long long)((a.M + pl.bm - 1) / pl.bm) * ((a.N + pl.bn - 1) / pl.bn) * (a.zbatch > 1 ? a.zbatch : 1);
+    if (total > 0x7fffffffll) return pl;
+    pl.total = (int)total;
+    // one workgroup per tile, or -- with more tiles than resident slots -- a persistent grid of one
+    // workgroup per slot (256 CUs x 2 four-wave workgroups, or x 1 of the 8/16-wave ones) that walks the tiles
+    int grid = pl.total;
+    if (pl.persist) {
+        const int slots = ((conv_cus() * (wgm * wgn > 4 ? 1 : 2)) / 8) * 8;   // multiple of 8: L % 8 stays the XCD
+        if (slots > 0 && grid > slots) grid = slots;
+        if (a.wg_cap > 0 && grid > a.wg_cap) grid = a.wg_cap;   // (test only: ConvArgs::wg_cap)
+    }
+    pl.grid_x = grid;
+    pl.rc = 0;
+    return pl;
+}
+
+template <int KS, int BM, int BN, int WGM, int WGN, int ORDER, int EPI, bool PERSIST = false>
+static int launch_one(hipStream_t st, const ConvArgs &a, const ConvPlan &pl)
+{
+    if (pl.bm != BM || pl.bn != BN || pl.wgm != WGM || pl.wgn != WGN || pl.persist != (PERSIST ? 1 : 0)) return 1;   // the plan and the dispatch disagree
     const size_t lds = (size_t)NSTAGE * (BM + BN) * LDK * sizeof(float);
     auto kern = conv_igemm_f32<KS, BM, BN, WGM, WGN, ORDER, EPI, PERSIST>;
     static PerDeviceOnce attr;
@@ -525,33 +600,19 @@ static int launch_one(hipStream_t st, const ConvArgs &a, int ksplit = 1)
             return hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess;
         }))
         return 1;
-    // one workgroup per tile, or -- with more tiles than resident slots -- a persistent grid of one
-    // workgroup per slot (256 CUs x 2 four-wave workgroups, or x 1 of the 8/16-wave ones) that walks the tiles
-    int grid = ntm * ntn * (a.zbatch > 1 ? a.zbatch : 1);
-    static const int cus = [] {
-        int dev = 0, n = 0;
-        if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || n <= 0)
-            n = 256;
-        return n;
-    }();
-    const int slots = ((cus * (WGM * WGN > 4 ? 1 : 2)) / 8) * 8;   // multiple of 8: L % 8 stays the XCD
-    if (PERSIST && ksplit == 1 && slots > 0 && grid > slots) grid = slots;
-    hipLaunchKernelGGL(kern, dim3((unsigned)grid, (unsigned)ksplit), dim3(64 * WGM * WGN), lds, st, a);
+    hipLaunchKernelGGL(kern, dim3((unsigned)pl.grid_x, (unsigned)pl.grid_y), dim3(64 * WGM * WGN), lds, st, a);
     return hipGetLastError() == hipSuccess ? 0 : 1;
 }
 
 template <int KS, int ORDER, int EPI>
-static int launch_cfg(hipStream_t st, const ConvArgs &a, int cfg)
+static int launch_cfg(hipStream_t st, const ConvArgs &a, const ConvPlan &pl)
 {
-    // The GEMM-shaped launches (1x1 layers and the batched Winograd GEMMs: short K, many tiles) use the
-    // persistent form of the kernel; the 3x3 layers keep one tile per workgroup (long K per tile, and the
-    // extra live state of the tile loop costs them registers).
     constexpr bool P = (KS == 1 && ORDER == ORD_LINEAR && EPI == EPI_PLAIN);
-    if (cfg == CFG_128x64) return launch_one<KS, 128, 64, 4, 1, ORDER, EPI, P>(st, a);
-    if (cfg == CFG_64x128) return launch_one<KS, 64, 128, 2, 2, ORDER, EPI, P>(st, a);       // few rows (a handful of Winograd tiles)
-    if (cfg == CFG_256x128) return launch_one<KS, 256, 128, 4, 2, ORDER, EPI, P>(st, a);   // 8 waves, 1 workgroup per CU
-    if (cfg == CFG_256x256) return launch_one<KS, 256, 256, 4, 4, ORDER, EPI, P>(st, a);   // 16 waves, 1 workgroup per CU
-    return launch_one<KS, 128, 128, 2, 2, ORDER, EPI, P>(st, a);
+    if (pl.cfg == CFG_128x64) return launch_one<KS, 128, 64, 4, 1, ORDER, EPI, P>(st, a, pl);
+    if (pl.cfg == CFG_64x128) return launch_one<KS, 64, 128, 2, 2, ORDER, EPI, P>(st, a, pl);
+    if (pl.cfg == CFG_256x128) return launch_one<KS, 256, 128, 4, 2, ORDER, EPI, P>(st, a, pl);
+    if (pl.cfg == CFG_256x256) return launch_one<KS, 256, 256, 4, 4, ORDER, EPI, P>(st, a, pl);
+    return launch_one<KS, 128, 128, 2, 2, ORDER, EPI, P>(st, a, pl);
 }
 
 int launch_conv_igemm(hipStream_t st, const ConvArgs &a_in, int ks, int order, int epi, int cfg)
@@ -560,13 +621,8 @@ int launch_conv_igemm(hipStream_t st, const ConvArgs &a_in, int ks, int order, i
     // column tiles per group of the tile order: measured FETCH_SIZE optimum is 1 for the 3x3
     // layers (all ~64 workgroups resident on an XCD share ONE weight panel) and 2 for 1x1 / gates
     a.tile_gn = (ks == 3 && epi != EPI_GATES) ? 1 : 2;
-    // a caller-forced tile configuration (Policy::conv_cfg: A/B runs and the tests that exercise every
-    // configuration at small shapes) applies to the 128-wide-or-wider layers
-    if (a.force_cfg > 0 && cfg != CFG_128x64 && cfg != CFG_64x128 && epi != EPI_PARTIAL) cfg = a.force_cfg - 1;
-    if (cfg == CFG_256x256) {   // the column tile may only read weight rows that exist
-        const int have = a.npad ? a.npad : (a.N + 127) / 128 * 128;
-        if (have < (a.N + 255) / 256 * 256) cfg = CFG_256x128;
-    }
+    const ConvPlan pl = plan_conv_igemm(a, ks, order, epi, cfg);
+    if (pl.rc) return pl.rc;
     static float *zeros_dev[64];   // per device: 256 B of zeros for the padding taps
     static PerDeviceOnce zeros_once;
     int dev = 0;
@@ -579,31 +635,24 @@ int launch_conv_igemm(hipStream_t st, const ConvArgs &a_in, int ks, int order, i
         }))
         return 1;
     a.zeros = zeros_dev[dev];
-    if (a.Cin % KCH != 0 || a.K != ks * ks * a.Cin) return 2;
-    if (ks == 1 && order == ORD_LINEAR && a.in_bs != (long long)a.H * a.W * a.in_ld) return 2;   // flat row addressing
     if (epi == EPI_GATES) {
-        if (order != ORD_LINEAR) return 2;
-        if (ks == 3 && cfg == CFG_256x256) return launch_one<3, 256, 256, 8, 2, ORD_LINEAR, EPI_GATES>(st, a);   // 16 waves
-        if (ks == 3) return launch_one<3, 128, 128, 4, 1, ORD_LINEAR, EPI_GATES>(st, a);
-        return launch_one<1, 128, 128, 4, 1, ORD_LINEAR, EPI_GATES>(st, a);
+        if (ks == 3 && pl.cfg == CFG_256x256) return launch_one<3, 256, 256, 8, 2, ORD_LINEAR, EPI_GATES>(st, a, pl);
+        if (ks == 3) return launch_one<3, 128, 128, 4, 1, ORD_LINEAR, EPI_GATES>(st, a, pl);
+        return launch_one<1, 128, 128, 4, 1, ORD_LINEAR, EPI_GATES>(st, a, pl);
     }
-    if (epi == EPI_PARTIAL) {
-        if (order != ORD_LINEAR || a.ksplit < 1) return 2;
-        return ks == 3 ? launch_one<3, 128, 128, 2, 2, ORD_LINEAR, EPI_PARTIAL>(st, a, a.ksplit)
-                       : launch_one<1, 128, 128, 2, 2, ORD_LINEAR, EPI_PARTIAL>(st, a, a.ksplit);
-    }
-    if (order == ORD_LINEAR) {
-        if (epi != EPI_PLAIN) return 2;
-        return ks == 3 ? launch_cfg<3, ORD_LINEAR, EPI_PLAIN>(st, a, cfg) : launch_cfg<1, ORD_LINEAR, EPI_PLAIN>(st, a, cfg);
-    }
-    // ORD_QUAD
+    if (epi == EPI_PARTIAL)
+        return ks == 3 ? launch_one<3, 128, 128, 2, 2, ORD_LINEAR, EPI_PARTIAL>(st, a, pl)
+                       : launch_one<1, 128, 128, 2, 2, ORD_LINEAR, EPI_PARTIAL>(st, a, pl);
+    if (order == ORD_LINEAR)
+        return ks == 3 ? launch_cfg<3, ORD_LINEAR, EPI_PLAIN>(st, a, pl) : launch_cfg<1, ORD_LINEAR, EPI_PLAIN>(st, a, pl);
+    // ORD_QUAD (plan_conv_igemm has refused every other combination)
     switch (epi) {
     case EPI_POOL:
-        return ks == 3 ? launch_cfg<3, ORD_QUAD, EPI_POOL>(st, a, cfg) : launch_cfg<1, ORD_QUAD, EPI_POOL>(st, a, cfg);
+        return ks == 3 ? launch_cfg<3, ORD_QUAD, EPI_POOL>(st, a, pl) : launch_cfg<1, ORD_QUAD, EPI_POOL>(st, a, pl);
     case EPI_POOL_BOTH:
-        return ks == 3 ? launch_cfg<3, ORD_QUAD, EPI_POOL_BOTH>(st, a, cfg) : 2;
+        return launch_cfg<3, ORD_QUAD, EPI_POOL_BOTH>(st, a, pl);
     case EPI_S2D:
-        return ks == 1 ? launch_cfg<1, ORD_QUAD, EPI_S2D>(st, a, cfg) : 2;
+        return launch_cfg<1, ORD_QUAD, EPI_S2D>(st, a, pl);
     default:
         return 2;
     }

@@ -76,16 +76,25 @@ struct ConvArgs {
     const float *zeros; // >= 16 B of device zeros: source of out-of-image taps (set by launch_conv_igemm)
     int ksplit;    // EPI_PARTIAL: number of K splits (grid.y); out = slab [ksplit][M][out_ld]
     int tile_gn;   // column tiles per group in the tile order (0 = all; set by launch_conv_igemm)
-    // batched GEMMs (Winograd positions): grid.z problems, blockIdx.z advances in / wt / out by these (floats)
+    // batched GEMMs (Winograd positions): zbatch problems of ntiles tiles each share ONE linear tile index (tile t belongs to problem
+    // z = t / ntiles); problem z reads in + z*z_in, wt + z*z_wt and writes out + z*z_out (floats)
     int zbatch;
     long long z_in, z_wt, z_out;
     int force_cfg; // > 0: tile configuration + 1 forced by the caller's policy (Policy::conv_cfg); 0: none
     unsigned *amax_out; // EPI_PLAIN (no split-K) / EPI_POOL / EPI_S2D: non-null = max |x| of the stored outputs into this slot (dt_amax_publish)
+    int wg_cap;    // test only (dt_conv_igemm), 0 in production -- like WinoArgs::wg_cap: > 0 = a persistent launch uses at most this many workgroups
 };
 
 // Tile configurations of the MFMA kernel
 enum { CFG_128x128 = 0, CFG_128x64 = 1, CFG_256x128 = 2, CFG_256x256 = 3, CFG_64x128 = 4 };
 
+// What launch_conv_igemm does with a call (plan_conv_igemm): rc 0 = launches, 2 = refuses the arguments; the tile configuration that runs
+// (after a forced one, the 256x256 -> 256x128 fallback and the gate / split-K instances' own tiles), its tile and workgroup shape,
+// whether the instance is the persistent one, and the grid over `total` tiles.
+struct ConvPlan {
+    int rc, cfg, bm, bn, wgm, wgn, threads, persist, grid_x, grid_y, total;
+};
+ConvPlan plan_conv_igemm(const ConvArgs &a, int ks, int order, int epi, int cfg);
 int launch_conv_igemm(hipStream_t st, const ConvArgs &a, int ks, int order, int epi, int cfg);
 int launch_splitk_reduce(hipStream_t st, const float *slab, int S, long long M, int N, const float *bias, float slope,
                          float *out, int out_ld);

@@ -3096,6 +3096,100 @@ extern "C" int dt_wino_output(dt_ctx *ctx, const float *d_m, long long m_floats,
     return DT_OK;
 }
 
+// conv_igemm.hip ALONE on caller views (tests/test_gpu_conv_igemm_edges.py): the production weight packing, the production launcher with the tile
+// configuration it is handed (force_cfg = 0: no policy reaches it), and -- for split-K -- the slab and the reduce kernel as conv_igemm() above runs
+// them.  h_info = what plan_conv_igemm, the function the launcher itself dispatches on, resolved.
+static_assert(DT_CONV_PLAIN == EPI_PLAIN && DT_CONV_POOL == EPI_POOL && DT_CONV_POOL_BOTH == EPI_POOL_BOTH && DT_CONV_S2D == EPI_S2D && DT_CONV_GATES == EPI_GATES &&
+                  DT_CONV_PARTIAL == EPI_PARTIAL && DT_CFG_128x128 == CFG_128x128 && DT_CFG_128x64 == CFG_128x64 && DT_CFG_256x128 == CFG_256x128 &&
+                  DT_CFG_256x256 == CFG_256x256 && DT_CFG_64x128 == CFG_64x128,
+              "the codes dt_conv_igemm takes and reports (mi355_dt.h)");
+extern "C" int dt_conv_igemm(dt_ctx *ctx, const dt_conv_igemm_desc *desc, const float *d_in, const float *h_kernel, const float *h_bias, const float *d_wt,
+                             float *d_out, float *d_out2, const float *d_xproj, float *d_cstate, int *h_info)
+{
+    if (!ctx || !desc || !d_in || !d_out || !h_info) return dt_fail(ctx, DT_ERR_ARG, "null argument");
+    call_begin(ctx, 0);
+    const dt_conv_igemm_desc &d = *desc;
+    const int ks = d.ks, B = d.B, H = d.H, W = d.W, Cin = d.Cin, N = d.N, P = d.P > 1 ? d.P : 1;
+    const bool batched = P > 1, gates = d.kind == DT_CONV_GATES, split = d.kind == DT_CONV_PARTIAL || d.ksplit > 1;
+    const int epi = split ? EPI_PARTIAL : d.kind, order = (epi == EPI_POOL || epi == EPI_POOL_BOTH || epi == EPI_S2D) ? ORD_QUAD : ORD_LINEAR;
+    const int ksplit = d.ksplit > 1 ? d.ksplit : 1;
+    memset(h_info, 0, DT_CONV_INFO_INTS * sizeof(int));
+    if ((ks != 1 && ks != 3) || B <= 0 || H <= 0 || W <= 0 || Cin <= 0 || N <= 0 || (long long)B * H * W >= (1ll << 24) || d.in_ld < Cin ||
+        d.in_bs < (long long)H * W * d.in_ld || d.kind < DT_CONV_PLAIN || d.kind > DT_CONV_PARTIAL || d.cfg < 0 || d.cfg > CFG_64x128 || d.wg_cap < 0 || d.ksplit < 0 ||
+        (d.act != 0 && d.act != 1) || (split && d.kind != DT_CONV_PLAIN && d.kind != DT_CONV_PARTIAL) || (long long)ksplit * 32 > (long long)ks * ks * Cin ||
+        (d.npad != 0 && (d.npad % 128 || d.npad < N)) || ((d.publish || d.act) && (split || gates)))
+        return dt_fail(ctx, DT_ERR_ARG, "dt_conv_igemm: unsupported arguments ks=%d B=%d H=%d W=%d Cin=%d N=%d in_ld=%d in_bs=%lld kind=%d cfg=%d ksplit=%d npad=%d wg_cap=%d",
+                       ks, B, H, W, Cin, N, d.in_ld, (long long)d.in_bs, d.kind, d.cfg, d.ksplit, d.npad, d.wg_cap);
+    const int out_cols = gates ? N / 4 : (epi == EPI_S2D ? 4 * N : N);
+    if (d.out_ld < out_cols || (epi == EPI_POOL_BOTH && (!d_out2 || d.out2_ld < N)) || (epi != EPI_POOL_BOTH && d_out2))
+        return dt_fail(ctx, DT_ERR_ARG, "dt_conv_igemm: kind %d writes %d columns to d_out (out_ld=%d) and %s d_out2 (out2_ld=%d)", d.kind, out_cols, d.out_ld,
+                       epi == EPI_POOL_BOTH ? "the pooled tensor to" : "has no", d.out2_ld);
+    if (gates ? (N % 128 || !d_xproj || !d_cstate || h_bias || d.xp_ld < N || d.c_ld < N / 4 || d.slope != 1.0f) : (d_xproj || d_cstate))
+        return dt_fail(ctx, DT_ERR_ARG, "dt_conv_igemm: the gate kind takes N = 4 U (U %% 32 == 0), xproj [..][xp_ld >= N], cstate [..][c_ld >= U], no bias; no other kind takes them");
+    if (batched ? (ks != 1 || d.kind != DT_CONV_PLAIN || split || B != 1 || H != 1 || !d_wt || h_kernel || h_bias || d.in_ld != Cin || d.in_bs != (long long)W * Cin)
+                : (!h_kernel || d_wt))
+        return dt_fail(ctx, DT_ERR_ARG, "dt_conv_igemm: P > 1 is the batched GEMM (ks 1, plain, B = H = 1, W = Mt, dense [P][Mt][Cin] and d_wt [P][N][Cin], no bias); "
+                                        "P <= 1 takes h_kernel");
+    const int K = ks * ks * Cin, M = B * H * W;
+    const int npad = gates ? N : (d.npad ? d.npad : round_up(N, 256));
+    ConvArgs a{};
+    a.in = d_in; a.in_ld = d.in_ld; a.in_bs = d.in_bs;
+    a.out = d_out; a.out_ld = d.out_ld; a.out_bs = (long long)H * W * d.out_ld;
+    a.out2 = d_out2; a.out2_ld = d.out2_ld;
+    a.xproj = d_xproj; a.xp_ld = d.xp_ld; a.xp_bs = (long long)H * W * d.xp_ld;
+    a.cstate = d_cstate; a.c_ld = d.c_ld; a.c_bs = (long long)H * W * d.c_ld;
+    a.B = B; a.H = H; a.W = W; a.Cin = Cin; a.N = N; a.M = M; a.K = K;
+    a.npad = gates ? 0 : npad; a.slope = d.slope; a.act = d.act; a.wg_cap = d.wg_cap;
+    if (batched) {      // as run_wino fills it
+        a.out_bs = (long long)M * d.out_ld;
+        a.zbatch = P; a.z_in = (long long)M * Cin; a.z_wt = (long long)npad * K; a.z_out = (long long)M * d.out_ld;
+    }
+    if (split) { a.out_ld = N; a.ksplit = ksplit; }      // as conv_igemm() above: raw partial sums to a dense slab, bias and activation in the reduce
+    // the launcher's own verdict BEFORE anything is packed or allocated (pack_conv_weights relies on Cin % 32 == 0)
+    const ConvPlan pl = plan_conv_igemm(a, ks, order, epi, d.cfg);
+    if (pl.rc) return dt_fail(ctx, DT_ERR_ARG, "dt_conv_igemm: the launcher refuses ks=%d kind=%d H=%d W=%d Cin=%d in_ld=%d in_bs=%lld (Cin %% 32, even H and W for the "
+                                               "quad kinds, dense frames for a 1x1 linear launch)", ks, d.kind, H, W, Cin, d.in_ld, (long long)d.in_bs);
+    const int info[DT_CONV_INFO_INTS] = {pl.cfg, pl.bm, pl.bn, pl.threads, pl.persist, pl.grid_x, pl.grid_y, pl.total};
+    memcpy(h_info, info, sizeof(info));
+    std::vector<float> packed, bias;
+    std::vector<int> n_map;
+    DevMem<float> wt, bs, slab;
+    SyncAtExit idle{ctx->stream};
+    int rc;
+    if (batched) {      // [P][N][K] -> [P][npad][K], the rows behind N zero (as upload_wino pads U)
+        HIP_TRY(ctx, wt.alloc((size_t)P * npad * K));
+        HIP_TRY(ctx, hipMemsetAsync(wt.get(), 0, (size_t)P * npad * K * sizeof(float), ctx->stream));
+        HIP_TRY(ctx, hipMemcpy2DAsync(wt.get(), (size_t)npad * K * sizeof(float), d_wt, (size_t)N * K * sizeof(float), (size_t)N * K * sizeof(float), P,
+                                      hipMemcpyDeviceToDevice, ctx->stream));
+    } else {
+        packed.resize((size_t)npad * K);
+        if (gates) gate_interleave_map(N / 4, n_map);      // as dt_convlstm_step / dt_tracker_load pack the recurrent kernel
+        pack_conv_weights(h_kernel, ks, Cin, N, nullptr, Cin, gates ? n_map.data() : nullptr, npad, nullptr, packed.data());
+        if ((rc = upload(ctx, wt, packed))) return rc;
+        if (h_bias) {      // padded to npad, as load_conv_layer does
+            bias.assign((size_t)npad, 0.0f);
+            for (int c = 0; c < N; ++c) bias[c] = h_bias[c];
+            if ((rc = upload(ctx, bs, bias))) return rc;
+        }
+    }
+    a.wt = wt.get(); a.bias = (h_bias && !split) ? bs.get() : nullptr;
+    if (split) {
+        HIP_TRY(ctx, slab.alloc((size_t)ksplit * M * N));
+        a.out = slab.get();
+    }
+    if (d.publish) {
+        a.amax_out = amax_slot(ctx, AMAX_TEST);
+        if (!a.amax_out) return dt_fail(ctx, DT_ERR_STATE, "max-|x| slots not allocated");
+        HIP_TRY(ctx, hipMemsetAsync(a.amax_out, 0, DT_AMAX_WORDS * sizeof(unsigned), ctx->stream));
+    }
+    rc = launch_conv_igemm(ctx->stream, a, ks, order, epi, d.cfg);
+    if (rc) return dt_fail(ctx, launch_code(rc), "dt_conv_igemm: launch failed (rc=%d)", rc);
+    if (split && launch_splitk_reduce(ctx->stream, slab.get(), ksplit, M, N, h_bias ? bs.get() : nullptr, d.slope, d_out, d.out_ld))
+        return dt_fail(ctx, DT_ERR_DEVICE, "dt_conv_igemm: split-K reduce launch failed");
+    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+    return DT_OK;
+}
+
 // Re-reads the tuning / test knobs from the environment into the context (they are otherwise read in dt_create and by the
 // layer-level test entry points); the context's pin override stays.  Knobs that shape the uploaded weights (DT_WINO, DT_WINO_TILE)
 // take effect at the next weight load.

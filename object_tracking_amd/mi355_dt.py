@@ -61,12 +61,18 @@ SYMBOLS = [
     "dt_hota_align", "dt_hota_weights", "dt_hota_count",
     "dt_associate_tracks_assign", "dt_associate_stream_tracks_assign",
     "dt_wino_geometry", "dt_wino_input", "dt_wino_output",
+    "dt_conv_igemm",
 ]
 # dt_wino_input / dt_wino_output (include/mi355_dt.h): what h_geom holds, and the codes of the kernel forms the launchers report
 DT_WINO_GEOM_INTS = 10
 WINO_GEOM_KEYS = ("g", "ph", "pw", "th", "tw", "Mt", "Mp", "form", "grid", "threads")
 WIN_FORMS = {"tpi2": 1, "tpi4": 2, "tpi6": 3, "tpi4_s3": 4, "coop6": 5, "s3_6": 6, "s3_4": 7, "h2_6": 8, "h2_4": 9}
 WOUT_FORMS = {"tpi6": 1, "tpi4": 2, "tpi2": 3, "coop6": 4, "gates6": 5, "gates4": 6, "gates2": 7}
+# dt_conv_igemm (include/mi355_dt.h): the kinds it takes, the tile configurations it takes and reports, and what h_info holds
+DT_CONV_INFO_INTS = 8
+CONV_INFO_KEYS = ("cfg", "BM", "BN", "threads", "persistent", "grid_x", "grid_y", "total")
+CONV_KINDS = {"plain": 0, "pool": 1, "pool_both": 2, "s2d": 3, "gates": 4, "partial": 5}
+CONV_CFGS = {"128x128": 0, "128x64": 1, "256x128": 2, "256x256": 3, "64x128": 4}
 
 _lib = None
 
@@ -81,6 +87,13 @@ class FrameDesc(ctypes.Structure):
                 ("height", ctypes.c_int32), ("width", ctypes.c_int32),
                 ("pitch0", ctypes.c_int32), ("pitch1", ctypes.c_int32),
                 ("format", ctypes.c_int32), ("reserved", ctypes.c_int32)]
+
+
+class ConvIgemmDesc(ctypes.Structure):
+    """dt_conv_igemm_desc (include/mi355_dt.h)"""
+    _fields_ = [(n, ctypes.c_int32) for n in ("ks", "B", "H", "W", "Cin", "N", "P", "in_ld")] + [("in_bs", ctypes.c_int64)] + \
+               [(n, ctypes.c_int32) for n in ("npad", "kind", "cfg", "ksplit", "act", "publish", "wg_cap")] + [("slope", ctypes.c_float)] + \
+               [(n, ctypes.c_int32) for n in ("out_ld", "out2_ld", "xp_ld", "c_ld")]
 
 
 class FrameView(ctypes.Structure):
@@ -179,6 +192,7 @@ def load_library():
     L.dt_wino_geometry.argtypes = [vp, ci, ci, ci, ci, ci, geom]
     L.dt_wino_input.argtypes = [vp, vp, ci, ci, ci, ci, ci, cll, ci, ci, ci, ci, ci, vp, cll, geom]
     L.dt_wino_output.argtypes = [vp, vp, cll, ci, ci, ci, ci, ci, ci, vp, vp, cf, vp, ci, vp, ci, ci, vp, ci, vp, ci, ci, ci, geom]
+    L.dt_conv_igemm.argtypes = [vp, ctypes.POINTER(ConvIgemmDesc), vp, vp, vp, vp, vp, vp, vp, vp, geom]
     L.dt_profile_enable.argtypes = [vp, ci]
     L.dt_graph_enable.argtypes = [vp, ci]
     L.dt_profile_reset.argtypes = [vp]
@@ -1346,6 +1360,39 @@ class Context(object):
                                             float(slope), _dptr(out), lds["out"], _dptr(out2), lds["out2"], int(bool(publish)), _dptr(xproj), lds["xproj"],
                                             _dptr(cstate), lds["cstate"], int(force_form), int(wg_cap), g), "dt_wino_output")
         return self._wino_geom(g)
+
+    # ---- the fp32 implicit-GEMM kernel alone (csrc/conv_igemm.hip) -----
+    def conv_igemm(self, x, out, ks, kernel=None, bias=None, wt=None, kind="plain", cfg="128x128", slope=1.0, act=0, ksplit=0, npad=0, out2=None,
+                   xproj=None, cstate=None, publish=False, wg_cap=0):
+        """conv_igemm.hip through its production launcher on caller views (dt_conv_igemm).  Layer mode: x [B,H,W,Cin] (pixel stride >= Cin,
+        any frame stride), kernel numpy HWIO [ks,ks,Cin,N], bias numpy [N] or None.  Batched GEMM: x [P,Mt,K] and wt [P,N,K] dense device
+        tensors.  out / out2 / xproj / cstate are 2-D row views [rows, columns] with unit column stride; their row stride is the ld ([P,Mt,N]
+        with dense problems for the batched GEMM).  Returns what ran: cfg, BM, BN, threads, persistent, grid_x, grid_y, total."""
+        t = self.torch
+        d = ConvIgemmDesc()
+        if wt is not None:
+            assert x.is_cuda and x.is_contiguous() and wt.is_cuda and wt.is_contiguous() and x.dim() == 3 and wt.dim() == 3 and x.dtype == wt.dtype == t.float32
+            assert out.dim() == 3 and out.stride(2) == 1 and out.stride(0) == out.shape[1] * out.stride(1)
+            d.P, (d.B, d.H, d.W), d.Cin, d.N = x.shape[0], (1, 1, x.shape[1]), x.shape[2], wt.shape[1]
+            d.in_ld, d.in_bs, d.out_ld = d.Cin, d.W * d.Cin, out.stride(1)
+        else:
+            d.in_ld, d.in_bs = self._nhwc_view(x, "x")
+            d.P, (d.B, d.H, d.W, d.Cin), d.N = 1, x.shape, kernel.shape[3]
+            assert out.dim() == 2 and out.stride(1) == 1
+            d.out_ld = out.stride(0)
+        for name, a in (("out2_ld", out2), ("xp_ld", xproj), ("c_ld", cstate)):
+            if a is not None:
+                assert a.is_cuda and a.dtype == t.float32 and a.dim() == 2 and a.stride(1) == 1, name
+                setattr(d, name, a.stride(0))
+        d.ks, d.npad, d.kind, d.cfg = int(ks), int(npad), CONV_KINDS.get(kind, kind), CONV_CFGS.get(cfg, cfg)
+        d.ksplit, d.act, d.publish, d.wg_cap, d.slope = int(ksplit), int(act), int(bool(publish)), int(wg_cap), float(slope)
+        kk, kp = _hptr(kernel) if kernel is not None else (None, None)
+        bb, bp = _hptr(bias) if bias is not None else (None, None)
+        info = (ctypes.c_int * DT_CONV_INFO_INTS)()
+        self._sync_stream()
+        self._check(self.lib.dt_conv_igemm(self.h, ctypes.byref(d), _dptr(x), kp, bp, _dptr(wt), _dptr(out), _dptr(out2), _dptr(xproj), _dptr(cstate), info),
+                    "dt_conv_igemm")
+        return dict(zip(CONV_INFO_KEYS, [int(v) for v in info]))
 
     # ---- profiling ------------------------------------------------------
     def profile_enable(self, on=True):
