@@ -79,6 +79,7 @@ DT_API int dt_set_stream(dt_ctx *ctx, void *hip_stream);
  * and the two track assignment entries dt_associate_tracks_assign, dt_associate_stream_tracks_assign
  * and the three Winograd transform test entries dt_wino_geometry, dt_wino_input, dt_wino_output
  * and the one implicit-GEMM kernel test entry dt_conv_igemm
+ * and the two track score entries dt_associate_tracks_scored, dt_associate_stream_tracks_scored
  * -- additions only, the number stayed; 1.07: 1.06 + dt_gemm_split, dt_policy_set) */
 DT_API int dt_abi_version(void);
 
@@ -393,6 +394,44 @@ DT_API int dt_associate_tracks_match(dt_ctx *ctx, const float *d_boxes, const in
 DT_API int dt_associate_tracks_assign(dt_ctx *ctx, const float *d_boxes, const int *d_counts,
                  int n_clips, int T, int cap, float assoc_threshold, int max_age, int tcap, float gain, int min_hits, int match,
                  int *d_ids, int *d_nids, int *d_gaps, int *d_hits, float *d_tracks, int *d_tinfo, int *d_tcounts);
+/* Track scores (BUILD-DEFINED, DESIGN.md "Track scores"): dt_associate_tracks_assign in two passes that use the detection score beside
+ * each box -- the BYTE rule (Zhang et al., ECCV 2022): confident boxes are matched first, the weak ones are offered only to the tracks
+ * still unmatched, and a weak box no track wants is thrown away instead of opening a track.  Everything not named here is
+ * dt_associate_tracks_assign's, bit for bit: arguments, outputs, prediction, velocity update, hits, gaps, rebuild order, capacity cut
+ * and read-out.  match is 0 or DT_MATCH_ANY_LABEL.
+ * A frame has n boxes, the table nt entries, and s_i = float score_at of box i (0..7; dt_decode writes conf at 4 and score at 6).
+ * Classes: box i is HIGH when s_i >= score_high as float32, else LOW; a NaN score is LOW.
+ * Pass 1: the candidates are dt_associate_tracks_assign's, restricted to HIGH boxes: W1[n][nt] is its weight matrix with every LOW row
+ * zero, and the pairs are the row_to_col of dt_assign_max on W1 with rows = n and cols = nt -- the full shape, so that the solver's
+ * orientation and tie rules do not depend on how many boxes are HIGH.
+ * Pass 2 (skipped when max_age_low = -1): the candidates are the pairs of a LOW box i and an entry j that was not claimed in pass 1, with
+ * age_j <= min(max_age, max_age_low), labels equal unless DT_MATCH_ANY_LABEL is set, and bbox_iou(box i, predicted box of j) >=
+ * assoc_threshold_low as float32.  A candidate weighs 1 + (int)(iou * 1048576.0f), everything else 0, on the full [n][nt] shape; the
+ * pairs are dt_assign_max's as in pass 1.  max_age_low = 0 is BYTE's own rule: a weak box only continues a track that had a box in the
+ * previous frame.
+ * After the passes a box that claimed an entry in either pass inherits exactly as in dt_associate_tracks_assign: id, gap, hits + 1 and
+ * the velocity update.  An unclaimed box with s_i >= score_new opens an id, in decode order, at rest, with hits 1.  Every other unclaimed
+ * box is DROPPED: d_ids = -1, d_gaps = -1, d_hits = 0 (in unused entries d_hits stays -1).
+ * The table: a dropped box still takes its row among the frame's leading rows -- a DEAD row with id -1, hits 0, age 0 and velocity 0; its
+ * box and label are stored.  So the table keeps its order: the leading rows are the frame's boxes in decode order, and an age-0 row's
+ * `box` index is its table index.  A dead row is never a candidate of any association entry, is never confirmed or read out, and never
+ * survives the next rebuild.  It DOES count in the capacity cut of the one frame that made it: with tcap close to the number of boxes
+ * plus lost tracks, dropped boxes can push the last lost tracks out of the table.
+ * Equivalences: if every box's score is >= both score_high and score_new, every output and the slot are dt_associate_tracks_assign's, bit
+ * for bit.  With max_age_low = -1 and score_new = score_high the HIGH boxes get the ids, gaps and hits that dt_associate_tracks_assign
+ * gives on the same frames with the LOW boxes removed and the rest moved up, as long as no capacity cut drops an entry in either run.
+ * Boxes and scores must be finite otherwise: non-finite ones give unspecified ids, but the call still terminates and stays in bounds.
+ * Not done here: a Kalman filter, a cost that weighs the score into the IoU, a separate rule for unconfirmed tracks (BYTE's third
+ * step), scored variants of the decode-order and best-first policies.
+ * DT_ERR_ARG, with nothing launched and nothing written: everything dt_associate_tracks_assign refuses, score_at outside 0..7, a NaN
+ * score_high, score_new or assoc_threshold_low, max_age_low < -1, and a table that does not fit the 160 KB of LDS: the general form
+ * holds one more word per box (its score), so 26 * tcap + 5 * cap + 6 words must not exceed 40960.  A table with tcap <= 64 and T <= 64
+ * runs in registers, fetches the score as one more scalar per box and refills the one weight tile for pass 2: 260 * cap + 512 bytes, as
+ * dt_associate_tracks_assign. */
+DT_API int dt_associate_tracks_scored(dt_ctx *ctx, const float *d_boxes, const int *d_counts,
+                 int n_clips, int T, int cap, float assoc_threshold, int max_age, int tcap, float gain, int min_hits, int match,
+                 int score_at, float score_high, float score_new, float assoc_threshold_low, int max_age_low,
+                 int *d_ids, int *d_nids, int *d_gaps, int *d_hits, float *d_tracks, int *d_tinfo, int *d_tcounts);
 
 /* Track scoring (BUILD-DEFINED, DESIGN.md "Track scoring"): the CLEAR-MOT frame step (Bernardin & Stiefelhagen 2008) of a tracker's output
  * against ground-truth tracks, with the optimal assignment replaced by this library's best-IoU-first order.  Clips are scored
@@ -670,6 +709,18 @@ DT_API int dt_associate_stream_tracks_match(dt_ctx *ctx, const float *d_boxes, c
 DT_API int dt_associate_stream_tracks_assign(dt_ctx *ctx, const float *d_boxes, const int *d_counts, int n, int T, int cap,
                         float thr, int max_age, float gain, int min_hits, int match, const int *h_slots, int *d_ids, int *d_nids,
                         int *d_gaps, int *d_hits, float *d_tracks, int *d_tinfo, int *d_tcounts);
+/* dt_associate_tracks_scored for streams: dt_associate_stream_tracks_assign with the two passes by score as the match of every frame.
+ * The slot layout is dt_associate_stream_tracks'; chunks of any sizes give what dt_associate_tracks_scored gives on the concatenation
+ * with tcap = the table's.  After a call the slot's leading rows may hold DEAD rows (id -1, hits 0: the last frame's dropped boxes).
+ * Calls of any association entry may still follow each other on one slot: every entry's candidate test asks for an id >= 0, so a dead
+ * row is matched by none of them and leaves the table at the end of the next call's first frame.  Errors as
+ * dt_associate_stream_tracks_assign, and DT_ERR_ARG for score_at outside 0..7, a NaN score_high, score_new or thr_low, max_age_low < -1
+ * or a table beyond 26 * tcap + 5 * cap + 6 <= 40960 words (refused before the slot list is written); an error leaves the slots as
+ * they were. */
+DT_API int dt_associate_stream_tracks_scored(dt_ctx *ctx, const float *d_boxes, const int *d_counts, int n, int T, int cap,
+                        float thr, int max_age, float gain, int min_hits, int match,
+                        int score_at, float score_high, float score_new, float thr_low, int max_age_low,
+                        const int *h_slots, int *d_ids, int *d_nids, int *d_gaps, int *d_hits, float *d_tracks, int *d_tinfo, int *d_tcounts);
 
 /* ---- cross-stream detection exchange (multi-GPU; the reference has no counterpart) ---- *
  * north_star: "RCCL all-gather of detections over xGMI only for cross-stream association".  Each rank packs its

@@ -8,6 +8,7 @@
 // arithmetic op for op (tests/track_*_ref.py), which rounds after every multiply and add, so no fused multiply-add may be
 // formed here.
 #include "dt_internal.h"
+#include <type_traits>
 
 // ---------------------------------------------------------------------------
 // Track identity (BUILD-DEFINED -- the reference has no association step and
@@ -261,6 +262,14 @@ int launch_associate_stream(hipStream_t st, const float *boxes, const int *count
 // dt_assign_max's method, orientation and tie rule (identity.hip:assign_max_kernel), step for step.  What the boxes inherit and the
 // ids the others open are the best-first block's code behind the match.
 //
+// ASSOC_MATCH_SCORED (dt_associate_tracks_scored, beside ASSOC_MATCH_ASSIGN only; DESIGN.md "Track scores"): the assignment block runs
+// twice per frame on masked weights.  Pass 0: the boxes whose score (float sc.at) is >= sc.high against the table, the assignment's own
+// candidates.  Pass 1 (none with max_age_low = -1): the other boxes against the entries pass 0 left unclaimed, no older than
+// min(max_age, max_age_low), at thr_low.  Both on the full [n][nt] shape, so orientation and tie rule are the assignment's.  An unclaimed
+// box opens an id only with a score >= sc.fresh; any other is DROPPED (id -1, gap -1, hits 0) and leaves a DEAD row in the rebuilt table
+// -- id -1, hits 0, age 0, at rest -- so that the leading rows stay the frame's boxes in decode order.  A dead row fails every candidate
+// test (id >= 0, which also means "unclaimed"), is never confirmed (min_hits >= 1) and fails the survivor test at the next rebuild.
+//
 // One wavefront per clip, two forms like associate_kernel, chosen from tcap and T alone.
 // ---------------------------------------------------------------------------
 __device__ __forceinline__ void track_row_store(float *tracks, int *tinfo, long long row, float x, float y, float w, float h, float l,
@@ -282,13 +291,24 @@ __device__ __forceinline__ int assign_weight(float iou) { return 1 + __float2int
 template <bool STREAM, int LEVEL, int MATCH>
 __global__ __launch_bounds__(64) void associate_table_kernel(const float *boxes, const int *counts, int T, int cap, float thr,
                                                              int max_age, int tcap, float gain, int min_hits, int *ids, int *nids,
-                                                             int *gaps, TrackReadout out, AssocCarry carry)
+                                                             int *gaps, TrackReadout out, AssocCarry carry,
+                                                             std::conditional_t<(MATCH & ASSOC_MATCH_SCORED) != 0, AssocScore, AssocNoScore> sc)
 {
     static_assert(LEVEL >= ASSOC_MEMORY && LEVEL <= ASSOC_TRACKS && (MATCH == 0 || LEVEL == ASSOC_TRACKS), "the match policies belong to the tracks level");
     constexpr bool VEL = LEVEL >= ASSOC_MOTION, HITS = LEVEL >= ASSOC_TRACKS;
     constexpr bool BEST = (MATCH & DT_MATCH_BEST_FIRST) != 0, ANY = (MATCH & DT_MATCH_ANY_LABEL) != 0;
     constexpr bool OPT = (MATCH & ASSOC_MATCH_ASSIGN) != 0;      // the optimal assignment; the launcher's bit, not a DT_MATCH_* one
+    constexpr bool SCORED = (MATCH & ASSOC_MATCH_SCORED) != 0;   // the assignment in two passes by detection score; the launcher's bit too
     static_assert(!(BEST && OPT), "an assignment has no order");
+    static_assert(!SCORED || OPT, "the scored passes are passes of the assignment");
+    // the passes of a frame's assignment and what the second one matches at (SCORED only; every other instance has one pass and none of this)
+    [[maybe_unused]] int n_pass = 1, low_age = 0;
+    [[maybe_unused]] float low_thr = 0.0f;
+    if constexpr (SCORED) {
+        n_pass = sc.max_age_low < 0 ? 1 : 2;
+        low_age = min(max_age, sc.max_age_low);
+        low_thr = sc.thr_low;
+    }
     constexpr int W = 7 + 2 * VEL + HITS;      // LDS words per entry of the general form: 5 box fields, id, age | vx, vy at 7, 8 | hits at 9
     extern __shared__ __attribute__((aligned(16))) float smem[];
     const int clip = blockIdx.x, lane = threadIdx.x;
@@ -356,11 +376,13 @@ __global__ __launch_bounds__(64) void associate_table_kernel(const float *boxes,
     // top of iteration t, in front of these stores, so the wait for them at the top of t + 1 does not wait for the read-out.
     if (tcap <= 64 && T <= 64) {
         const int cnt_l = lane < T ? min(cnt[lane], cap) : 0;
+        [[maybe_unused]] float ns = 0.0f;               // SCORED: the score of the requested frame's box, fetched beside its label
         auto request = [&](int t, float4 &q, float &ql) {
             const int n = __builtin_amdgcn_readlane(cnt_l, t);
             const float *src = bx + ((long long)t * cap + (lane < n ? lane : 0)) * DT_BOX_FLOATS;
             q = *reinterpret_cast<const float4 *>(src);
             ql = src[5];
+            if constexpr (SCORED) ns = src[sc.at];
         };
         float4 nq; float nl;
         request(0, nq, nl);
@@ -386,6 +408,7 @@ __global__ __launch_bounds__(64) void associate_table_kernel(const float *boxes,
         for (int t = 0; t < T; ++t) {
             const int n = __builtin_amdgcn_readlane(cnt_l, t);
             const float cx = nq.x, cy = nq.y, cw = nq.z, ch = nq.w, cl = nl;        // waits for frame t's boxes
+            [[maybe_unused]] const float cs = ns;
             if (t + 1 < T) request(t + 1, nq, nl);
             if (t > 0 && lane < cap) {
                 id[(t - 1) * cap + lane] = outv;
@@ -417,14 +440,23 @@ __global__ __launch_bounds__(64) void associate_table_kernel(const float *boxes,
                 tid0 = tid; cent = -1;
                 volatile int *wm = reinterpret_cast<volatile int *>(smem);
                 volatile int *pent = wm + ASSIGN_TILE_STRIDE * cap, *pclm = pent + 64;   // the pairs: per box its entry, per entry whether claimed
-                const bool live = lane < nt && tid >= 0 && tage <= max_age;
+                // SCORED: two passes over the one tile and the one solve.  Pass 0 weighs the HIGH boxes' rows (a NaN score is LOW) and leaves
+                // the LOW rows zero; pass 1 weighs the LOW rows against the entries still live -- the claims of pass 0 have set tid = -1 --
+                // and no older than low_age, at low_thr.  Both solve the full [n][nt] shape; the pairs of pass 0 stay in pent / pclm.
+                [[maybe_unused]] unsigned long long hi = 0ull;
+                if constexpr (SCORED) hi = __ballot(lane < n && cs >= sc.high);
+                [[maybe_unused]] int pass = 0;
+                do {
+                const bool live = lane < nt && tid >= 0 && tage <= (SCORED && pass ? low_age : max_age);
+                const float pthr = SCORED && pass ? low_thr : thr;
+                [[maybe_unused]] const unsigned long long rows = SCORED && pass ? ~hi : hi;
                 for (int i = 0; i < n; ++i) {
                     const float ax = readlane_f(cx, i), ay = readlane_f(cy, i), aw = readlane_f(cw, i), ah = readlane_f(ch, i);
                     const float al = readlane_f(cl, i);
                     const float iou = bbox_iou_ref(ax, ay, aw, ah, qx, qy, tbw, tbh);
-                    wm[i * ASSIGN_TILE_STRIDE + lane] = (live && (ANY || tbl == al) && iou >= thr) ? assign_weight(iou) : 0;
+                    wm[i * ASSIGN_TILE_STRIDE + lane] = (live && (!SCORED || ((rows >> i) & 1ull)) && (ANY || tbl == al) && iou >= pthr) ? assign_weight(iou) : 0;
                 }
-                pent[lane] = -1; pclm[lane] = 0;
+                if (!SCORED || pass == 0) { pent[lane] = -1; pclm[lane] = 0; }
                 __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
                 __builtin_amdgcn_wave_barrier();
                 const bool tr = nt < n;                 // the solve's rows are the entries
@@ -476,7 +508,8 @@ __global__ __launch_bounds__(64) void associate_table_kernel(const float *boxes,
                 __builtin_amdgcn_wave_barrier();
                 cent = pent[lane];
                 if (pclm[lane]) tid = -1;               // claimed
-                __builtin_amdgcn_wave_barrier();        // the next frame's tile stands behind these reads
+                __builtin_amdgcn_wave_barrier();        // the next tile (the second pass's, the next frame's) stands behind these reads
+                } while (SCORED && ++pass < n_pass);
                 } else {
                 // best-IoU-first order: the frame's keys are an [n][64] tile of dynamic LDS, column = lane = entry, and a lane
                 // reads and writes its own column only.  Each lane caches its column's best remaining (key, box), ties to the
@@ -543,7 +576,12 @@ __global__ __launch_bounds__(64) void associate_table_kernel(const float *boxes,
                     }
                 }
                 // the boxes that claimed nothing open ids in decode order, at hits = 1 and at rest
-                const bool fresh = lane < n && cent < 0;
+                bool fresh = lane < n && cent < 0;
+                if constexpr (SCORED) {
+                    // ... those of them with a score >= sc.fresh.  The others are DROPPED: id -1, gap -1, hits 0, at rest, and the rebuild
+                    // below makes of them a dead row, which no candidate test accepts (tid >= 0) and no survivor test keeps
+                    if (fresh && !(cs >= sc.fresh)) { fresh = false; chits = 0; }
+                }
                 const unsigned long long fm = __ballot(fresh);
                 if (fresh) { cid = next_id + __popcll(fm & below); cgap = -1; chits = 1; }
                 next_id += __popcll(fm);
@@ -660,6 +698,8 @@ __global__ __launch_bounds__(64) void associate_table_kernel(const float *boxes,
     volatile unsigned *bkey = reinterpret_cast<volatile unsigned *>(smem + 2 * TS + cap);
     volatile int *bent = reinterpret_cast<volatile int *>(smem + 2 * TS + 2 * cap);
     volatile int *bdone = reinterpret_cast<volatile int *>(smem + 2 * TS + 3 * cap);
+    // SCORED only: the current frame's scores, [cap], behind the assignment's six work arrays
+    [[maybe_unused]] volatile float *bsc = reinterpret_cast<volatile float *>(smem + 2 * TS + 4 * cap + 6 * (tcap + 1));
     // read-out of table A (nt entries, as frame t left it): 64 entries per pass compacted by a running count, the way the survivor
     // pass compacts; then the empty rows behind the count.  Called once the NEXT frame's boxes have been fetched (below), so these
     // stores stand behind those loads and never in front of them.  (HITS only: no other level calls it.)
@@ -712,6 +752,7 @@ __global__ __launch_bounds__(64) void associate_table_kernel(const float *boxes,
             B[j] = q[0]; B[tcap + j] = q[1]; B[2 * tcap + j] = q[2]; B[3 * tcap + j] = q[3]; B[4 * tcap + j] = q[5];
             bage[j] = 0;
             if constexpr (BEST || OPT) bdone[j] = 0;
+            if constexpr (SCORED) bsc[j] = q[sc.at];
         }
         __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
         __builtin_amdgcn_wave_barrier();
@@ -730,12 +771,23 @@ __global__ __launch_bounds__(64) void associate_table_kernel(const float *boxes,
             const int L = tcap + 1;
             volatile unsigned *zu = reinterpret_cast<volatile unsigned *>(smem + 2 * TS + 4 * cap), *zv = zu + L, *zminv = zv + L;
             volatile int *zway = reinterpret_cast<volatile int *>(zminv + L), *zp = zway + L, *zused = zp + L;
+            // SCORED: two passes of the one solve, the six work arrays initialised anew by each.  Pass 0 weighs the HIGH boxes (a NaN score
+            // is LOW), pass 1 the LOW ones against the entries no older than low_age, at low_thr; the entries pass 0 claimed have a
+            // complemented id by then, so `aid[e] >= 0` is "live and unclaimed" in both.  The pairs of pass 0 stay in bent / bdone.
+            [[maybe_unused]] int pass = 0;
+            do {
+            // an id below 0 is a claimed entry or a dead row (one a scored call left in the slot): no candidate of any box
             auto weight_of = [&](int b, int e) -> int {       // box b of the frame, entry e of table A
-                if (!(aage[e] <= max_age && (ANY || A[4 * tcap + e] == B[4 * tcap + b]))) return 0;
+                if constexpr (SCORED) {
+                    if ((bsc[b] >= sc.high) == (pass != 0)) return 0;
+                }
+                const int page = SCORED && pass ? low_age : max_age;
+                const float pthr = SCORED && pass ? low_thr : thr;
+                if (!(aid[e] >= 0 && aage[e] <= page && (ANY || A[4 * tcap + e] == B[4 * tcap + b]))) return 0;
                 const float k = (float)(aage[e] + 1);
                 const float qx = A[e] + k * A[7 * tcap + e], qy = A[tcap + e] + k * A[8 * tcap + e];
                 const float iou = bbox_iou_ref(B[b], B[tcap + b], B[2 * tcap + b], B[3 * tcap + b], qx, qy, A[2 * tcap + e], A[3 * tcap + e]);
-                return iou >= thr ? assign_weight(iou) : 0;
+                return iou >= pthr ? assign_weight(iou) : 0;
             };
             const bool tr = nt < n;                     // the solve's rows are the entries
             const int N = tr ? nt : n, M = tr ? n : nt;
@@ -819,6 +871,7 @@ __global__ __launch_bounds__(64) void associate_table_kernel(const float *boxes,
             }
             __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
             __builtin_amdgcn_wave_barrier();
+            } while (SCORED && ++pass < n_pass);
             } else {
             // best-IoU-first order.  scan(i): box i's best candidate among the unclaimed entries, 64 entries per pass, ties to the
             // lowest entry -- the decode-order match's inner loop -- cached in bkey / bent.  A round: the largest cached key over
@@ -883,11 +936,19 @@ __global__ __launch_bounds__(64) void associate_table_kernel(const float *boxes,
             // a box that claimed an entry inherits from it; the others open ids in decode order, at hits = 1 and at rest
             for (int i0 = 0; i0 < n; i0 += 64) {
                 const int i = i0 + lane;
-                const bool fresh = i < n && !bdone[i];
+                bool fresh = i < n && !bdone[i];
+                [[maybe_unused]] bool drop = false;
+                if constexpr (SCORED) {
+                    // ... those of them with a score >= sc.fresh.  The others are DROPPED and leave a dead row: id -1, hits 0, at rest
+                    drop = fresh && !(bsc[i] >= sc.fresh);
+                    fresh = fresh && !drop;
+                }
                 const unsigned long long fm = __ballot(fresh);
                 if (fresh) {
                     bid[i] = next_id + __popcll(fm & ((1ull << lane) - 1ull));
                     cgap[i] = -1; bhit[i] = 1; B[7 * tcap + i] = 0.0f; B[8 * tcap + i] = 0.0f;
+                } else if (SCORED && drop) {
+                    bid[i] = -1; cgap[i] = -1; bhit[i] = 0; B[7 * tcap + i] = 0.0f; B[8 * tcap + i] = 0.0f;
                 } else if (i < n) {
                     const int bj = bent[i];
                     const int my_gap = aage[bj];
@@ -1005,7 +1066,8 @@ size_t assoc_table_lds_bytes(int level, int T, int cap, int tcap, int match)
         return best ? (size_t)64 * cap * sizeof(unsigned) : 0;                             // the frame's keys, [cap][64]
     }
     const int words = 7 + 2 * (level >= ASSOC_MOTION) + (level >= ASSOC_TRACKS);           // per entry, as the kernel's W
-    return ((size_t)2 * words * tcap + (best || opt ? 4 : 1) * cap                         // + key, entry, claimed per box
+    const bool scored = (match & ASSOC_MATCH_SCORED) != 0;                                 // (the register form above needs no word for it)
+    return ((size_t)2 * words * tcap + ((best || opt ? 4 : 1) + scored) * cap              // + key, entry, claimed per box; scored: + its score
             + (opt ? (size_t)6 * (tcap + 1) : 0)) * sizeof(float);                         // + the solver's u, v, minv, way, p, used
 }
 
@@ -1019,8 +1081,10 @@ static int launch_table_as(hipStream_t st, size_t lds, const AssocTableArgs &a, 
                                        hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) != hipSuccess;
         }))
         return 1;
+    std::conditional_t<(MATCH & ASSOC_MATCH_SCORED) != 0, AssocScore, AssocNoScore> sc{};
+    if constexpr ((MATCH & ASSOC_MATCH_SCORED) != 0) sc = a.score;
     hipLaunchKernelGGL((associate_table_kernel<STREAM, LEVEL, MATCH>), dim3((unsigned)n_clips), dim3(64), lds, st, a.boxes, a.counts, a.T, a.cap,
-                       a.thr, a.max_age, a.tcap, a.gain, a.min_hits, a.ids, a.nids, a.gaps, a.out, a.carry);
+                       a.thr, a.max_age, a.tcap, a.gain, a.min_hits, a.ids, a.nids, a.gaps, a.out, a.carry, sc);
     return hipGetLastError() == hipSuccess ? 0 : 1;
 }
 
@@ -1033,6 +1097,11 @@ int launch_associate_table(hipStream_t st, const AssocTableArgs &a, int n_clips)
     if (a.level >= ASSOC_MOTION && !(a.gain >= 0.0f && a.gain <= 1.0f)) return 2;      // (NaN fails both comparisons)
     if (a.level < ASSOC_TRACKS ? a.match != 0 : (a.match < 0 || a.match > (DT_MATCH_BEST_FIRST | DT_MATCH_ANY_LABEL))) return 2;
     if (a.assign && (a.level != ASSOC_TRACKS || (a.match & DT_MATCH_BEST_FIRST))) return 2;
+    if (a.scored) {
+        const AssocScore &s = a.score;
+        if (!a.assign || s.at < 0 || s.at >= DT_BOX_FLOATS || s.max_age_low < -1) return 2;
+        if (s.high != s.high || s.fresh != s.fresh || s.thr_low != s.thr_low) return 2;      // a NaN
+    }
     const int match = assoc_kernel_match(a);
     if (a.level == ASSOC_TRACKS) {
         const TrackReadout &o = a.out;
@@ -1048,8 +1117,8 @@ int launch_associate_table(hipStream_t st, const AssocTableArgs &a, int n_clips)
     if (lds > 160 * 1024) return 2;
     if (n_clips <= 0) return 0;
 #define DT_TABLE_LAUNCH(L, M) \
-    case (L) * 8 + (M): return stream ? launch_table_as<true, L, M>(st, lds, a, n_clips) : launch_table_as<false, L, M>(st, lds, a, n_clips);
-    switch (a.level * 8 + match) {
+    case (L) * 16 + (M): return stream ? launch_table_as<true, L, M>(st, lds, a, n_clips) : launch_table_as<false, L, M>(st, lds, a, n_clips);
+    switch (a.level * 16 + match) {
         DT_TABLE_LAUNCH(ASSOC_MEMORY, 0)
         DT_TABLE_LAUNCH(ASSOC_MOTION, 0)
         DT_TABLE_LAUNCH(ASSOC_TRACKS, 0)
@@ -1058,6 +1127,8 @@ int launch_associate_table(hipStream_t st, const AssocTableArgs &a, int n_clips)
         DT_TABLE_LAUNCH(ASSOC_TRACKS, 3)
         DT_TABLE_LAUNCH(ASSOC_TRACKS, ASSOC_MATCH_ASSIGN)
         DT_TABLE_LAUNCH(ASSOC_TRACKS, ASSOC_MATCH_ASSIGN | DT_MATCH_ANY_LABEL)
+        DT_TABLE_LAUNCH(ASSOC_TRACKS, ASSOC_MATCH_SCORED | ASSOC_MATCH_ASSIGN)
+        DT_TABLE_LAUNCH(ASSOC_TRACKS, ASSOC_MATCH_SCORED | ASSOC_MATCH_ASSIGN | DT_MATCH_ANY_LABEL)
     }
 #undef DT_TABLE_LAUNCH
     return 2;

@@ -386,6 +386,16 @@ struct TrackReadout {   // ASSOC_TRACKS only; tracks / tinfo / tcounts: all thre
     int *tinfo;         // [n_clips][T][tcap][DT_TRACK_INTS]
     int *tcounts;       // [n_clips][T]
 };
+// The scored two-pass match (dt_associate_tracks_scored; DESIGN.md "Track scores"): a box is HIGH when its float `at` is >= high.  Pass 1
+// assigns the HIGH boxes as dt_associate_tracks_assign does, pass 2 the LOW boxes to the entries still unclaimed with age <= min(max_age,
+// max_age_low) at thr_low (max_age_low = -1: no pass 2); an unclaimed box opens an id only with a score >= fresh and is dropped otherwise.
+struct AssocScore {
+    int at;             // 0..7: the float of a box that holds its score
+    float high, fresh;
+    float thr_low;
+    int max_age_low;    // >= -1
+};
+struct AssocNoScore {}; // what the kernel's instances without ASSOC_MATCH_SCORED get in its place
 struct AssocTableArgs {
     const float *boxes; // [n_clips][T][cap][DT_BOX_FLOATS]
     const int *counts;  // [n_clips][T]
@@ -404,22 +414,26 @@ struct AssocTableArgs {
     int level;         // ASSOC_MEMORY .. ASSOC_TRACKS
     int match;          // the track match policy, DT_MATCH_* bits (0 = decode order within a label); non-zero at ASSOC_TRACKS only
     bool assign;        // the optimal assignment (dt_associate_tracks_assign): ASSOC_TRACKS only, match 0 or DT_MATCH_ANY_LABEL
+    bool scored;        // the two passes by detection score (dt_associate_tracks_scored): with `assign` only
+    AssocScore score;   // read when `scored`
 };
 // The kernel's MATCH template value: the call's DT_MATCH_* bits and, for the assignment entries, ASSOC_MATCH_ASSIGN -- a bit of the
 // launcher's own, never accepted from a public `match` argument (the match entries refuse 4 as they always did).
 #define ASSOC_MATCH_ASSIGN 4
-inline int assoc_kernel_match(const AssocTableArgs &a) { return a.match | (a.assign ? ASSOC_MATCH_ASSIGN : 0); }
+#define ASSOC_MATCH_SCORED 8      // the scored entries' two passes around the assignment: another launcher's bit, beside ASSOC_MATCH_ASSIGN only
+inline int assoc_kernel_match(const AssocTableArgs &a) { return a.match | (a.assign ? ASSOC_MATCH_ASSIGN : 0) | (a.scored ? ASSOC_MATCH_SCORED : 0); }
 #define ASSIGN_TILE_STRIDE 65     // words per row of the register form's weight tile: odd, so a column's 64 words fall in 64 banks
 #define ASSIGN_INF 0x7fffffff     // assign_max_kernel's and the assignment match's "no reduced cost yet"
 // dynamic LDS the launch needs: none in the register form (tcap <= 64, T <= 64) but the best-IoU-first order's keys [cap][64] or the
 // assignment's weights [cap][65] and 128 words of pairs; in the general form two tables of 7 / 9 / 10 words per entry, the frame's
-// gaps, three more words per box for the best-IoU-first order and the assignment, and the assignment's 6 * (tcap + 1) solver words.
+// gaps, three more words per box for the best-IoU-first order and the assignment, and the assignment's 6 * (tcap + 1) solver words; the
+// scored passes add one word per box (its score) to the general form and nothing to the register form.
 // match: the kernel's MATCH value (assoc_kernel_match)
 size_t assoc_table_lds_bytes(int level, int T, int cap, int tcap, int match);
 // 0: launched (or, n_clips <= 0, nothing to launch); 1: device error; 2: argument error, nothing launched -- T or cap < 1, tcap < cap or
 // beyond the meta word's 16 bits, max_age < 0, a table beyond 160 KB of LDS, carry.tcap != tcap, a stream launch without the level's
 // slot arrays; from ASSOC_MOTION on a gain outside [0, 1] or NaN; at ASSOC_TRACKS min_hits < 1, a partial read-out triple, match outside 0..3, assign below
-// ASSOC_TRACKS or with DT_MATCH_BEST_FIRST
+// ASSOC_TRACKS or with DT_MATCH_BEST_FIRST, scored without assign or with score.at outside 0..7, a NaN score.high / fresh / thr_low, max_age_low < -1
 int launch_associate_table(hipStream_t st, const AssocTableArgs &a, int n_clips);
 
 __device__ __forceinline__ float readlane_f(float v, int l) { return __int_as_float(__builtin_amdgcn_readlane(__float_as_int(v), l)); }

@@ -1828,7 +1828,7 @@ extern "C" int dt_bbox_iou(dt_ctx *ctx, const float *d_pairs, int n, float *d_io
     return DT_OK;
 }
 
-// ---- track identity: the twelve dt_associate* entries (DESIGN.md "Track identity") ---------------------------------------------------
+// ---- track identity: the fourteen dt_associate* entries (DESIGN.md "Track identity") ---------------------------------------------------
 // One path.  A request is the launch's own argument struct: level = ASSOC_FRAME (associate_kernel, the previous-frame rule) or a level
 // of the table kernel.  An entry fills what its level has; associate_entry adds tcap and the carry of a stream call.
 static AssocTableArgs assoc_args(int level, const float *d_boxes, const int *d_counts, int T, int cap, float thr, int *d_ids, int *d_nids)
@@ -1851,6 +1851,12 @@ static const char *assoc_params_refusal(const AssocTableArgs &a, bool stream)
     if (given != 0 && given != 3) return "d_tracks, d_tinfo and d_tcounts are given all three or none";
     if (a.assign && a.match != 0 && a.match != DT_MATCH_ANY_LABEL) return "match must be 0 or DT_MATCH_ANY_LABEL: an order means nothing to an assignment";
     if (a.match < 0 || a.match > (DT_MATCH_BEST_FIRST | DT_MATCH_ANY_LABEL)) return "match must be a combination of DT_MATCH_BEST_FIRST and DT_MATCH_ANY_LABEL";
+    if (a.scored) {
+        if (a.score.at < 0 || a.score.at >= DT_BOX_FLOATS) return "score_at must be in 0..7";
+        if (a.score.high != a.score.high || a.score.fresh != a.score.fresh) return "score_high and score_new must not be NaN";
+        if (a.score.thr_low != a.score.thr_low) return "the low association threshold must not be NaN";
+        if (a.score.max_age_low < -1) return "max_age_low must be at least -1 (-1: no second pass)";
+    }
     return nullptr;
 }
 
@@ -1881,7 +1887,7 @@ static int associate_entry(dt_ctx *ctx, AssocTableArgs a, int n, bool stream, co
         if (a.level >= ASSOC_MEMORY && assoc_table_lds_bytes(a.level, a.T, a.cap, a.tcap, assoc_kernel_match(a)) > 160 * 1024)
             return dt_fail(ctx, DT_ERR_ARG, "a track table of %d entries%s%s does not fit the LDS", a.tcap,
                            a.level == ASSOC_MOTION ? " with velocities" : a.level == ASSOC_TRACKS ? " with velocities and hit counts" : "",
-                           a.assign ? " and the assignment's words per box and per entry" : (a.match & DT_MATCH_BEST_FIRST) ? " and the best-first order's words per box" : "");
+                           a.scored ? " and the scored assignment's words per box and per entry" : a.assign ? " and the assignment's words per box and per entry" : (a.match & DT_MATCH_BEST_FIRST) ? " and the best-first order's words per box" : "");
         if (launch_stream_slots(ctx->stream, h_slots, n, S.list.get(), nullptr)) return dt_fail(ctx, DT_ERR_DEVICE, "slot list launch failed");
         a.carry = assoc_carry(S, a.level);
     }
@@ -1890,10 +1896,12 @@ static int associate_entry(dt_ctx *ctx, AssocTableArgs a, int n, bool stream, co
     const char *tag = level_tag[stream][a.level];
     if (a.match) tag = stream ? "stream_tracks_match" : "tracks_match";
     if (a.assign) tag = stream ? "stream_tracks_assign" : "tracks_assign";
+    if (a.scored) tag = stream ? "stream_tracks_scored" : "tracks_scored";
     ProfScope ps(ctx, "associate", 0.0, 4.0 * n * (box_bytes + row_bytes), tag);
     int rc;
     if (!stream && a.assign && assoc_table_lds_bytes(a.level, a.T, a.cap, a.tcap, assoc_kernel_match(a)) > 160 * 1024)
-        return dt_fail(ctx, DT_ERR_ARG, "tcap: a track table of %d entries with the assignment's words per box and per entry does not fit the LDS", a.tcap);
+        return dt_fail(ctx, DT_ERR_ARG, "tcap: a track table of %d entries with the %sassignment's words per box and per entry does not fit the LDS", a.tcap,
+                       a.scored ? "scored " : "");
     if (a.level != ASSOC_FRAME) rc = launch_associate_table(ctx->stream, a, n);
     else if (stream) rc = launch_associate_stream(ctx->stream, a.boxes, a.counts, n, a.T, a.cap, a.thr, a.ids, a.nids, a.carry);
     else rc = launch_associate(ctx->stream, a.boxes, a.counts, n, a.T, a.cap, a.thr, a.ids, a.nids);
@@ -1951,10 +1959,11 @@ extern "C" int dt_associate_stream_motion(dt_ctx *ctx, const float *d_boxes, con
 // itself.  The policy leaves no trace in a slot: calls with different `match` may follow each other on one slot.
 static int associate_tracks(dt_ctx *ctx, bool stream, const int *h_slots, const float *d_boxes, const int *d_counts, int n, int T, int cap, float thr,
                             int max_age, int tcap, float gain, int min_hits, int match, int *d_ids, int *d_nids, int *d_gaps, const TrackReadout &out,
-                            bool assign = false)
+                            bool assign = false, const AssocScore *score = nullptr)
 {
     AssocTableArgs a = assoc_args(ASSOC_TRACKS, d_boxes, d_counts, T, cap, thr, d_ids, d_nids);
     a.max_age = max_age; a.tcap = tcap; a.gain = gain; a.min_hits = min_hits; a.match = match; a.gaps = d_gaps; a.out = out; a.assign = assign;
+    if (score) { a.scored = true; a.score = *score; }
     return associate_entry(ctx, a, n, stream, h_slots);
 }
 
@@ -2007,6 +2016,27 @@ extern "C" int dt_associate_stream_tracks_assign(dt_ctx *ctx, const float *d_box
 {
     return associate_tracks(ctx, true, h_slots, d_boxes, d_counts, n, T, cap, assoc_threshold, max_age, 0, gain, min_hits, match, d_ids, d_nids, d_gaps,
                             TrackReadout{d_hits, d_tracks, d_tinfo, d_tcounts}, true);
+}
+
+// the assignment entries in two passes by detection score (DESIGN.md "Track scores"); match: 0 or DT_MATCH_ANY_LABEL
+extern "C" int dt_associate_tracks_scored(dt_ctx *ctx, const float *d_boxes, const int *d_counts, int n_clips, int T, int cap,
+                                          float assoc_threshold, int max_age, int tcap, float gain, int min_hits, int match, int score_at,
+                                          float score_high, float score_new, float assoc_threshold_low, int max_age_low, int *d_ids,
+                                          int *d_nids, int *d_gaps, int *d_hits, float *d_tracks, int *d_tinfo, int *d_tcounts)
+{
+    const AssocScore score{score_at, score_high, score_new, assoc_threshold_low, max_age_low};
+    return associate_tracks(ctx, false, nullptr, d_boxes, d_counts, n_clips, T, cap, assoc_threshold, max_age, tcap, gain, min_hits, match, d_ids, d_nids,
+                            d_gaps, TrackReadout{d_hits, d_tracks, d_tinfo, d_tcounts}, true, &score);
+}
+
+extern "C" int dt_associate_stream_tracks_scored(dt_ctx *ctx, const float *d_boxes, const int *d_counts, int n, int T, int cap, float thr,
+                                                 int max_age, float gain, int min_hits, int match, int score_at, float score_high,
+                                                 float score_new, float thr_low, int max_age_low, const int *h_slots, int *d_ids, int *d_nids,
+                                                 int *d_gaps, int *d_hits, float *d_tracks, int *d_tinfo, int *d_tcounts)
+{
+    const AssocScore score{score_at, score_high, score_new, thr_low, max_age_low};
+    return associate_tracks(ctx, true, h_slots, d_boxes, d_counts, n, T, cap, thr, max_age, 0, gain, min_hits, match, d_ids, d_nids, d_gaps,
+                            TrackReadout{d_hits, d_tracks, d_tinfo, d_tcounts}, true, &score);
 }
 
 // track scoring (DESIGN.md "Track scoring"): CLEAR-MOT counts of hypotheses against ground-truth tracks; the caller owns the state

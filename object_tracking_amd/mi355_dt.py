@@ -62,6 +62,7 @@ SYMBOLS = [
     "dt_associate_tracks_assign", "dt_associate_stream_tracks_assign",
     "dt_wino_geometry", "dt_wino_input", "dt_wino_output",
     "dt_conv_igemm",
+    "dt_associate_tracks_scored", "dt_associate_stream_tracks_scored",
 ]
 # dt_wino_input / dt_wino_output (include/mi355_dt.h): what h_geom holds, and the codes of the kernel forms the launchers report
 DT_WINO_GEOM_INTS = 10
@@ -154,6 +155,9 @@ def load_library():
     L.dt_associate_stream_tracks_match.argtypes = [vp, vp, vp, ci, ci, ci, cf, ci, cf, ci, ci, ctypes.POINTER(ci), vp, vp, vp, vp, vp, vp, vp]
     L.dt_associate_tracks_assign.argtypes = L.dt_associate_tracks_match.argtypes
     L.dt_associate_stream_tracks_assign.argtypes = L.dt_associate_stream_tracks_match.argtypes
+    L.dt_associate_tracks_scored.argtypes = [vp, vp, vp, ci, ci, ci, cf, ci, ci, cf, ci, ci, ci, cf, cf, cf, ci, vp, vp, vp, vp, vp, vp, vp]
+    L.dt_associate_stream_tracks_scored.argtypes = [vp, vp, vp, ci, ci, ci, cf, ci, cf, ci, ci, ci, cf, cf, cf, ci, ctypes.POINTER(ci), vp, vp, vp, vp, vp,
+                                                    vp, vp]
     L.dt_track_score.argtypes = [vp, vp, vp, vp, ci, vp, vp, vp, ci, ci, ci, ci, ci, cf, ci, ci, vp, vp, vp, vp, vp, vp]
     L.dt_identity_overlap.argtypes = [vp, vp, vp, vp, ci, vp, vp, vp, ci, ci, ci, ci, ci, cf, ci, ci, ci, vp, vp, vp, vp]
     L.dt_assign_max.argtypes = [vp, vp, ci, ci, vp, ci, ci, ci, ci, vp, vp, vp]
@@ -616,6 +620,28 @@ class Context(object):
                     "dt_associate_tracks")
         return r
 
+    def associate_tracks_scored(self, boxes, counts, assoc_threshold, max_age, gain, min_hits, score_high, score_new=None,
+                                assoc_threshold_low=None, max_age_low=0, score_at=6, track_cap=None, match=0, readout=True):
+        """associate_tracks(..., assign=True) in two passes by detection score (dt_associate_tracks_scored; DESIGN.md "Track scores"): the
+        boxes whose float score_at is >= score_high are assigned first; the others are offered to the tracks still unmatched, no older
+        than min(max_age, max_age_low), at assoc_threshold_low (max_age_low = -1: not at all); an unmatched box opens an id only with a
+        score >= score_new and is dropped otherwise: ids -1, gaps -1, hits 0.  score_new None: score_high; assoc_threshold_low None:
+        assoc_threshold.  match: 0 or DT_MATCH_ANY_LABEL.  The dict of associate_tracks."""
+        t = self.torch
+        assert boxes.is_cuda and boxes.is_contiguous() and counts.is_contiguous() and counts.dtype == t.int32
+        n_clips, T, cap, _ = boxes.shape
+        tcap = cap if track_cap is None else int(track_cap)
+        r = self._tracks_outputs(n_clips, T, cap, max(tcap, 0), readout)
+        self._sync_stream()
+        self._check(self.lib.dt_associate_tracks_scored(self.h, _dptr(boxes), _dptr(counts), n_clips, T, cap, float(assoc_threshold), int(max_age),
+                                                        tcap, float(gain), int(min_hits), int(match), int(score_at), float(score_high),
+                                                        float(score_high if score_new is None else score_new),
+                                                        float(assoc_threshold if assoc_threshold_low is None else assoc_threshold_low),
+                                                        int(max_age_low), _dptr(r["ids"]), _dptr(r["nids"]), _dptr(r["gaps"]), _dptr(r["hits"]),
+                                                        _dptr(r.get("tracks")), _dptr(r.get("track_info")), _dptr(r.get("track_counts"))),
+                    "dt_associate_tracks_scored")
+        return r
+
     def track_score(self, gt_boxes, gt_counts, gt_ids, hyp_boxes, hyp_counts, hyp_ids, iou_threshold=0.5, any_label=False, obj_cap=None,
                     state=None, per_box=True):
         """CLEAR-MOT counts of a tracker's output against ground-truth tracks (dt_track_score; the rule: DESIGN.md "Track scoring").
@@ -1074,6 +1100,29 @@ class Context(object):
                                                         float(gain), int(min_hits), arr, _dptr(r["ids"]), _dptr(r["nids"]), _dptr(r["gaps"]),
                                                         _dptr(r["hits"]), _dptr(r.get("tracks")), _dptr(r.get("track_info")),
                                                         _dptr(r.get("track_counts"))), "dt_associate_stream_tracks")
+        return r
+
+    def associate_stream_tracks_scored(self, boxes, counts, assoc_threshold, slots, max_age, gain, min_hits, score_high, score_new=None,
+                                       assoc_threshold_low=None, max_age_low=0, score_at=6, match=0, readout=True):
+        """associate_tracks_scored for streams (dt_associate_stream_tracks_scored): associate_stream_tracks(..., assign=True) with the two
+        passes by score.  The slot may be shared with every other association entry: the rows a call leaves for its last frame's dropped
+        boxes are matched by none of them."""
+        t = self.torch
+        assert boxes.is_cuda and boxes.is_contiguous() and counts.is_contiguous() and counts.dtype == t.int32
+        n, T, cap, _ = boxes.shape
+        ns, arr = self._slot_array(slots)
+        if ns != n:
+            raise NativeError("dt_associate_stream_tracks_scored failed (1): %d slots for %d streams" % (ns, n))
+        r = self._tracks_outputs(n, T, cap, getattr(self, "_stream_tcap", None) or cap, readout)
+        self._sync_stream()
+        self._check(self.lib.dt_associate_stream_tracks_scored(self.h, _dptr(boxes), _dptr(counts), n, T, cap, float(assoc_threshold), int(max_age),
+                                                               float(gain), int(min_hits), int(match), int(score_at), float(score_high),
+                                                               float(score_high if score_new is None else score_new),
+                                                               float(assoc_threshold if assoc_threshold_low is None else assoc_threshold_low),
+                                                               int(max_age_low), arr, _dptr(r["ids"]), _dptr(r["nids"]), _dptr(r["gaps"]),
+                                                               _dptr(r["hits"]), _dptr(r.get("tracks")),
+                                                               _dptr(r.get("track_info")), _dptr(r.get("track_counts"))),
+                    "dt_associate_stream_tracks_scored")
         return r
 
     def track_row_width(self):

@@ -148,6 +148,17 @@ class MultiObjDetTracker(object):
     # IoU, the Hungarian step of the SORT family) instead of a greedy pass; MATCH_ANY_LABEL still applies, MATCH_BEST_FIRST beside it is
     # refused by the library.  The result carries `gaps` and `hits` as with a MATCH_* policy
     MATCH_OPTIMAL = False
+    # build-defined track scores: None = off.  A number = the two-pass match of BYTE on the decoded boxes' scores
+    # (mi355_dt.Context.associate_tracks_scored; the optimal assignment is implied, MATCH_BEST_FIRST is refused): boxes with float SCORE_AT
+    # (6: the class score, 4: the objectness) >= SCORE_HIGH are matched first, the weaker ones only continue a track still unmatched and no
+    # older than MAX_AGE_LOW frames (at ASSOC_THRESHOLD_LOW; None: ASSOC_THRESHOLD), and a box that matches nothing opens a track only
+    # with a score >= SCORE_NEW (None: SCORE_HIGH) -- otherwise it is dropped: ids -1, hits 0.  Meant to go with a low OBJ_THRESHOLD.
+    # MATCH_ANY_LABEL, MIN_HITS, MOTION_GAIN, TRACK_CAP and INGEST_FIT apply as they do without it; the result carries `gaps` and `hits`
+    SCORE_HIGH = None
+    SCORE_NEW = None
+    ASSOC_THRESHOLD_LOW = None
+    MAX_AGE_LOW = 0
+    SCORE_AT = 6
     # build-defined frame ingest: track_stream on lists of device frames exchanges channels 0 and 2 while ingesting
     INGEST_SWAP_RB = False
     # build-defined frame views: None = lists of frames are stretched (dt_ingest_frames).  "letterbox" / "stretch" = they
@@ -214,6 +225,11 @@ class MultiObjDetTracker(object):
     def _match_policy(self):
         return (mi355_dt.DT_MATCH_BEST_FIRST if self.MATCH_BEST_FIRST else 0) | (mi355_dt.DT_MATCH_ANY_LABEL if self.MATCH_ANY_LABEL else 0)
 
+    def _score_args(self):
+        """the keyword arguments of the scored association entries (SCORE_HIGH set)"""
+        return dict(score_high=self.SCORE_HIGH, score_new=self.SCORE_NEW, assoc_threshold_low=self.ASSOC_THRESHOLD_LOW,
+                    max_age_low=self.MAX_AGE_LOW, score_at=self.SCORE_AT, match=self._match_policy(), readout=self.MIN_HITS is not None)
+
     def train(self):
         raise NotImplementedError("training (custom_loss_*, fit_generator) is outside the MI355X hot path this "
                                   "build covers (SURVEY.md C7/C8); only inference entry points are implemented")
@@ -226,7 +242,7 @@ class MultiObjDetTracker(object):
           counts [n_clips,T]        boxes per frame
           ids    [n_clips,T,cap]    track ids (-1 in unused slots), per clip from 0
           nids   [n_clips]          ids opened per clip
-          gaps   [n_clips,T,cap]    only with MAX_AGE > 0, a MOTION_GAIN, MIN_HITS or a MATCH_* policy (MATCH_OPTIMAL included): frames the box's track had missed (0 unbroken, -1 new id / unused)
+          gaps   [n_clips,T,cap]    only with MAX_AGE > 0, a MOTION_GAIN, MIN_HITS or a MATCH_* policy (MATCH_OPTIMAL and SCORE_HIGH included): frames the box's track had missed (0 unbroken, -1 new id / unused)
         and only with MIN_HITS (the track read-out, mi355_dt.Context.associate_tracks):
           hits   [n_clips,T,cap]    frames in which the box's track has had a box (also with a MATCH_* policy alone)
           tracks [n_clips,T,tcap,8], track_info [n_clips,T,tcap,4], track_counts [n_clips,T]   the confirmed tracks of every frame
@@ -279,6 +295,10 @@ class MultiObjDetTracker(object):
         """the association entry the class attributes select, on a call's boxes: the result dict without `netout`"""
         ctx = self.model.ctx
         match = self._match_policy()
+        if self.SCORE_HIGH is not None:
+            a = ctx.associate_stream_tracks_scored(boxes, counts, self.ASSOC_THRESHOLD, slots, self.MAX_AGE,
+                                                   0.0 if self.MOTION_GAIN is None else self.MOTION_GAIN, self.MIN_HITS or 1, **self._score_args())
+            return dict(a, boxes=boxes, counts=counts)
         if self.MIN_HITS is not None or match or self.MATCH_OPTIMAL:
             a = ctx.associate_stream_tracks(boxes, counts, self.ASSOC_THRESHOLD, slots, self.MAX_AGE,
                                             0.0 if self.MOTION_GAIN is None else self.MOTION_GAIN, self.MIN_HITS or 1, match=match,
@@ -323,6 +343,10 @@ class MultiObjDetTracker(object):
         boxes = r["boxes"].reshape(n_clips, T, cap, mi355_dt.DT_BOX_FLOATS)
         counts = r["counts"].reshape(n_clips, T)
         match = self._match_policy()
+        if self.SCORE_HIGH is not None:
+            a = ctx.associate_tracks_scored(boxes, counts, self.ASSOC_THRESHOLD, self.MAX_AGE, 0.0 if self.MOTION_GAIN is None else self.MOTION_GAIN,
+                                            self.MIN_HITS or 1, track_cap=self.TRACK_CAP, **self._score_args())
+            return dict(a, boxes=boxes, counts=counts, netout=trk)
         if self.MIN_HITS is not None or match or self.MATCH_OPTIMAL:
             a = ctx.associate_tracks(boxes, counts, self.ASSOC_THRESHOLD, self.MAX_AGE, 0.0 if self.MOTION_GAIN is None else self.MOTION_GAIN,
                                      self.MIN_HITS or 1, track_cap=self.TRACK_CAP, match=match, readout=self.MIN_HITS is not None,
@@ -348,7 +372,7 @@ class MultiObjDetTracker(object):
         z = lambda shape, dt: torch.zeros(shape, dtype=dt, device=ctx.device)
         res = dict(boxes=z((0, T, cap, mi355_dt.DT_BOX_FLOATS), torch.float32), counts=z((0, T), torch.int32),
                    ids=z((0, T, cap), torch.int32), nids=z((0,), torch.int32), netout=None)
-        if self.MIN_HITS is None and (self._match_policy() or self.MATCH_OPTIMAL):
+        if self.MIN_HITS is None and (self._match_policy() or self.MATCH_OPTIMAL or self.SCORE_HIGH is not None):
             res.update(gaps=z((0, T, cap), torch.int32), hits=z((0, T, cap), torch.int32))
         if self.MIN_HITS is not None:
             tcap = cap if self.TRACK_CAP is None else self.TRACK_CAP
