@@ -80,6 +80,7 @@ DT_API int dt_set_stream(dt_ctx *ctx, void *hip_stream);
  * and the three Winograd transform test entries dt_wino_geometry, dt_wino_input, dt_wino_output
  * and the one implicit-GEMM kernel test entry dt_conv_igemm
  * and the two track score entries dt_associate_tracks_scored, dt_associate_stream_tracks_scored
+ * and the one conv_1 kernel test entry dt_conv1
  * -- additions only, the number stayed; 1.07: 1.06 + dt_gemm_split, dt_policy_set) */
 DT_API int dt_abi_version(void);
 
@@ -919,6 +920,22 @@ typedef struct dt_conv_igemm_desc {
 } dt_conv_igemm_desc;
 DT_API int dt_conv_igemm(dt_ctx *ctx, const dt_conv_igemm_desc *desc, const float *d_in, const float *h_kernel, const float *h_bias, const float *d_wt,
                          float *d_out, float *d_out2, const float *d_xproj, float *d_cstate, int *h_info);
+
+/* conv_1's direct kernels ALONE (csrc/conv1.hip: x/255, Conv2D(32,(3,3),'same') on RGB, bias, LeakyReLU, 2x2 max) through the production
+ * launcher, with no detector configured (tests/test_gpu_conv1_edges.py).
+ *   d_frames [B][H][W][3], DT_FRAMES_U8 (ANY byte address) or DT_FRAMES_F32 (already normalised; 4-byte aligned); H and W even, B in 1..65535;
+ *   h_w [27][32], row k = 9 ky + 3 kx + ci, the BatchNorm scale already folded in; h_bias [32]; slope >= 0: LeakyReLU slope (1 = linear);
+ *   split: 1 = the two three-term bf16 tables are built from h_w exactly as dt_load_darknet_weights builds them and passed (the split kernels;
+ *     uint8 frames with W % 4 != 0 or at an unaligned address fall back to the fp32 MFMA kernel), 0 = null tables (the fp32 MFMA kernel);
+ *   tpw: the launcher's test-only force_tpw -- 0 = its own rule for the tiles a workgroup walks along x, 1..26 = walk that many;
+ *   publish != 0: max |x| of the stored values into max-|x| slot 57, zeroed first (dt_amax_read; the fp32 MFMA kernel publishes nothing: 0);
+ *   d_out [B][H/2][W/2][32].
+ * h_info[DT_CONV1_INFO_INTS] receives the launcher's plan: the instance (DT_C1_*), tpw, grid x, y, z, and 1 if the instance fills the slot.
+ * DT_ERR_ARG with a message, and no launch, for what the launcher refuses: odd H or W, B <= 0 or > 65535, slope < 0, tpw outside 0..26. */
+#define DT_CONV1_INFO_INTS 6
+enum { DT_C1_MFMA_F32 = 0, DT_C1_S3_U8_FULL, DT_C1_S3_U8, DT_C1_S3_F32 };
+DT_API int dt_conv1(dt_ctx *ctx, const void *d_frames, int frames_dtype, int B, int H, int W, const float *h_w, const float *h_bias, float slope,
+                    int split, int tpw, int publish, float *d_out, int *h_info);
 
 /* ---- tuning / test knobs ------------------------------------------------- *
  * The DT_* environment variables of DESIGN.md's appendix are read in dt_create (no launch path calls getenv);

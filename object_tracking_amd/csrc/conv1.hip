@@ -387,20 +387,16 @@ void conv1_split_tables(const float *w_in /*[27][32]*/, bool scale255, unsigned 
             }
 }
 
-// does launch_conv1_direct take the kernel that fills `amax_out` for these arguments?
-bool conv1_direct_fills_amax(const void *frames, int dtype, int W, const unsigned *w3, const unsigned *w3u8)
+// What launch_conv1_direct does with a call (the one place that decides it; dt_internal.h: Conv1Plan).  split: both three-term tables were passed
+// (Policy::s3_conv1).  force_tpw: test only, 0 in production = the rule below; 1..C1_TPW = walk that many tiles per workgroup.
+Conv1Plan plan_conv1(const void *frames, int dtype, int B, int H, int W, float slope, bool split, int force_tpw)
 {
-    return w3 && w3u8 && (dtype != DT_FRAMES_U8 || (W % 4 == 0 && (reinterpret_cast<uintptr_t>(frames) & 3) == 0));
-}
-int launch_conv1_direct(hipStream_t st, const void *frames, int dtype, int B, int H, int W, const float *w_packed,
-                        const float *bias, const float *lut, float slope, float *out, const unsigned *w3, const unsigned *w3u8, unsigned *amax_out)
-{
-    if ((H & 1) || (W & 1) || B <= 0) return 2;
-    Conv1Args a;
-    a.amax_out = amax_out;
-    a.frames = frames; a.dtype = dtype; a.B = B; a.H = H; a.W = W;
-    a.w = w_packed; a.bias = bias; a.lut = lut; a.slope = slope; a.out = out;
-    a.w3 = w3; a.w3u8 = w3u8;
+    Conv1Plan pl{};
+    pl.rc = 2;
+    if ((dtype != DT_FRAMES_U8 && dtype != DT_FRAMES_F32) || H <= 0 || W <= 0 || (H & 1) || (W & 1) || B <= 0) return pl;
+    if (B > 65535) return pl;                         // the grid's z limit
+    if (!(slope >= 0.0f)) return pl;                  // conv1_s3_kernel takes the 2x2 max BEFORE the activation: LeakyReLU must be non-decreasing
+    if (force_tpw < 0 || force_tpw > C1_TPW) return pl;
     const int H2 = H / 2, W2 = W / 2;
     // whole rows per workgroup when there are thousands of rows (the walk hides each tile's load latency); with a few
     // frames per call shorter walks keep every CU busy
@@ -408,14 +404,37 @@ int launch_conv1_direct(hipStream_t st, const void *frames, int dtype, int B, in
     const int ntx = (W2 + 7) / 8;
     int tpw = C1_TPW;
     while (tpw > 1 && rows * ((ntx + tpw - 1) / tpw) < 2048) tpw = (tpw + 1) / 2;
-    a.tpw = tpw;
-    const dim3 grid((unsigned)((ntx + tpw - 1) / tpw), (unsigned)((H2 + 7) / 8), (unsigned)B);
-    if (w3 && w3u8 && (dtype != DT_FRAMES_U8 || (W % 4 == 0 && (reinterpret_cast<uintptr_t>(frames) & 3) == 0))) {      // split-bf16 form (Policy::s3_conv1); uint8: the kernel reads aligned dwords of the rows -- a view at an odd byte offset takes the fp32 MFMA kernel
-        const bool full = H % 16 == 0 && W % 16 == 0;
-        if (dtype == DT_FRAMES_U8 && full) hipLaunchKernelGGL((conv1_s3_kernel<true, true>), grid, dim3(256), 0, st, a);
-        else if (dtype == DT_FRAMES_U8) hipLaunchKernelGGL((conv1_s3_kernel<true, false>), grid, dim3(256), 0, st, a);
-        else hipLaunchKernelGGL((conv1_s3_kernel<false, false>), grid, dim3(256), 0, st, a);
-    } else
-        hipLaunchKernelGGL(conv1_mfma_kernel, grid, dim3(256), 0, st, a);
+    if (force_tpw) tpw = force_tpw;
+    pl.tpw = tpw;
+    pl.grid_x = (ntx + tpw - 1) / tpw; pl.grid_y = (H2 + 7) / 8; pl.grid_z = B;
+    // split-bf16 form (Policy::s3_conv1); uint8: the kernel reads aligned dwords of the rows -- W % 4 != 0 or a view at an odd byte offset takes the
+    // fp32 MFMA kernel
+    if (split && (dtype != DT_FRAMES_U8 || (W % 4 == 0 && (reinterpret_cast<uintptr_t>(frames) & 3) == 0)))
+        pl.inst = dtype != DT_FRAMES_U8 ? C1_S3_F32 : (H % 16 == 0 && W % 16 == 0) ? C1_S3_U8_FULL : C1_S3_U8;
+    else
+        pl.inst = C1_MFMA_F32;
+    pl.fills_amax = pl.inst != C1_MFMA_F32;           // conv1_mfma_kernel has no max-|x| epilogue
+    pl.rc = 0;
+    return pl;
+}
+int launch_conv1_direct(hipStream_t st, const void *frames, int dtype, int B, int H, int W, const float *w_packed,
+                        const float *bias, const float *lut, float slope, float *out, const unsigned *w3, const unsigned *w3u8, unsigned *amax_out,
+                        int force_tpw)
+{
+    const Conv1Plan pl = plan_conv1(frames, dtype, B, H, W, slope, w3 && w3u8, force_tpw);
+    if (pl.rc) return pl.rc;
+    Conv1Args a;
+    a.amax_out = amax_out;
+    a.frames = frames; a.dtype = dtype; a.B = B; a.H = H; a.W = W;
+    a.w = w_packed; a.bias = bias; a.lut = lut; a.slope = slope; a.out = out;
+    a.w3 = w3; a.w3u8 = w3u8;
+    a.tpw = pl.tpw;
+    const dim3 grid((unsigned)pl.grid_x, (unsigned)pl.grid_y, (unsigned)pl.grid_z);
+    switch (pl.inst) {
+    case C1_S3_U8_FULL: hipLaunchKernelGGL((conv1_s3_kernel<true, true>), grid, dim3(256), 0, st, a); break;
+    case C1_S3_U8: hipLaunchKernelGGL((conv1_s3_kernel<true, false>), grid, dim3(256), 0, st, a); break;
+    case C1_S3_F32: hipLaunchKernelGGL((conv1_s3_kernel<false, false>), grid, dim3(256), 0, st, a); break;
+    default: hipLaunchKernelGGL(conv1_mfma_kernel, grid, dim3(256), 0, st, a); break;
+    }
     return hipGetLastError() == hipSuccess ? 0 : 1;
 }

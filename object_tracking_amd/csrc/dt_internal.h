@@ -332,12 +332,21 @@ void wino_pack_weights(int ts, const float *hwio, int cin_src, int cout_src, con
 // ---------------------------------------------------------------------------
 // other kernels
 // ---------------------------------------------------------------------------
+// What launch_conv1_direct does with a call (plan_conv1, conv1.hip): rc 0 = launches, 2 = refuses the arguments (odd or non-positive H / W, B outside
+// 1..65535, a negative slope, an unknown dtype); which of the four kernel instances runs, the tiles a workgroup walks along x, the grid, and whether
+// the instance fills `amax_out`.  The codes are mi355_dt.h's DT_C1_* (dt_conv1 reports them).
+enum { C1_MFMA_F32 = 0, C1_S3_U8_FULL = 1, C1_S3_U8 = 2, C1_S3_F32 = 3 };
+struct Conv1Plan {
+    int rc, inst, tpw, grid_x, grid_y, grid_z, fills_amax;
+};
+Conv1Plan plan_conv1(const void *frames, int dtype, int B, int H, int W, float slope, bool split /*both three-term tables are passed*/,
+                     int force_tpw /*test only: 0 = the launcher's rule*/);
 int launch_conv1_direct(hipStream_t st, const void *frames, int dtype, int B, int H, int W,
                         const float *w_packed /*[27][32]*/, const float *bias /*[32]*/,
                         const float *lut /*[256] or null*/, float slope, float *out /*[B,H/2,W/2,32]*/,
                         const unsigned *w3 = nullptr /*[2][3][64][4]*/, const unsigned *w3u8 = nullptr /*weights / 255: both set -> conv1_s3_kernel*/,
-                        unsigned *amax_out = nullptr /*conv1_s3_kernel: max |x| of the outputs into this slot*/);
-bool conv1_direct_fills_amax(const void *frames, int dtype, int W, const unsigned *w3, const unsigned *w3u8);
+                        unsigned *amax_out = nullptr /*conv1_s3_kernel: max |x| of the outputs into this slot*/,
+                        int force_tpw = 0 /*test only (dt_conv1), 0 in production*/);
 #define C1_W3_WORDS 1540      // 1536 table words + 16 bytes of zeros: where conv1_s3_kernel points the loads of out-of-image pixels
 void conv1_split_tables(const float *w /*[27][32]*/, bool scale255, unsigned *w3 /*[1536 of C1_W3_WORDS]*/);
 

@@ -755,6 +755,18 @@ static int build_merged_xproj(dt_ctx *ctx)
     return upload(ctx, ctx->trk_bx16, b16);
 }
 
+// conv_1's weights [27][32] (BatchNorm scale folded) as three bf16 terms, plain (float32 frames) and with normalize()'s 1/255 folded in (uint8
+// frames): conv1_s3_kernel's tables, each 1536 words + 4 zero words (the kernel's source of padding pixels).  dt_load_darknet_weights and dt_conv1.
+static int upload_conv1_tables(dt_ctx *ctx, const float *w, DevMem<unsigned> &d_w3, DevMem<unsigned> &d_w3u8)
+{
+    std::vector<unsigned> w3(C1_W3_WORDS, 0u), w3u8(C1_W3_WORDS, 0u);
+    conv1_split_tables(w, false, w3.data());
+    conv1_split_tables(w, true, w3u8.data());
+    int rc;
+    if ((rc = upload(ctx, d_w3, w3)) || (rc = upload(ctx, d_w3u8, w3u8))) return rc;
+    return DT_OK;
+}
+
 extern "C" int dt_load_darknet_weights(dt_ctx *ctx, const float *h_blob, size_t n_floats, size_t *consumed)
 {
     if (!ctx || !h_blob) return DT_ERR_ARG;
@@ -786,14 +798,10 @@ extern "C" int dt_load_darknet_weights(dt_ctx *ctx, const float *h_blob, size_t 
             std::vector<float> w(27 * 32);
             for (int t = 0; t < 27; ++t)
                 for (int c = 0; c < 32; ++c) w[t * 32 + c] = hwio[(size_t)t * 32 + c] * scale[c];
-            // the same weights as three bf16 terms, plain (float32 frames) and with normalize()'s 1/255 folded in (uint8 frames): conv1_s3_kernel
-            std::vector<unsigned> w3(C1_W3_WORDS, 0u), w3u8(C1_W3_WORDS, 0u);   // 1536 table words + 4 zero words (the kernel's source of padding pixels)
-            conv1_split_tables(w.data(), false, w3.data());
-            conv1_split_tables(w.data(), true, w3u8.data());
             (void)hipStreamSynchronize(ctx->stream);      // queued work may still read the tables these replace
             int rc;
-            if ((rc = upload(ctx, ctx->conv1_w, w)) || (rc = upload(ctx, ctx->conv1_b, shift)) || (rc = upload(ctx, ctx->conv1_w3, w3)) ||
-                (rc = upload(ctx, ctx->conv1_w3u8, w3u8)))
+            if ((rc = upload(ctx, ctx->conv1_w, w)) || (rc = upload(ctx, ctx->conv1_b, shift)) ||
+                (rc = upload_conv1_tables(ctx, w.data(), ctx->conv1_w3, ctx->conv1_w3u8)))
                 return rc;
             ctx->conv1_hwio32.assign((size_t)9 * 32 * 32, 0.0f);   // [3][3][32 (3 used)][32]
             for (int t = 0; t < 9; ++t)
@@ -1458,15 +1466,20 @@ static int detect_internal(dt_ctx *ctx, const void *frames, int dtype, int B, De
         const bool c1s3 = ctx->pol.s3 != 0 && ctx->pol.s3_conv1 != 0;
         const double c1_bytes = (double)B * H * W * 3.0 * (dtype == DT_FRAMES_U8 ? 1 : 4) + 4.0 * B * (H / 2) * (W / 2) * 32.0;
         // EXECUTED MFMA FLOPs: K = 27 padded to 32 (bf16: 3 partial products per multiply for uint8 frames, 6 for float32 frames) or to 28 (fp32 MFMA)
-        const double c1_exec = c1s3 ? (dtype == DT_FRAMES_U8 ? 3.0 : 6.0) * 2.0 * B * H * W * 32.0 * 32.0 : 2.0 * B * H * W * 28.0 * 32.0;
-        ProfScope ps(ctx, "conv1_direct", c1_exec, c1_bytes, c1s3 ? "bf16" : "f32");
+        // what the launcher will do with this call: the policy asks for the split form, the launcher may still take the fp32 MFMA kernel (uint8
+        // frames at an unaligned address) -- the tag and the executed FLOPs are those of the instance that runs
+        const Conv1Plan c1p = plan_conv1(frames, dtype, B, H, W, LEAKY, c1s3 && ctx->conv1_w3.get() && ctx->conv1_w3u8.get(), 0);
+        if (c1p.rc) return dt_fail(ctx, DT_ERR_ARG, "conv_1: the launcher refuses B=%d H=%d W=%d (even H and W, at most 65535 frames a call)", B, H, W);
+        const bool c1bf = c1p.inst != C1_MFMA_F32;
+        const double c1_exec = c1bf ? (c1p.inst == C1_S3_F32 ? 6.0 : 3.0) * 2.0 * B * H * W * 32.0 * 32.0 : 2.0 * B * H * W * 28.0 * 32.0;
+        ProfScope ps(ctx, "conv1_direct", c1_exec, c1_bytes, c1bf ? "bf16" : "f32");
         prof_direct_form(ctx, 2.0 * B * H * W * 27.0 * 32.0, c1_bytes, DF_CONV1);
         amax_forget(ctx, bufA, (long long)per_frame * B);
         if (int rcz = amax_begin(ctx)) return rcz;
         // (its epilogue takes max |x| of what it writes: conv_2's direct fp16-form kernel scales its input by it)
         // (conv_1 publishes only where conv_2 will read it: the direct fp16-form kernel -- run_trunk's launch of conv_2, asked for ahead of time)
         const bool c2_direct = choose_conv(ctx, ctx->layers[2], bufA, ctx->layers[2].cin, B, H / 2, W / 2, bufB, ORD_QUAD, EPI_POOL, false).form == CF_DIRECT_H2;
-        unsigned *am1 = c1s3 && h2_wanted(ctx) && c2_direct && conv1_direct_fills_amax(frames, dtype, W, ctx->conv1_w3.get(), ctx->conv1_w3u8.get()) ? amax_slot(ctx, 1) : nullptr;
+        unsigned *am1 = c1s3 && h2_wanted(ctx) && c2_direct && c1p.fills_amax ? amax_slot(ctx, 1) : nullptr;
         if (launch_conv1_direct(ctx->stream, frames, dtype, B, H, W, ctx->conv1_w.get(), ctx->conv1_b.get(), ctx->lut255.get(), LEAKY,
                                 bufA, c1s3 ? ctx->conv1_w3.get() : nullptr, c1s3 ? ctx->conv1_w3u8.get() : nullptr, am1))
             return dt_fail(ctx, DT_ERR_DEVICE, "conv_1 launch failed");
@@ -3216,6 +3229,43 @@ extern "C" int dt_conv_igemm(dt_ctx *ctx, const dt_conv_igemm_desc *desc, const 
     if (rc) return dt_fail(ctx, launch_code(rc), "dt_conv_igemm: launch failed (rc=%d)", rc);
     if (split && launch_splitk_reduce(ctx->stream, slab.get(), ksplit, M, N, h_bias ? bs.get() : nullptr, d.slope, d_out, d.out_ld))
         return dt_fail(ctx, DT_ERR_DEVICE, "dt_conv_igemm: split-K reduce launch failed");
+    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+    return DT_OK;
+}
+
+// conv1.hip ALONE (tests/test_gpu_conv1_edges.py): the production split tables (upload_conv1_tables), the context's x/255 table and the production
+// launcher, with no detector configured and no policy.  h_info = what plan_conv1, the function the launcher itself dispatches on, resolved.
+static_assert(DT_C1_MFMA_F32 == C1_MFMA_F32 && DT_C1_S3_U8_FULL == C1_S3_U8_FULL && DT_C1_S3_U8 == C1_S3_U8 && DT_C1_S3_F32 == C1_S3_F32,
+              "the instance codes dt_conv1 reports (mi355_dt.h)");
+extern "C" int dt_conv1(dt_ctx *ctx, const void *d_frames, int frames_dtype, int B, int H, int W, const float *h_w, const float *h_bias, float slope,
+                        int split, int tpw, int publish, float *d_out, int *h_info)
+{
+    if (!ctx || !d_frames || !h_w || !h_bias || !d_out || !h_info) return dt_fail(ctx, DT_ERR_ARG, "null argument");
+    call_begin(ctx, 0);
+    memset(h_info, 0, DT_CONV1_INFO_INTS * sizeof(int));
+    if (frames_dtype == DT_FRAMES_F32 && (reinterpret_cast<uintptr_t>(d_frames) & 3))
+        return dt_fail(ctx, DT_ERR_ARG, "dt_conv1: float32 frames at an address that is no multiple of 4");
+    const Conv1Plan pl = plan_conv1(d_frames, frames_dtype, B, H, W, slope, split != 0, tpw);
+    if (pl.rc)
+        return dt_fail(ctx, DT_ERR_ARG, "dt_conv1: the launcher refuses dtype=%d B=%d H=%d W=%d slope=%g tpw=%d (uint8 or float32 frames, even H and W, "
+                                        "B in 1..65535, slope >= 0, tpw in 0..26)", frames_dtype, B, H, W, (double)slope, tpw);
+    const int info[DT_CONV1_INFO_INTS] = {pl.inst, pl.tpw, pl.grid_x, pl.grid_y, pl.grid_z, pl.fills_amax};
+    memcpy(h_info, info, sizeof(info));
+    DevMem<float> w, bs;
+    DevMem<unsigned> w3, w3u8;
+    SyncAtExit idle{ctx->stream};
+    int rc;
+    if ((rc = upload(ctx, w, std::vector<float>(h_w, h_w + 27 * 32))) || (rc = upload(ctx, bs, std::vector<float>(h_bias, h_bias + 32)))) return rc;
+    if (split && (rc = upload_conv1_tables(ctx, h_w, w3, w3u8))) return rc;
+    unsigned *am = nullptr;
+    if (publish) {
+        am = amax_slot(ctx, AMAX_TEST);
+        if (!am) return dt_fail(ctx, DT_ERR_STATE, "max-|x| slots not allocated");
+        HIP_TRY(ctx, hipMemsetAsync(am, 0, DT_AMAX_WORDS * sizeof(unsigned), ctx->stream));
+    }
+    rc = launch_conv1_direct(ctx->stream, d_frames, frames_dtype, B, H, W, w.get(), bs.get(), ctx->lut255.get(), slope, d_out, split ? w3.get() : nullptr,
+                             split ? w3u8.get() : nullptr, am, tpw);
+    if (rc) return dt_fail(ctx, launch_code(rc), "dt_conv1: launch failed (rc=%d)", rc);
     HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
     return DT_OK;
 }

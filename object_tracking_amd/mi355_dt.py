@@ -63,6 +63,7 @@ SYMBOLS = [
     "dt_wino_geometry", "dt_wino_input", "dt_wino_output",
     "dt_conv_igemm",
     "dt_associate_tracks_scored", "dt_associate_stream_tracks_scored",
+    "dt_conv1",
 ]
 # dt_wino_input / dt_wino_output (include/mi355_dt.h): what h_geom holds, and the codes of the kernel forms the launchers report
 DT_WINO_GEOM_INTS = 10
@@ -74,6 +75,10 @@ DT_CONV_INFO_INTS = 8
 CONV_INFO_KEYS = ("cfg", "BM", "BN", "threads", "persistent", "grid_x", "grid_y", "total")
 CONV_KINDS = {"plain": 0, "pool": 1, "pool_both": 2, "s2d": 3, "gates": 4, "partial": 5}
 CONV_CFGS = {"128x128": 0, "128x64": 1, "256x128": 2, "256x256": 3, "64x128": 4}
+# dt_conv1 (include/mi355_dt.h): what h_info holds and the kernel instances it reports
+DT_CONV1_INFO_INTS = 6
+CONV1_INFO_KEYS = ("instance", "tpw", "grid_x", "grid_y", "grid_z", "fills_amax")
+CONV1_INSTANCES = {"mfma_f32": 0, "s3_u8_full": 1, "s3_u8": 2, "s3_f32": 3}
 
 _lib = None
 
@@ -197,6 +202,7 @@ def load_library():
     L.dt_wino_input.argtypes = [vp, vp, ci, ci, ci, ci, ci, cll, ci, ci, ci, ci, ci, vp, cll, geom]
     L.dt_wino_output.argtypes = [vp, vp, cll, ci, ci, ci, ci, ci, ci, vp, vp, cf, vp, ci, vp, ci, ci, vp, ci, vp, ci, ci, ci, geom]
     L.dt_conv_igemm.argtypes = [vp, ctypes.POINTER(ConvIgemmDesc), vp, vp, vp, vp, vp, vp, vp, vp, geom]
+    L.dt_conv1.argtypes = [vp, vp, ci, ci, ci, ci, vp, vp, cf, ci, ci, ci, vp, geom]
     L.dt_profile_enable.argtypes = [vp, ci]
     L.dt_graph_enable.argtypes = [vp, ci]
     L.dt_profile_reset.argtypes = [vp]
@@ -1442,6 +1448,29 @@ class Context(object):
         self._check(self.lib.dt_conv_igemm(self.h, ctypes.byref(d), _dptr(x), kp, bp, _dptr(wt), _dptr(out), _dptr(out2), _dptr(xproj), _dptr(cstate), info),
                     "dt_conv_igemm")
         return dict(zip(CONV_INFO_KEYS, [int(v) for v in info]))
+
+    # ---- conv_1's direct kernels alone (csrc/conv1.hip) ------------------
+    def conv1(self, frames, w, bias, out, slope=0.1, split=True, tpw=0, publish=False, batch=None):
+        """conv1.hip through its production launcher (dt_conv1), no detector configured.  frames [B,H,W,3] uint8 (a contiguous view at ANY byte
+        offset of its buffer) or float32; w numpy [27,32] (row 9 ky + 3 kx + ci, scale folded), bias numpy [32]; out a contiguous float32
+        [B,H/2,W/2,32] view.  split: pass the three-term tables (False: the fp32 MFMA kernel); tpw: 0 = the launcher's rule;
+        batch: the B to pass instead of frames.shape[0] (a refusal test's 0).  Returns the launcher's plan: instance (CONV1_INSTANCES), tpw, grid_x,
+        grid_y, grid_z, fills_amax."""
+        t = self.torch
+        assert frames.is_cuda and frames.is_contiguous() and frames.dim() == 4 and frames.shape[3] == 3
+        B, H, W, _ = frames.shape
+        assert out.is_cuda and out.is_contiguous() and out.dtype == t.float32 and out.numel() == B * (H // 2) * (W // 2) * 32
+        if batch is not None:
+            B = batch
+        w = np.ascontiguousarray(w, dtype=np.float32)
+        bias = np.ascontiguousarray(bias, dtype=np.float32)
+        assert w.shape == (27, 32) and bias.shape == (32,)
+        info = (ctypes.c_int * DT_CONV1_INFO_INTS)()
+        self._sync_stream()
+        self._check(self.lib.dt_conv1(self.h, _dptr(frames), self._frames_dtype(frames), int(B), int(H), int(W), w.ctypes.data_as(ctypes.c_void_p),
+                                      bias.ctypes.data_as(ctypes.c_void_p), float(slope), int(bool(split)), int(tpw), int(bool(publish)), _dptr(out), info),
+                    "dt_conv1")
+        return dict(zip(CONV1_INFO_KEYS, [int(v) for v in info]))
 
     # ---- profiling ------------------------------------------------------
     def profile_enable(self, on=True):
